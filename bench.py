@@ -3,9 +3,22 @@
 
 N = 1 (the headline): a "step" is one pass of the hot path (K1 front end -> K2 sync detect -> K3 scan -> K4 slice)
 over one resident capture: BASELINE.json configs[1], 1 channel x 600 s of synthetic C4FM IQ at 240 ksps
-(1.44e8 cf32 samples, 1.152 GB), generated in HBM before the timed region.  The same JSON line carries an
-`extra` array with the other single-GPU configurations (u8 input, config 3 end to end, config 4, config 5 on one GPU),
-each timed over its own >= 100 ms region after the headline one (`--no-extra` skips them).
+(1.44e8 cf32 samples, 1.152 GB), generated in HBM before the timed region.
+
+A plain run does only what the headline needs: set up, pre-warm and warm up, time the K steps, check what they produced
+(dibits == the modulator's symbols), write the last step's outputs if `--dump-outputs DIR` is given, print the line.  Its
+`roofline` comes from K1's HIP events inside the timed steps and the committed PMC record, at no extra run.  Everything
+else that takes runs of its own is behind `--full`: the per-kernel split of K2-K4, the serial step, torch's copy / sum
+bandwidth, `cpu_baseline` and its oracle gate, and the `extra` array with the other single-GPU configurations (u8 input,
+config 3 end to end, config 4, config 5 on one GPU), each timed over its own >= 100 ms region after the headline one
+(`--no-extra` / `--no-cpu` skip parts of a `--full` run).
+
+`--dump-outputs DIR` (N = 1): after the timed steps, what a caller of the timed step receives from its last one --
+`DIR/dibits.npy` (float32: every channel's valid dibits, one channel after the other) and `DIR/result.npy` (float64,
+[channels, fields]: the fields of p25fe_result_t in declaration order, anchor_out's inline, the reserved words left
+out) -- at most 64 MB in all; a larger dibit output is a fixed seeded sample whose positions are in `DIR/dibits_index.npy`.
+The capture is generated from fixed seeds, so the same arguments give the same inputs on every run and two builds can be
+compared output for output.
 
 N > 1 (one rank per GPU): the time-sharded step of the C ABI -- p25fe_shard_step of include/p25fe_rccl.h, driven through
 ctypes (p25rx_amd/rccl.py), RCCL inside libp25fe_rccl.so: halo send / recv to the right neighbour (hidden behind K1) ->
@@ -20,8 +33,8 @@ the contract's keys, value 0, `error` and the `stage` it happened in, and exits 
 because another rank failed first).
 
 Prints ONE JSON line on rank 0 (contract in the task statement), with `roofline` for the dominant kernel (K1) from HIP
-events recorded inside the library on the launch stream, and `cpu_baseline` from the CPU oracle timed on this box's
-host cores (rank 0, N = 1 only).
+events recorded inside the library on the launch stream, and (`--full`) `cpu_baseline` from the CPU oracle timed on this
+box's host cores (rank 0, N = 1 only).
 """
 import argparse
 import json
@@ -51,6 +64,7 @@ FLOPS_PER_SAMPLE = (2 * 2 * 31 + 2 * 2 * 41 + 30 + 10) / 5.0
 FLOPS_PER_SAMPLE_U8 = FLOPS_PER_SAMPLE + 4.0
 PMC_FILES = [os.path.join("profiles", "r06_k1_pmc.json"), os.path.join("profiles", "r05_k1_pmc.json"), os.path.join("profiles", "r04_k1_pmc.json")]
 PREWARM_MS = 150.0               # untimed steps before the W warm-up steps: the chip reaches its steady clock / power state
+DUMP_BYTES = 64 << 20            # --dump-outputs: all arrays together
 
 
 STAGE = ["start"]                # where the run is (N > 1: what a failure line names)
@@ -145,6 +159,36 @@ def timed(torch, step, steps, warmup, dist=None, finish=None):
 
 def steps_for(ms_guess, min_ms=120.0, lo=5, hi=2000):
     return int(max(lo, min(hi, np.ceil(min_ms / ms_guess))))
+
+
+def dump_outputs(out_dir, dibits, result):
+    """--dump-outputs: the last step's dibits [C, cap] and results [C, sizeof(p25fe_result_t)] (device tensors, complete) as
+    DIR/dibits.npy and DIR/result.npy (module docstring)."""
+    from p25rx_amd.frontend import parse_results
+    r = parse_results(result)
+    cols = []
+
+    def leaves(a):
+        for name in a.dtype.names:
+            if a.dtype[name].names:
+                leaves(a[name])
+            elif name != "reserved":
+                cols.append(a[name].astype(np.float64))
+    leaves(r)
+    res = np.stack(cols, axis=1)
+    dib = np.concatenate([dibits[c, :int(r[c]["n_dibits"])].cpu().numpy() for c in range(len(r))]).astype(np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    index_path = os.path.join(out_dir, "dibits_index.npy")
+    if os.path.exists(index_path):
+        os.unlink(index_path)                                    # (left by an earlier, larger run into the same directory)
+    room = DUMP_BYTES - res.nbytes - 4096                        # (and the files' headers)
+    if dib.nbytes > room:
+        # float32 dibit + float64 position per sampled element; the positions depend only on the output's length
+        idx = np.sort(np.random.default_rng(20251015).choice(len(dib), room // 12, replace=False))
+        dib = dib[idx]
+        np.save(index_path, idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "dibits.npy"), dib)
+    np.save(os.path.join(out_dir, "result.npy"), res)
 
 
 def k1_frac(fe, torch, step, n_samples, bytes_per_sample, reps=8):
@@ -577,7 +621,10 @@ def bench_channels(args, torch, dist, world, rank, local, dev, staged):
         dib, res = cs.step(fe, iq, dibits=dib, result=res)
 
     dt = timed(torch, step, args.steps, args.warmup, dist)
-    k1, ach, _ = k1_frac(fe, torch, step, cs.n_local * n, BYTES_PER_SAMPLE, reps=3)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dib, res)
+    if args.full:
+        k1, ach, _ = k1_frac(fe, torch, step, cs.n_local * n, BYTES_PER_SAMPLE, reps=3)
     cdev = torch.device("cpu") if staged else dev
     if dist:
         tt = torch.tensor([dt], dtype=torch.float64, device=cdev)
@@ -600,7 +647,7 @@ def bench_channels(args, torch, dist, world, rank, local, dev, staged):
         ok, ok_table = bool(okt[0].item()), bool(okt[1].item())
     if rank == 0:
         total = float(n) * args.channels * args.steps
-        print(json.dumps({
+        out = {
             "metric": "IQ Msamples/s through FM-demod+C4FM slice", "value": round(total / dt / 1e6, 1), "unit": "Msamples/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4),
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -609,10 +656,12 @@ def bench_channels(args, torch, dist, world, rank, local, dev, staged):
                        "sharding": "channel blocks, no collective on the data path; summaries all-gathered after the timed region"
                                    + (" (TEST HOOK: gloo through host copies, all ranks on one GPU)" if staged and world > 1 else ""),
                        "parity_gate": "dibits == modulator symbols (first and last local channel of every rank): %s" % ok,
-                       "table_gate": "gathered per-channel table complete and in channel order: %s" % ok_table},
-            "roofline": {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                         "frac": round(ach / HBM_PEAK_GBPS, 4), "traffic": None, "kernel": "k_frontend<cf32>",
-                         "kernel_ms": round(k1, 4), "algorithmic_bytes_per_launch": BYTES_PER_SAMPLE * cs.n_local * n}}))
+                       "table_gate": "gathered per-channel table complete and in channel order: %s" % ok_table}}
+        if args.full:
+            out["roofline"] = {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                               "frac": round(ach / HBM_PEAK_GBPS, 4), "traffic": None, "kernel": "k_frontend<cf32>",
+                               "kernel_ms": round(k1, 4), "algorithmic_bytes_per_launch": BYTES_PER_SAMPLE * cs.n_local * n}
+        print(json.dumps(out))
     if dist:
         dist.destroy_process_group()
     if not (ok and ok_table) and world == 1:
@@ -759,14 +808,23 @@ def main():
                     help="N > 1: the dibit shards go to rank 0 as whole rows + a compaction pass (root, the default: no host wait "
                          "anywhere in the step), as exactly their valid bytes received at their offsets of the ordered stream "
                          "(root_exact: one host wait for the offsets per step), all-gathered, or stay sharded (diagnostics)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need, in runs of their own: the per-kernel split, the "
+                         "serial step, copy / sum bandwidth, cpu_baseline, the extra configurations (module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="N = 1: write the last timed step's outputs as DIR/*.npy (module docstring)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--no-pipeline", action="store_true",
                     help="N = 1: strictly serial steps (K1 -> K2 -> K3 -> K4 on one stream) instead of p25fe_run_dev_pipelined")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra configurations (N = 1: the other single-GPU configs; N > 1 weak: the strong row)")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the extra configurations (N = 1: the other single-GPU configs; N > 1 weak: the strong row)")
     ap.add_argument("--strong-seconds", type=float, default=3600.0,
                     help="N > 1, --scaling weak: total length of the capture of the extra configs[4]-as-worded (strong) row")
     ap.add_argument("--cpu-seconds", type=float, default=600.0, help="length of the capture prefix timed on the CPU")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.dump_outputs and args.gpus > 1:
+        ap.error("--dump-outputs: N = 1 only")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return launch_ranks(args)                                 # (before torch is imported: this process never touches the GPU)
     if int(os.environ.get("WORLD_SIZE", "1")) == 1:
@@ -922,20 +980,24 @@ def run(args):
     if world > 1 and not staged:
         # where a step's time goes between the kernels: the library's own events around the three exchanges (last <= 64 steps)
         comm_ms = {k_: (round(v_, 4) if isinstance(v_, float) else v_) for k_, v_ in ss.comm_ms().items()}
-    # per-kernel split of the other kernels: a few extra steps OUTSIDE the timed region with events around every kernel
-    fe.profile_enable(1)
-    n_extra_steps = min(args.steps, 8)
-    for _ in range(n_extra_steps):
-        if world == 1:
-            fe.run_dev(iq, dibits=dibits, result=result)            # serial form: the split is that of the kernels alone
-        else:
-            step()
-    fe.join_dev()
-    torch.cuda.synchronize()
-    kms_all, _ = fe.profile_read()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, dibits, result)
+    # --full: per-kernel split of the other kernels: a few extra steps OUTSIDE the timed region with events around every kernel
+    kms_all = None
+    if args.full:
+        fe.profile_enable(1)
+        n_extra_steps = min(args.steps, 8)
+        for _ in range(n_extra_steps):
+            if world == 1:
+                fe.run_dev(iq, dibits=dibits, result=result)        # serial form: the split is that of the kernels alone
+            else:
+                step()
+        fe.join_dev()
+        torch.cuda.synchronize()
+        kms_all, _ = fe.profile_read()
     fe.profile_enable(False)
     serial_ms = None
-    if world == 1 and not args.no_pipeline:
+    if args.full and world == 1 and not args.no_pipeline:
         # the strictly serial form of the same step (K1 -> K2 -> K3 -> K4 on one stream), for comparison; not `value`
         ks = min(args.steps, 100)
         t0 = time.perf_counter()
@@ -944,7 +1006,7 @@ def run(args):
         torch.cuda.synchronize()
         serial_ms = (time.perf_counter() - t0) / ks * 1e3
     copy_gbps = sum_gbps = None
-    if world == 1:
+    if args.full and world == 1:
         # context for the roofline: what a plain device-to-device copy of the same capture moves on THIS box, right now
         # (read + write bytes / time over 30 back-to-back copies, torch's copy kernel) -- the practical ceiling of a
         # streaming kernel, against which K1's measured traffic is set below; not part of any timed region above
@@ -1024,8 +1086,8 @@ def run(args):
     gather_ran = ss.gather_ran() if world > 1 else "none"           # the mode the library EXECUTED (p25fe_shard_gather_ran)
     rccl_evidence = shard_evidence(ss, dist, world) if world > 1 else None
     strong_extra, strong_ok = None, True
-    if world > 1 and not strong and not args.no_extra:
-        # configs[4] AS WORDED rides along as an extra row of the default (weak) line: one 3 600 s capture cut N ways
+    if args.full and world > 1 and not strong and not args.no_extra:
+        # configs[4] AS WORDED rides along as an extra row of a --full weak line: one 3 600 s capture cut N ways
         try:
             stage("the strong row (configs[4] as worded): shard create + steps")
             strong_extra, strong_ok = strong_row(torch, dist, args, world, rank, local, dev, staged, max(3, min(args.steps, 100)),
@@ -1106,11 +1168,12 @@ def run(args):
                          "whole_step": {"algorithmic_bytes_per_sample": 8.02,
                                         "achieved": round(8.02 * n * world * args.steps / dt / 1e9, 1),
                                         "frac_of_peak_x_gpus": round(8.02 * n * args.steps / dt / 1e9 / HBM_PEAK_GBPS, 4)},
-                         "other_kernels_ms": {"k_detect": round(kms_all[1] / n_extra_steps, 4),
-                                              "k_scan_tiles": round(kms_all[2] / n_extra_steps, 4),
-                                              "k_slice": round(kms_all[3] / n_extra_steps, 4),
-                                              "note": "from extra SERIAL steps after the timed region, HIP events around every kernel"
-                                                      + ("; N > 1: RCCL time is in none of them" if world > 1 else "")}},
+                         "other_kernels_ms": ({"k_detect": round(kms_all[1] / n_extra_steps, 4),
+                                               "k_scan_tiles": round(kms_all[2] / n_extra_steps, 4),
+                                               "k_slice": round(kms_all[3] / n_extra_steps, 4),
+                                               "note": "from extra SERIAL steps after the timed region, HIP events around every kernel"
+                                                       + ("; N > 1: RCCL time is in none of them" if world > 1 else "")}
+                                              if kms_all is not None else None)},
         }
         if world == 1:
             out["config"]["prewarm"] = "%d untimed steps (>= %.0f ms) before the W warm-up steps" % (n_prewarm, PREWARM_MS)
@@ -1139,7 +1202,7 @@ def run(args):
         if gather_ok is not None:
             out["config"]["gather_gate"] = ("gathered stream holds every shard at its resolved offset (length, sum and "
                                             "position-weighted sum of every rank's dibits): %s" % gather_ok)
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             ncpu = min(n, int(args.cpu_seconds * 240000))
             host = iq[:ncpu].cpu().numpy().view(np.complex64).reshape(-1)
             cb, cpu_dib = cpu_baseline(host, "first %.0f s" % (ncpu / 240000))
@@ -1148,7 +1211,7 @@ def run(args):
             # the oracle on the same samples must agree with the GPU bit for bit (full prefix)
             out["config"]["oracle_gate"] = "GPU dibits == oracle dibits on the CPU sample: %s" % bool(
                 np.array_equal(cpu_dib[:kk - 1], got[:kk - 1]))
-        if world == 1 and not args.no_extra:
+        if args.full and world == 1 and not args.no_extra:
             try:
                 out["extra"] = run_extras(torch, dev, args, iq, truth)
             except Exception as e:                         # the headline line must not be lost to an extra

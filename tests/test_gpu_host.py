@@ -237,8 +237,8 @@ def test_bench_two_ranks_time_shards_host_staged(scaling):
     env = dict(os.environ, P25FE_BENCH_HOST_STAGED="1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                          "--gpus", "2", "--steps", "3", "--warmup", "1", "--seconds", "60", "--strong-seconds", "40"]
-                         + (["--scaling", "strong", "--gather", "root_exact"] if scaling == "strong" else []),     # weak + rows are the defaults (the driver's command)
+                          "--gpus", "2", "--steps", "3", "--warmup", "1", "--seconds", "60", "--strong-seconds", "40", "--full"]
+                         + (["--scaling", "strong", "--gather", "root_exact"] if scaling == "strong" else []),     # weak is the default; --full adds the strong row
                          env=env, capture_output=True, text=True, timeout=280)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith('{"metric"')]
@@ -276,6 +276,30 @@ def test_bench_n2_exits_nonzero_on_a_false_gate():
     assert out.returncode != 0
     line = [l for l in out.stdout.splitlines() if l.startswith('{"metric"')]
     assert len(line) == 1 and json.loads(line[0])["config"]["gather_gate"].endswith("False")
+
+
+@pytest.mark.timeout(300)
+def test_bench_plain_run_dumps_the_same_outputs_twice(tmp_path):
+    """`bench.py --gpus 1` without --full: the headline line and nothing that takes runs of its own; --dump-outputs writes the last
+    timed step's dibits and results, the same arrays on a second run with the same arguments."""
+    import json
+    import sys
+    lines = []
+    for k in ("a", "b"):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                              "--seconds", "10", "--dump-outputs", str(tmp_path / k)], capture_output=True, text=True, timeout=280)
+        assert out.returncode == 0, out.stderr[-2000:]
+        lines.append(json.loads([l for l in out.stdout.splitlines() if l.startswith('{"metric"')][-1]))
+    d = lines[0]
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["config"]["parity_gate"].endswith("True")
+    assert "extra" not in d and "cpu_baseline" not in d and "serial_ms_per_step" not in d["config"]
+    assert d["roofline"]["other_kernels_ms"] is None and d["roofline"]["kernel_ms"] > 0
+    dib = [np.load(tmp_path / k / "dibits.npy") for k in ("a", "b")]
+    res = [np.load(tmp_path / k / "result.npy") for k in ("a", "b")]
+    assert dib[0].dtype == np.float32 and res[0].dtype == np.float64 and res[0].shape[0] == 1
+    assert res[0][0, 1] == len(dib[0]) > 10 * 240000 // 50 - 100          # column 1 = n_dibits: every dibit of the capture
+    assert set(np.unique(dib[0])) <= {0.0, 1.0, 2.0, 3.0} and not (tmp_path / "a" / "dibits_index.npy").exists()
+    assert np.array_equal(dib[0], dib[1]) and np.array_equal(res[0], res[1])
 
 
 @pytest.mark.parametrize("mode", [0, 1])

@@ -33,10 +33,10 @@ def test_library_host_side_under_asan_ubsan():
 
 @pytest.mark.gpu
 def test_library_streaming_entry_points_under_host_asan():
-    """On the GPU box (the sanitizer build travels prebuilt in build/): the host-buffer entry points -- pinned staging,
-    history and tail bookkeeping, capacity / format errors, state export / import -- with the host side instrumented."""
-    exe = os.path.join(ROOT, "build", "abi_host_asan")
-    if not os.path.exists(exe):
-        pytest.skip("sanitizer build not present")
-    out = run_clean(exe)
+    """On the GPU box (the same host-side sanitizer build as above, made here when a CPU run has not left it in build/): the
+    host-buffer entry points -- pinned staging, history and tail bookkeeping, capacity / format errors, state export / import --
+    with the host side instrumented."""
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "p25rx_amd", "csrc"), "asan"],
+                          env=dict(os.environ, HIPCC=os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")))
+    out = run_clean(os.path.join(ROOT, "build", "abi_host_asan"))
     assert "streaming entry points exercised" in out

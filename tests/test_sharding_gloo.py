@@ -227,6 +227,38 @@ def test_bench_plain_invocation_reaches_the_launcher():
     assert d["value"] == 0.0 and d["n_gpus"] == 2 and "No HIP GPUs" in d["error"] and d["stage"] and d["metric"].startswith("IQ Msamples/s")
 
 
+def test_bench_dump_outputs_stays_in_budget(tmp_path):
+    """bench.py --dump-outputs on host tensors: every channel's valid dibits in order and the result fields as floats; an output over
+    the 64 MB budget becomes a seeded sample whose positions are written beside it (and are gone again after a smaller dump)."""
+    import sys
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    from p25rx_amd._lib import RESULT_DTYPE
+
+    def outputs(channels, cap, nd):
+        r = np.zeros(channels, dtype=RESULT_DTYPE)
+        r["n_dibits"], r["first_event"], r["anchor_out"]["hi"] = nd, -1, 1.5
+        dib = torch.randint(0, 4, (channels, cap), dtype=torch.uint8, generator=torch.Generator().manual_seed(channels))
+        return dib, torch.from_numpy(r.view(np.uint8).reshape(channels, -1).copy())
+
+    d = str(tmp_path / "dump")
+    dib, res = outputs(2, 1000, 900)
+    bench.dump_outputs(d, dib, res)
+    got, fields = np.load(os.path.join(d, "dibits.npy")), np.load(os.path.join(d, "result.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, torch.cat([dib[0, :900], dib[1, :900]]).numpy())
+    assert fields.dtype == np.float64 and fields.shape == (2, 15) and list(fields[0, :2]) == [0.0, 900.0] and fields[0, 4] == 1.5
+    dib, res = outputs(8, 3000000, 2900000)                            # 23.2 M dibits: 93 MB as float32
+    bench.dump_outputs(d, dib, res)
+    got, idx = np.load(os.path.join(d, "dibits.npy")), np.load(os.path.join(d, "dibits_index.npy"))
+    assert sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d)) <= bench.DUMP_BYTES
+    whole = np.concatenate([dib[c, :2900000].numpy() for c in range(8)])
+    assert idx.dtype == np.float64 and np.array_equal(got, whole[idx.astype(np.int64)])
+    bench.dump_outputs(d, *outputs(1, 1000, 900))
+    assert sorted(os.listdir(d)) == ["dibits.npy", "result.npy"]
+
+
 def test_bench_watchdog_ends_a_rank_stuck_in_the_rendezvous():
     """A rank whose peers never arrive (a dead GPU, a wedged RCCL bootstrap) must not hang until somebody else's timeout: after
     P25FE_BENCH_WATCHDOG_S rank 0 prints the failure line -- with the stage it was stuck in -- and the process ends with code 5."""

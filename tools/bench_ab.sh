@@ -11,7 +11,7 @@ for r in $(seq 1 $R); do
       tag=${spec%%:*}; envs=""
       if [[ "$spec" == *:* ]]; then envs=$(echo "${spec#*:}" | tr ',' ' '); fi
       lib=$PWD/build/variants/libp25fe_$tag.so; [ "$tag" == "cur" ] && lib=$PWD/p25rx_amd/libp25fe.so
-      line=$(env $envs P25FE_LIB=$lib python3 bench.py --no-extra --no-cpu --steps $K --warmup $W 2>/dev/null | tail -1)
+      line=$(env $envs P25FE_LIB=$lib python3 bench.py --full --no-extra --no-cpu --steps $K --warmup $W 2>/dev/null | tail -1)
       python3 - "$spec" "$K" "$line" <<'PY'
 import json, sys
 r = json.loads(sys.argv[3])

@@ -6,7 +6,7 @@ mkdir -p "$OUT"
 run() { # name, env..., -- args
   local name=$1; shift
   local envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-  env "${envs[@]}" python3 bench.py --no-extra --no-cpu "$@" 2>>"$OUT/err.log" | tail -1 >> "$OUT/$name.jsonl"
+  env "${envs[@]}" python3 bench.py --full --no-extra --no-cpu "$@" 2>>"$OUT/err.log" | tail -1 >> "$OUT/$name.jsonl"
 }
 for r in $(seq 1 "$ROUNDS"); do
   for S in "20 5" "400 20"; do

@@ -7,9 +7,9 @@ ROOT=$PWD
 OUT=$ROOT/gpurun_out/prof_$TAG; mkdir -p $OUT
 export TMPDIR=/tmp
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python3 $ROOT/bench.py --steps 20 --warmup 5 --no-cpu --no-extra > $OUT/stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- python3 $ROOT/bench.py --full --steps 20 --warmup 5 --no-cpu --no-extra > $OUT/stats.log 2>&1
 grep -o '{"metric.*' $OUT/stats.log > $OUT/bench_under_rocprof.json
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_serial -o stats -- python3 $ROOT/bench.py --steps 20 --warmup 5 --no-cpu --no-extra --no-pipeline > $OUT/stats_serial.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_serial -o stats -- python3 $ROOT/bench.py --full --steps 20 --warmup 5 --no-cpu --no-extra --no-pipeline > $OUT/stats_serial.log 2>&1
 # the other kernels at the bench's own sizes
 mkdir -p $OUT/kb_u8 $OUT/kb_wide $OUT/kb_spec
 echo "configs[1] as u8: 1 channel x 600 s = 1.44e8 samples, 20 rounds of run_u8 (K1<u8> planar -> K2 -> K3 -> K4) and lin_u8" > $OUT/kb_u8/WORKLOAD

@@ -58,7 +58,7 @@ for sub, log, what in (("stats", "stats.log", "pipelined steps (the bench's defa
     if not rows:
         continue
     b = bench_json(log)
-    print("== rocprofv3 --kernel-trace -- python3 bench.py --steps 20 --warmup 5 --no-cpu --no-extra [%s]" % what)
+    print("== rocprofv3 --kernel-trace -- python3 bench.py --full --steps 20 --warmup 5 --no-cpu --no-extra [%s]" % what)
     k1 = [dur for _, dur, k in rows if k.startswith("k_frontend")]
     if b and "k1_launch_range" in b.get("config", {}):
         first, cnt = b["config"]["k1_launch_range"]

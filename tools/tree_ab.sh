@@ -1,15 +1,16 @@
 #!/bin/bash
 # Same-box, interleaved A/B of whole TREES through their own bench.py (the libraries' ABIs differ, so each tree runs its own
 # driver): build/r5tree (git archive of round 5's last commit) and the working tree.
-#   usage: bash tools/tree_ab.sh <rounds> [extras=0|1]     extras=1: the full default run (configs[3] / [4] on one GPU are extras)
+#   usage: bash tools/tree_ab.sh <rounds> [extras=0|1]     extras=1: the --full run with its extras (configs[3] / [4] on one GPU)
 R=${1:-2}; EX=${2:-0}
 for r in $(seq 1 $R); do
   for t in build/r3tree build/r5tree .; do
     [ -f $t/bench.py ] || continue
+    full=$(grep -q -- '"--full"' $t/bench.py && echo --full)     # (older trees measure everything by default)
     if [ "$EX" == "1" ]; then
-      line=$(cd $t && python3 bench.py --steps 20 --warmup 5 --no-cpu 2>/dev/null | tail -1)
+      line=$(cd $t && python3 bench.py $full --steps 20 --warmup 5 --no-cpu 2>/dev/null | tail -1)
     else
-      line=$(cd $t && python3 bench.py --steps 400 --warmup 20 --no-cpu --no-extra 2>/dev/null | tail -1)
+      line=$(cd $t && python3 bench.py $full --steps 400 --warmup 20 --no-cpu --no-extra 2>/dev/null | tail -1)
     fi
     python3 - "$t" "$line" <<'PY'
 import json, sys
