@@ -649,174 +649,189 @@ static void prof_k1_events(p25fe_t* h, hipEvent_t* e0, hipEvent_t* e1)
 // --------------------------------------------------------------------------------------------
 // internal launchers
 // --------------------------------------------------------------------------------------------
-static int ensure_chunk_scratch(p25fe_t* h)
+// One K1 launch (k_frontend, or k_chunk when `chunk` is set).  The output is the linear baseband (`bb`, from output 0 on) or --
+// `planar` -- the handle's planar scratch, from the layout's own first output on (a block boundary of the layout, or 80 outputs
+// in front of the receiver's 240-sample history).
+// part: which segments of a time shard's range run -- every one; only those whose input window lies inside the owned samples
+// (the main launch, runs while the halo is still on the wire); the others (the head, after the halo has arrived)
+enum K1Part { K1_ALL = 0, K1_MAIN = 1, K1_HEAD = 2 };
+struct K1Launch {
+    const void* src = nullptr;             // owned sample 0 of channel 0, n_hist valid samples in front of it
+    int fmt = P25FE_FMT_CF32;
+    size_t ch_stride = 0, n_hist = 0, n = 0;
+    uint64_t abs0 = 0;
+    float* bb = nullptr; size_t bb_stride = 0;      // linear output ...
+    float* power_dbm = nullptr;            // ... and (nullable) its power per channel
+    bool planar = false;
+    K1Part part = K1_ALL;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;        // (nullable) attached to K1's dispatch: begin / end of the kernel
+    const ChunkRecvArgs* chunk = nullptr;  // (nullable, planar only) k_chunk: K1 plus the one-tile receiver run by each channel's last workgroup
+    long* head_end = nullptr;              // (nullable, K1_HEAD) receives the planar position up to which the head's segments write
+    unsigned* done_flag = nullptr; unsigned done_seq = 0u;   // (nullable, planar) the launch's last workgroup publishes done_flag[0] = done_seq
+    hipStream_t stream = nullptr;
+};
+
+// What a K1Launch comes to: the segment geometry and the part split (as the kernel's arguments), the kernel's form, grid and LDS.
+// Arithmetic only.
+struct K1Plan {
+    bool empty;                            // nothing to launch: no output, or no segment on this side of the part split
+    K1Args a;                              // complete but for power_partial (the launch allocates it)
+    bool u8, ct; int pk;                   // which kernel: format, immediate coefficients, FIR outputs per lane
+    long n_seg;                            // segments of the whole range (a.seg_first, a.seg_count: this launch's)
+    long head_end;                         // planar position up to which the head's segments write (part != K1_ALL)
+    size_t lds;
+};
+static int k1_plan(const p25fe_t* h, const K1Launch& L, K1Plan* p)
 {
-    if (h->chunk_cnt.p) return P25FE_OK;
-    HIPCHK(h, h->chunk_cnt.ensure(sizeof(unsigned) * (size_t)h->C));
-    HIPCHK(h, hipMemsetAsync(h->chunk_cnt.p, 0, sizeof(unsigned) * (size_t)h->C, h->stream));
-    return P25FE_OK;
-}
-static int launch_frontend(p25fe_t* h, const void* d_x, int fmt, size_t ch_stride, size_t n_hist, size_t n,
-                           uint64_t abs0, long m_begin, float* d_bb, size_t bb_stride, float* d_power_dbm,
-                           hipStream_t st, const PlanarGeo* planar = nullptr, int part = 0, hipEvent_t ev0 = nullptr,
-                           hipEvent_t ev1 = nullptr, const ChunkRecvArgs* chunk = nullptr, long* head_end = nullptr,
-                           unsigned* done_flag = nullptr, unsigned done_seq = 0u)
-{
-    // head_end (nullable, part 2): receives the planar position up to which this launch's segments write
-    // done_flag (nullable, planar): the launch's last workgroup publishes done_flag[0] = done_seq (K1Args.done_flag)
-    // chunk (nullable, planar only): launch k_chunk -- K1 plus the one-tile receiver run by each channel's last workgroup
-    // ev0 / ev1 (nullable): events attached to K1's dispatch (begin / end of the kernel)
-    // part: 0 = every segment; 1 = only the segments whose input window lies inside the owned samples (a shard's main
-    // launch, runs while the halo is still on the wire); 2 = the others (the shard's head, after the halo has arrived)
+    const int fmt = L.fmt;
     if (fmt != P25FE_FMT_CF32 && fmt != P25FE_FMT_U8) return P25FE_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(d_x) & 15u) != 0) return P25FE_ERR_ARG;     // 16-B vector loads
-    if (h->C > 1 && (ch_stride % (fmt == P25FE_FMT_CF32 ? 2 : 8)) != 0) return P25FE_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(L.src) & 15u) != 0) return P25FE_ERR_ARG;   // 16-B vector loads
+    if (h->C > 1 && (L.ch_stride % (fmt == P25FE_FMT_CF32 ? 2 : 8)) != 0) return P25FE_ERR_ARG;
+    if (L.chunk && (!L.planar || L.part)) return P25FE_ERR_ARG;
     const bool pro = seg_prologue(fmt);                            // p25fe_kernels.hip: segment prologue (u8) or recomputed halo (cf32)
-    // planar output: the first output K1 produces is the form's (a block boundary of the layout, or 80 outputs in front of
-    // the receiver's 240-sample history) -- the caller's value is ignored
-    if (planar) m_begin = pro ? -(long)PLPAD - h->look : -(long)HIST_BB - h->look;
-    const size_t n_out = p25fe_n_baseband_h(h, abs0, n);
+    const long m_begin = !L.planar ? 0 : (pro ? -(long)PLPAD - h->look : -(long)HIST_BB - h->look);
+    const size_t n_out = p25fe_n_baseband_h(h, L.abs0, L.n);
     const long total = (long)n_out - m_begin;
-    if (total <= 0) {
-        // power_dbm of an empty chunk: the reference divides 0 by 0 (src/demod.rs:123-134) -> NaN (0xffffffff is a quiet NaN)
-        if (d_power_dbm) HIPCHK(h, hipMemsetAsync(d_power_dbm, 0xff, sizeof(float) * (size_t)h->C, st));
-        return P25FE_OK;
-    }
+    K1Args& a = p->a;
+    a.m_begin = m_begin; a.n_out = (long)n_out; p->head_end = 0;
+    p->empty = total <= 0;
+    if (p->empty) return P25FE_OK;
     // Segments are SHORT: three sub-tiles per one-wave workgroup.  Measured on config 2 (profiles/): one long
     // segment per resident wave (44 sub-tiles, no tail round) ran K1 in 0.305 ms, 2-4 sub-tiles per workgroup in
     // 0.23-0.27 ms depending on the box -- neighbouring workgroups then stream neighbouring DRAM pages and the
     // dispatcher balances the CUs, which outweighs recomputing the 50-sample filter halo once per segment (5.5 % at
     // 3 sub-tiles; A/B on one box, three rounds: 2 -> 0.275, 3 -> 0.264, 4 -> 0.269 ms).  P25FE_SUBS overrides.
-    const int pk = (planar || h->long_taps || h->variant == P25FE_VARIANT_SPECIALIZED) ? 5 : h->k1_p;
+    const int pk = (L.planar || h->long_taps || h->variant == P25FE_VARIANT_SPECIALIZED) ? 5 : h->k1_p;
     const int t1 = h->long_taps ? TMAX : T1;
     const long sub = (long)WV * pk;
     static const long subs_env = [] { const char* e = getenv("P25FE_SUBS"); return e ? atol(e) : 0L; }();
     // (round 2: the instruction-bound u8 kernel prefers longer segments -- less halo recomputed: 3 -> 239, 6 -> 231 us on one
     // box; with the final build 4 -> 222 / 216, 6 -> 217 / 215, 9 -> 212 / 209, 12 -> 216 / 205 us under rocprofv3)
     long subs = subs_env > 0 ? subs_env : (fmt == P25FE_FMT_U8 ? 9 : 3);
-    if (chunk) subs = 1;                                            // a chunk is latency: every sub-tile its own workgroup
+    if (L.chunk) subs = 1;                                          // a chunk is latency: every sub-tile its own workgroup
     if (subs > 32768) subs = 32768;
     // the post-discriminator filter's length as far as the kernel's GEOMETRY goes (frontend_body's T3): the handle's own for the
     // immediate-coefficient kernels, the ABI's ceiling for the generic ones; the halo form's recomputed halo follows the
     // handle's real length either way (the generic kernels take it as an argument)
-    const bool ct_k = h->variant != P25FE_VARIANT_GENERIC;
+    const bool ct = h->variant != P25FE_VARIANT_GENERIC;
     const int t2e = h->long_taps ? TMAX : T2;
-    const int t3geo = ct_k ? h->n_avg : TMAX;
+    const int t3geo = ct ? h->n_avg : TMAX;
     const long segh = seg_halo_for(h->n_avg, t2e);
     const long seg_len = pro ? subs * sub : (sub - segh) + (subs - 1) * sub;
     // what a segment needs in front of its first output: the prologue's decimator outputs, or the recomputed halo
     const long nd = pro ? t3geo + t2e - 1 : segh;
-    // a time shard's launches (part != 0): the segments in front of the first one whose input lies inside the owned samples
+    // a time shard's launches (part != K1_ALL): the segments in front of the first one whose input lies inside the owned samples
     // are ONE sub-tile long (K1Args.lead_segs) -- the head is then a few one-sub-tile workgroups side by side
     const long lead_len = pro ? sub : sub - segh;
-    const long o0l = (long)(((uint64_t)h->phase + 5 - abs0 % 5) % 5);
+    const long o0 = (long)(((uint64_t)h->phase + 5 - L.abs0 % 5) % 5);
     long lead = 0;
-    if (part && subs > 1 && !chunk)
-        while (lead < 64 && o0l + DEC * (m_begin + lead * lead_len - nd) - (t1 - 1) < 0 && lead * lead_len < total) ++lead;
+    if (L.part && subs > 1 && !L.chunk)
+        while (lead < 64 && o0 + DEC * (m_begin + lead * lead_len - nd) - (t1 - 1) < 0 && lead * lead_len < total) ++lead;
     auto seg_start = [&](long k) { return k < lead ? m_begin + k * lead_len : m_begin + lead * lead_len + (k - lead) * seg_len; };
     const long n_seg = lead * lead_len >= total ? (total + lead_len - 1) / lead_len : lead + (total - lead * lead_len + seg_len - 1) / seg_len;
     const long pl_shift = PLPAD + h->look;       // the general receiver sees the range h->look samples late (p25fe_recv.hip)
-    if (planar && pro && (m_begin + pl_shift < 0 || (m_begin + pl_shift) % PL_BLK != 0 || seg_len % PL_BLK != 0)) return P25FE_ERR_ARG;
+    if (L.planar && pro && (m_begin + pl_shift < 0 || (m_begin + pl_shift) % PL_BLK != 0 || seg_len % PL_BLK != 0)) return P25FE_ERR_ARG;
     // (halo form: the outputs a segment recomputes and drops may lie in front of planar position 0 -- with a 160-output halo the
     // range's first segment starts 80 positions in front of it; they are never stored, only whole bytes of the planes are)
-    if (planar && !pro && (m_begin + pl_shift < 0 || (m_begin + pl_shift) % 80 != 0 || seg_len % 80 != 0)) return P25FE_ERR_ARG;
-    if (planar && n_out > MAX_RANGE_BB) return P25FE_ERR_ARG;
-
-    K1Args a;
-    a.x = d_x;
-    a.ch_stride = (long)ch_stride;
-    a.n_hist = (long)n_hist;
-    a.n_new = (long)n;
-    a.o0 = (int)o0l;
-    a.bb = d_bb;
-    a.bb_stride = (long)bb_stride;
-    a.n_out = (long)n_out;
-    a.subs_per_seg = (int)subs;
-    a.seg_first = 0;
-    long seg_count = n_seg;
-    if (part) {
-        if (d_power_dbm) return P25FE_ERR_ARG;
+    if (L.planar && !pro && (m_begin + pl_shift < 0 || (m_begin + pl_shift) % 80 != 0 || seg_len % 80 != 0)) return P25FE_ERR_ARG;
+    if (L.planar && n_out > MAX_RANGE_BB) return P25FE_ERR_ARG;
+    long seg_first = 0, seg_count = n_seg;
+    if (L.part) {
+        if (L.power_dbm) return P25FE_ERR_ARG;
         // segment k reads input from o0 + 5 (its first output - nd) - (T1 - 1) on
         long k_min = 0;
-        while (k_min < n_seg && o0l + DEC * (seg_start(k_min) - nd) - (t1 - 1) < 0) ++k_min;
-        if (part == 1) { a.seg_first = (int)k_min; seg_count = n_seg - k_min; }
+        while (k_min < n_seg && o0 + DEC * (seg_start(k_min) - nd) - (t1 - 1) < 0) ++k_min;
+        if (L.part == K1_MAIN) { seg_first = k_min; seg_count = n_seg - k_min; }
         else seg_count = k_min;
-        if (head_end) *head_end = seg_start(k_min) - m_begin;
-        if (seg_count <= 0) return P25FE_OK;
+        p->head_end = seg_start(k_min) - m_begin;
+        p->empty = seg_count <= 0;
+        if (p->empty) return P25FE_OK;
     }
-    a.seg_count = (int)seg_count;
-    a.n_ch = h->C;
-    a.m_begin = m_begin;
-    a.power_partial = nullptr;
+    if (seg_count * (long)h->C > 0x7fffffffL) return P25FE_ERR_ARG;
+    p->u8 = fmt == P25FE_FMT_U8; p->ct = ct; p->pk = pk; p->n_seg = n_seg;
+    a.x = L.src; a.ch_stride = (long)L.ch_stride; a.n_hist = (long)L.n_hist; a.n_new = (long)L.n; a.o0 = (int)o0; a.n_ch = h->C;
+    a.bb = L.bb; a.bb_stride = (long)L.bb_stride; a.power_partial = nullptr;
+    a.subs_per_seg = (int)subs; a.seg_first = (int)seg_first; a.seg_count = (int)seg_count; a.lead_segs = (int)lead; a.seg_halo = (int)segh;
     a.bbp = nullptr; a.bbp_ch_stride = 0; a.bits = nullptr; a.bits_ch_stride = 0; a.pl_shift = (int)pl_shift;
-    a.done_flag = planar ? done_flag : nullptr; a.done_seq = done_seq;
-    a.lead_segs = (int)lead;
-    a.seg_halo = (int)segh;
-    if (planar) {
-        a.bbp = h->pl_f.as<float>(); a.bbp_ch_stride = (long)planar->floats();
-        a.bits = h->pl_bits.as<uint8_t>(); a.bits_ch_stride = (long)(4 * planar->words());
+    a.done_flag = L.planar ? L.done_flag : nullptr; a.done_seq = L.done_seq;
+    if (L.planar) {
+        const PlanarGeo g(n_out);
+        a.bbp = h->pl_f.as<float>(); a.bbp_ch_stride = (long)g.floats();
+        a.bits = h->pl_bits.as<uint8_t>(); a.bits_ch_stride = (long)(4 * g.words());
     }
-    if (d_power_dbm) {
-        HIPCHK(h, h->power_partial.ensure(sizeof(float) * (size_t)h->C * (size_t)n_seg));
-        a.power_partial = h->power_partial.as<float>();
-    }
-    const long n_items = seg_count * (long)h->C;
-    if (n_items > 0x7fffffffL) return P25FE_ERR_ARG;
-    const Taps* dt = h->d_taps.as<Taps>();
-    const bool u8 = fmt == P25FE_FMT_U8;
-    const dim3 grid((unsigned)seg_count, (unsigned)h->C);            // one one-wave workgroup per (segment, channel)
     // LDS per workgroup: [d carry | window] (+ taps: generic kernels) (+ the u8 table: generic u8 kernels, and specialised ones
     // whose table is not affine).  Immediate-coefficient kernels never touch the taps area at the end of the layout: not
     // allocated.  (13 376 B per wave is 11 waves per CU; a 12th would need 13 312 -- trimming to that changed nothing.)
-    const bool ct = h->variant != P25FE_VARIANT_GENERIC;
-    const bool lut = u8 && (!ct || h->u8_lut_mode);
-    size_t lds = h->long_taps ? k1_lds_bytes<Geo<5, 1>>(ct, lut, t3geo) : (pk == 3 ? k1_lds_bytes<Geo<3>>(ct, lut, t3geo) : k1_lds_bytes<Geo<5>>(ct, lut, t3geo));
+    const bool lut = p->u8 && (!ct || h->u8_lut_mode);
+    p->lds = h->long_taps ? k1_lds_bytes<Geo<5, 1>>(ct, lut, t3geo) : (pk == 3 ? k1_lds_bytes<Geo<3>>(ct, lut, t3geo) : k1_lds_bytes<Geo<5>>(ct, lut, t3geo));
     // (experiments: extra dynamic LDS per workgroup = fewer resident waves per CU; the occupancy sensitivity of docs/MEASUREMENTS.md)
     static const size_t lds_pad_env = [] { const char* e = getenv("P25FE_K1_LDS_PAD"); return e ? (size_t)atol(e) : (size_t)0; }();
-    lds += lds_pad_env;
-    ChunkTail tail;
-    if (chunk) {
-        if (!planar || part) return P25FE_ERR_ARG;
-        int rc = ensure_chunk_scratch(h);
-        if (rc) return rc;
-        tail.r = *chunk; tail.counter = h->chunk_cnt.as<unsigned>(); tail.wg_per_ch = (int)seg_count;
+    p->lds += lds_pad_env;
+    return P25FE_OK;
+}
+
+// The built-in kernels: one instantiation per (format, coefficient form, outputs per lane, output layout, long taps) in use.
+// (Long taps are never the build's own numbers: the generic form, five outputs per lane; every planar kernel has five too.)
+using K1Kernel = void (*)(K1Args, const Taps*);
+using ChunkKernel = void (*)(K1Args, const Taps*, ChunkTail);
+template <int FMT> static K1Kernel k1_kernel_of(bool ct, int pk, bool planar, bool long_taps)
+{
+    if (long_taps) return planar ? k_frontend<FMT, false, 5, OUT_PLANAR, 1> : k_frontend<FMT, false, 5, OUT_LINEAR, 1>;
+    if (planar) return ct ? k_frontend<FMT, true, 5, OUT_PLANAR, 0> : k_frontend<FMT, false, 5, OUT_PLANAR, 0>;
+    if (pk == 3) return ct ? k_frontend<FMT, true, 3, OUT_LINEAR, 0> : k_frontend<FMT, false, 3, OUT_LINEAR, 0>;
+    return ct ? k_frontend<FMT, true, 5, OUT_LINEAR, 0> : k_frontend<FMT, false, 5, OUT_LINEAR, 0>;
+}
+template <int FMT> static ChunkKernel chunk_kernel_of(bool ct, bool long_taps)
+{
+    if (long_taps) return k_chunk<FMT, false, 1>;
+    return ct ? k_chunk<FMT, true, 0> : k_chunk<FMT, false, 0>;
+}
+
+static int launch_k1(p25fe_t* h, const K1Launch& L)
+{
+    K1Plan p;
+    if (int rc = k1_plan(h, L, &p)) return rc;
+    if (L.head_end) *L.head_end = p.head_end;
+    hipStream_t st = L.stream;
+    if (p.empty) {
+        // power_dbm of an empty chunk: the reference divides 0 by 0 (src/demod.rs:123-134) -> NaN (0xffffffff is a quiet NaN)
+        if (L.power_dbm) HIPCHK(h, hipMemsetAsync(L.power_dbm, 0xff, sizeof(float) * (size_t)h->C, st));
+        return P25FE_OK;
     }
+    K1Args& a = p.a;
+    if (L.power_dbm) {
+        HIPCHK(h, h->power_partial.ensure(sizeof(float) * (size_t)h->C * (size_t)p.n_seg));
+        a.power_partial = h->power_partial.as<float>();
+    }
+    ChunkTail tail;
+    if (L.chunk) {
+        if (!h->chunk_cnt.p) {                                      // the channels' arrival counters: zero between launches
+            HIPCHK(h, h->chunk_cnt.ensure(sizeof(unsigned) * (size_t)h->C));
+            HIPCHK(h, hipMemsetAsync(h->chunk_cnt.p, 0, sizeof(unsigned) * (size_t)h->C, h->stream));
+        }
+        tail.r = *L.chunk; tail.counter = h->chunk_cnt.as<unsigned>(); tail.wg_per_ch = a.seg_count;
+    }
+    const Taps* dt = h->d_taps.as<Taps>();
+    const dim3 grid((unsigned)a.seg_count, (unsigned)h->C);          // one one-wave workgroup per (segment, channel)
     if (h->variant == P25FE_VARIANT_SPECIALIZED) {
         // kernels compiled for this handle's numbers (p25fe_jit.cpp): same source, same launch shape, C entry points
-        hipFunction_t f = h->jit_fn[u8 ? 1 : 0][chunk ? 2 : (planar ? 1 : 0)];
+        hipFunction_t f = h->jit_fn[p.u8 ? 1 : 0][L.chunk ? 2 : (L.planar ? 1 : 0)];
         void* params[3] = {&a, &dt, &tail};
-        if (ev0 || ev1)
-            HIPCHK(h, hipExtModuleLaunchKernel(f, grid.x * WV, grid.y, 1, WV, 1, 1, lds, st, params, nullptr, ev0, ev1, 0));
+        if (L.ev0 || L.ev1)
+            HIPCHK(h, hipExtModuleLaunchKernel(f, grid.x * WV, grid.y, 1, WV, 1, 1, p.lds, st, params, nullptr, L.ev0, L.ev1, 0));
         else
-            HIPCHK(h, hipModuleLaunchKernel(f, grid.x, grid.y, 1, WV, 1, 1, (unsigned)lds, st, params, nullptr));
+            HIPCHK(h, hipModuleLaunchKernel(f, grid.x, grid.y, 1, WV, 1, 1, (unsigned)p.lds, st, params, nullptr));
+    } else if (L.chunk) {
+        const ChunkKernel k = p.u8 ? chunk_kernel_of<P25FE_FMT_U8>(p.ct, h->long_taps) : chunk_kernel_of<P25FE_FMT_CF32>(p.ct, h->long_taps);
+        hipLaunchKernelGGL(k, grid, dim3(WV), p.lds, st, a, dt, tail);
     } else {
-#define P25FE_K1_CASE(FMT, CT, PK, OM, TX) launch_ev(k_frontend<FMT, CT, PK, OM, TX>, grid, dim3(WV), lds, st, ev0, ev1, a, dt)
-#define P25FE_CHUNK_CASE(FMT, CT, TX) hipLaunchKernelGGL((k_chunk<FMT, CT, TX>), grid, dim3(WV), lds, st, a, dt, tail)
-        if (chunk) {
-            if (h->long_taps) { if (u8) P25FE_CHUNK_CASE(P25FE_FMT_U8, false, 1); else P25FE_CHUNK_CASE(P25FE_FMT_CF32, false, 1); }
-            else if (ct) { if (u8) P25FE_CHUNK_CASE(P25FE_FMT_U8, true, 0); else P25FE_CHUNK_CASE(P25FE_FMT_CF32, true, 0); }
-            else { if (u8) P25FE_CHUNK_CASE(P25FE_FMT_U8, false, 0); else P25FE_CHUNK_CASE(P25FE_FMT_CF32, false, 0); }
-        } else if (h->long_taps) {
-            if (planar) { if (u8) P25FE_K1_CASE(P25FE_FMT_U8, false, 5, OUT_PLANAR, 1); else P25FE_K1_CASE(P25FE_FMT_CF32, false, 5, OUT_PLANAR, 1); }
-            else { if (u8) P25FE_K1_CASE(P25FE_FMT_U8, false, 5, OUT_LINEAR, 1); else P25FE_K1_CASE(P25FE_FMT_CF32, false, 5, OUT_LINEAR, 1); }
-        } else if (planar) {
-            if (ct) { if (u8) P25FE_K1_CASE(P25FE_FMT_U8, true, 5, OUT_PLANAR, 0); else P25FE_K1_CASE(P25FE_FMT_CF32, true, 5, OUT_PLANAR, 0); }
-            else { if (u8) P25FE_K1_CASE(P25FE_FMT_U8, false, 5, OUT_PLANAR, 0); else P25FE_K1_CASE(P25FE_FMT_CF32, false, 5, OUT_PLANAR, 0); }
-        } else if (pk == 3) {
-            if (ct) { if (u8) P25FE_K1_CASE(P25FE_FMT_U8, true, 3, OUT_LINEAR, 0); else P25FE_K1_CASE(P25FE_FMT_CF32, true, 3, OUT_LINEAR, 0); }
-            else { if (u8) P25FE_K1_CASE(P25FE_FMT_U8, false, 3, OUT_LINEAR, 0); else P25FE_K1_CASE(P25FE_FMT_CF32, false, 3, OUT_LINEAR, 0); }
-        } else {
-            if (ct) { if (u8) P25FE_K1_CASE(P25FE_FMT_U8, true, 5, OUT_LINEAR, 0); else P25FE_K1_CASE(P25FE_FMT_CF32, true, 5, OUT_LINEAR, 0); }
-            else { if (u8) P25FE_K1_CASE(P25FE_FMT_U8, false, 5, OUT_LINEAR, 0); else P25FE_K1_CASE(P25FE_FMT_CF32, false, 5, OUT_LINEAR, 0); }
-        }
-#undef P25FE_K1_CASE
-#undef P25FE_CHUNK_CASE
+        const K1Kernel k = p.u8 ? k1_kernel_of<P25FE_FMT_U8>(p.ct, p.pk, L.planar, h->long_taps)
+                                : k1_kernel_of<P25FE_FMT_CF32>(p.ct, p.pk, L.planar, h->long_taps);
+        launch_ev(k, grid, dim3(WV), p.lds, st, L.ev0, L.ev1, a, dt);
     }
-    if (chunk) { HIPCHK(h, hipGetLastError()); return P25FE_OK; }
     HIPCHK(h, hipGetLastError());
-    if (d_power_dbm) {
-        hipLaunchKernelGGL(k_power_finish, dim3((unsigned)h->C), dim3(256), 0, st, a.power_partial, (int)n_seg,
-                           (long)n_out, d_power_dbm);
+    if (L.power_dbm) {
+        hipLaunchKernelGGL(k_power_finish, dim3((unsigned)h->C), dim3(256), 0, st, a.power_partial, (int)p.n_seg, a.n_out, L.power_dbm);
         HIPCHK(h, hipGetLastError());
     }
     return P25FE_OK;
@@ -851,12 +866,38 @@ static int ensure_slice_scratch(p25fe_t* h, size_t n_bb)
     return P25FE_OK;
 }
 
-// The receiver options of the call being enqueued.  h->rs_* (p25fe_resync_at_dev) is consumed by the call that runs the
-// sync detection; a shard keeps its copy for pass 2.
+// The receive side (K2 .. K4) of the call being enqueued: the range on the planar scratch, where the results go, the receiver's
+// options and which steps run.  h->rs_* (p25fe_resync_at_dev) is consumed by the call that runs the sync detection; a shard keeps
+// its copy for pass 2.
+struct RecvRange {
+    size_t n_bb = 0;                            // owned baseband samples per channel
+    long abs_bb0 = 0;                           // absolute index of the first PROCESSED sample = owned sample 0 minus h->look
+    const p25fe_anchor_t* anchor_in = nullptr;  // nullable, [ch]
+};
+struct RecvDest {
+    uint8_t* dibits = nullptr; size_t dibit_stride = 0;
+    uint8_t* dibits2 = nullptr;                 // nullable: second destination of the dibits
+    int64_t* sync_pos = nullptr; uint64_t* sync_dibit = nullptr;      // nullable, both or neither
+    size_t sync_stride = 0;
+    p25fe_result_t* result = nullptr;
+};
 struct RecvCall {
     bool gen = false;
     bool reslice = false;       // SPEC 3.8c: set by the entry points that hold the whole range (p25fe_run_dev*, p25fe_slice_dev)
     RecvOpt opt;
+    RecvRange range;
+    RecvDest dest;
+    // detect: K2 runs in this call, and K3 whole behind it (k_scan_tiles / k_scan_tiles_g: group scans, then the range's).  Otherwise --
+    // and for an empty range, whose record is the carry-in handed through -- the group summaries in the scratch are re-scanned
+    // under range.anchor_in by the top step alone (k_range_scan / k_range_scan_g: a time shard's pass 2 under resolved anchors).
+    bool detect = true;
+    bool slice = true;          // K4 runs (a time shard's pass 1 stops behind K3)
+    bool wait_head = false;     // K2's first tiles wait for the flag of a shard's head launch (p25fe_shard_pass1_head)
+    // (nullable, fixed-stride receiver only) pass 2 of a time shard on pass 1's scan: no K3, the slicer applies the shard's carry-in in
+    // closed form (ShardFix in p25fe_recv.hip) on top of the group's
+    const ShardFix* fix = nullptr;
+    hipEvent_t ev_done = nullptr;               // (nullable) fires when the last kernel of the chain has finished
+    hipStream_t stream = nullptr;
 };
 static RecvCall recv_call(const p25fe_t* h)
 {
@@ -868,6 +909,7 @@ static RecvCall recv_call(const p25fe_t* h)
     c.gen = h->track != 0 || h->rs_n != 0;
     return c;
 }
+static inline int n_tiles_of(const RecvRange& r) { return r.n_bb ? (int)PlanarGeo(r.n_bb).n_tiles : 0; }
 
 static Planar planar_view(const p25fe_t* h, const PlanarGeo& g)
 {
@@ -875,6 +917,28 @@ static Planar planar_view(const p25fe_t* h, const PlanarGeo& g)
     p.f = h->pl_f.as<float>(); p.f_ch = (long)g.floats();
     p.bits = h->pl_bits.as<uint32_t>(); p.bits_ch = (long)g.words();
     return p;
+}
+
+// The scratch buffers and the call's range / destination as the receive kernels' argument structs name them: every mapping that
+// more than one struct shares is written here.
+template <class A> static void view_planes(const p25fe_t* h, const RecvRange& r, A* a)       // K2, K4 (all forms), the chunk receiver
+{
+    a->pl = planar_view(h, PlanarGeo(r.n_bb)); a->n = (long)r.n_bb; a->abs0 = r.abs_bb0;
+    a->evl = h->evl.as<uint16_t>(); a->evthr = h->evthr.as<float>();
+}
+template <class A> static void view_tiles(const p25fe_t* h, A* a) { a->recs = h->recs.as<TileRec>(); a->tsum = h->tsum.as<unsigned long long>(); }
+template <class A> static void view_general(const p25fe_t* h, A* a) { a->gsum = h->gsum.as<TileSumG>(); a->evg = h->evg.as<uint32_t>(); }
+template <class A> static void view_scan(const p25fe_t* h, const RecvCall& rc, A* a)         // K3, both receivers
+{
+    a->recs = h->recs.as<TileRec>(); a->tickets = h->gtick.as<unsigned>();
+    a->n_tiles = n_tiles_of(rc.range); a->n = (long)rc.range.n_bb; a->abs0 = rc.range.abs_bb0; a->n_baseband = rc.range.n_bb;
+    a->anchor_in = rc.range.anchor_in; a->result = rc.dest.result;
+}
+template <class A> static void view_dest(const RecvRange& r, const RecvDest& d, A* a)        // K4 (all forms), the chunk receiver
+{
+    a->anchor_in = r.anchor_in;
+    a->dibits = d.dibits; a->dibit_stride = (long)d.dibit_stride;
+    a->sync_pos = (d.sync_pos && d.sync_dibit) ? d.sync_pos : nullptr; a->sync_dibit = d.sync_dibit; a->sync_stride = (long)d.sync_stride;
 }
 
 // linear baseband (n_hist_bb valid samples before d_bb) -> the planar scratch
@@ -891,155 +955,159 @@ static int launch_planarize(p25fe_t* h, const float* d_bb, size_t bb_stride, siz
     return P25FE_OK;
 }
 
-// K3's arguments, fixed-stride receiver (k_scan_tiles / k_range_scan)
-static void scan_args(p25fe_t* h, size_t n_bb, long abs_bb0, int n_tiles, const p25fe_anchor_t* d_anchor_in, p25fe_result_t* d_result, ScanArgs* t)
+// K2 on the planar scratch
+static int launch_detect(p25fe_t* h, const RecvCall& rc)
 {
-    t->tsum = h->tsum.as<unsigned long long>(); t->recs = h->recs.as<TileRec>(); t->n_tiles = n_tiles; t->n = (long)n_bb; t->abs0 = abs_bb0;
-    t->outs = h->outs.as<ScanOut>(); t->gagg = h->gagg.as<GroupAgg>(); t->gpre = h->gpre.as<GroupPre>();
-    t->tickets = h->gtick.as<unsigned>(); t->anchor_in = d_anchor_in; t->result = d_result;
-    t->n_baseband = n_bb;
-}
-// K2 on the planar scratch (abs_bb0: absolute index of the first PROCESSED sample = owned sample 0 minus h->look)
-static int launch_detect(p25fe_t* h, size_t n_bb, long abs_bb0, hipStream_t st, const RecvCall& rc, bool wait_head_flag = false)
-{
-    const PlanarGeo g(n_bb);
     DetArgs d;
     d.head_flag = nullptr; d.head_seq = 0u; d.head_tile_max = -1; d.head_err = nullptr;
-    if (wait_head_flag) {
+    if (rc.wait_head) {
         d.head_flag = h->sh_flag.as<unsigned>(); d.head_seq = h->sh_seq; d.head_tile_max = h->sh_head_tile_max;
         d.head_err = h->sh_flag.as<unsigned>() + SH_FLAG_ERR;
     }
-    d.pl = planar_view(h, g); d.n = (long)n_bb; d.abs0 = abs_bb0; d.n_tiles = (int)g.n_tiles;
-    d.recs = h->recs.as<TileRec>(); d.tsum = h->tsum.as<unsigned long long>(); d.evl = h->evl.as<uint16_t>(); d.evthr = h->evthr.as<float>();
-    d.opt = rc.opt; d.gsum = h->gsum.as<TileSumG>(); d.evg = h->evg.as<uint32_t>();
-    const dim3 grid((unsigned)g.n_tiles, (unsigned)h->C);
-    if (rc.gen) hipLaunchKernelGGL(k_detect<true>, grid, dim3(WV), 0, st, d);
-    else hipLaunchKernelGGL(k_detect<false>, grid, dim3(WV), 0, st, d);
+    view_planes(h, rc.range, &d); view_tiles(h, &d); view_general(h, &d);
+    d.n_tiles = n_tiles_of(rc.range); d.opt = rc.opt;
+    const dim3 grid((unsigned)d.n_tiles, (unsigned)h->C);
+    if (rc.gen) hipLaunchKernelGGL(k_detect<true>, grid, dim3(WV), 0, rc.stream, d);
+    else hipLaunchKernelGGL(k_detect<false>, grid, dim3(WV), 0, rc.stream, d);
     HIPCHK(h, hipGetLastError());
     return P25FE_OK;
 }
 
-// What follows K2: the slicer (do_slice), in front of it whatever completes the per-tile carry-ins.
-//   scanned   K2 has just run in this call, for THIS carry-in: K3 is launched whole (k_scan_tiles / k_scan_tiles_g: group scans, then the
-//             range's).  Otherwise the group summaries in the scratch are re-scanned under d_anchor_in by the top step alone
-//             (k_range_scan / k_range_scan_g: a time shard's pass 2 under resolved anchors; an empty range, whose record is the
-//             carry-in handed through).
-//   ev_done   (nullable) attached to the LAST kernel this function launches (its completion = the receive side is done)
-//   d_dibits2 (nullable) second destination of the dibits
-//   fix       (nullable, fixed-stride receiver only) pass 2 of a time shard on pass 1's scan: the slicer applies the shard's carry-in in
-//             closed form (ShardFix in p25fe_recv.hip) on top of the group's
-static int launch_scan_slice(p25fe_t* h, size_t n_bb, long abs_bb0, const p25fe_anchor_t* d_anchor_in,
-                             uint8_t* d_dibits, size_t dibit_stride, int64_t* d_sync_pos, uint64_t* d_sync_dibit,
-                             size_t sync_stride, p25fe_result_t* d_result, bool do_slice, hipStream_t st,
-                             const RecvCall& rc, bool scanned, hipEvent_t ev_done = nullptr, uint8_t* d_dibits2 = nullptr,
-                             const ShardFix* fix = nullptr)
+// K3, either receiver.  SCAN_WHOLE: group scans, then the range's; SCAN_RANGE: the range's alone, on the group summaries that are
+// there; SCAN_TILES_G: the general receiver's pass B, the tiles' carry-ins under their groups' (one wave per group).
+enum ScanStep { SCAN_WHOLE, SCAN_RANGE, SCAN_TILES_G };
+static int launch_scan(p25fe_t* h, const RecvCall& rc, ScanStep step, hipEvent_t ev_done)
 {
-    const PlanarGeo g(n_bb);
-    const int n_tiles = n_bb ? (int)g.n_tiles : 0;
-    const bool slice = do_slice && n_tiles != 0;
-    bool ev_pending = ev_done != nullptr;                            // no kernel has carried ev_done yet
+    const dim3 grid = step == SCAN_RANGE ? dim3((unsigned)h->C) : dim3((unsigned)n_groups_of(n_tiles_of(rc.range)), (unsigned)h->C);
     if (rc.gen) {
         ScanArgsG c;
-        c.gsum = h->gsum.as<TileSumG>(); c.recs = h->recs.as<TileRec>(); c.outs = h->gouts.as<ScanOutG>();
-        c.gsg = h->gsg.as<GroupSumG>(); c.gpg = h->gpg.as<GroupPreG>(); c.tickets = h->gtick.as<unsigned>();
-        c.n_tiles = n_tiles; c.n = (long)n_bb; c.abs0 = abs_bb0; c.anchor_in = d_anchor_in; c.result = d_result;
-        c.n_baseband = n_bb; c.track = h->track;
-        if (!scanned) {
-            launch_ev(k_range_scan_g, dim3((unsigned)h->C), dim3(WV), 0, st, nullptr, slice ? nullptr : ev_done, c);
-            HIPCHK(h, hipGetLastError());
-            if (!slice) ev_pending = false;
-        } else if (n_tiles) {
-            launch_ev(k_scan_tiles_g, dim3((unsigned)n_groups_of(n_tiles), (unsigned)h->C), dim3(WV), 0, st, nullptr, slice ? nullptr : ev_done, c);
-            HIPCHK(h, hipGetLastError());
-            if (!slice) ev_pending = false;
-        }
-        prof_mark(h, 3, st);
-        if (!slice) {
-            if (ev_pending) HIPCHK(h, hipEventRecord(ev_done, st));  // (K2 was the last kernel: the event goes behind it)
-            prof_mark(h, 4, st);
-            return P25FE_OK;
-        }
-        // pass B: the tiles' carry-ins under their groups' (one wave per group)
-        hipLaunchKernelGGL(k_scan_g_groups, dim3((unsigned)n_groups_of(n_tiles), (unsigned)h->C), dim3(WV), 0, st, c);
-        HIPCHK(h, hipGetLastError());
-        if (rc.reslice) {
-            // SPEC 3.8c: the slicer by detection (k_ev_collect / k_ev_count / k_ev_scan / k_ev_slice) on those carry-ins
-            const size_t C = (size_t)h->C;
-            size_t cap_ev = (size_t)n_tiles * EVCAP;
-            const size_t bound = n_bb / (size_t)(W + 1) + (size_t)n_tiles + 8;
-            if (bound < cap_ev) cap_ev = bound;
-            const size_t stride = cap_ev + 2;
-            HIPCHK(h, h->evrec.ensure(C * stride * sizeof(EvRec)));
-            HIPCHK(h, h->evoff.ensure(C * (stride + 1) * sizeof(unsigned long long)));
-            {
-                const void* before = h->evnext.p;
-                HIPCHK(h, h->evnext.ensure(C * stride * sizeof(EvNext)));
-                if (h->evnext.p != before) HIPCHK(h, hipMemsetAsync(h->evnext.p, 0, h->evnext.cap, st));   // sequence numbers start above 0
-            }
-            EvArgs e;
-            e.pl = planar_view(h, g); e.n = (long)n_bb; e.abs0 = abs_bb0; e.n_tiles = n_tiles;
-            e.outs = h->gouts.as<ScanOutG>(); e.gsum = h->gsum.as<TileSumG>(); e.evl = h->evl.as<uint16_t>(); e.evg = h->evg.as<uint32_t>();
-            e.evthr = h->evthr.as<float>(); e.anchor_in = d_anchor_in;
-            e.rec = h->evrec.as<EvRec>(); e.nxt = h->evnext.as<EvNext>(); e.off = h->evoff.as<unsigned long long>();
-            e.ev_stride = (long)stride; e.seq = ++h->ev_seq; e.result = d_result;
-            e.dibits = d_dibits; e.dibit_stride = (long)dibit_stride;
-            e.sync_pos = (d_sync_pos && d_sync_dibit) ? d_sync_pos : nullptr; e.sync_dibit = d_sync_dibit; e.sync_stride = (long)sync_stride;
-            hipLaunchKernelGGL(k_ev_collect, dim3((unsigned)n_tiles, (unsigned)h->C), dim3(WV), 0, st, e);
-            HIPCHK(h, hipGetLastError());
-            hipLaunchKernelGGL(k_ev_count, dim3((unsigned)(n_tiles < 1024 ? n_tiles : 1024), (unsigned)h->C), dim3(WV), 0, st, e);
-            HIPCHK(h, hipGetLastError());
-            hipLaunchKernelGGL(k_ev_scan, dim3((unsigned)h->C), dim3(WV), 0, st, e);
-            HIPCHK(h, hipGetLastError());
-            // (a tracked period is within 1 / 1024 of the nominal one over long intervals and at least 9 samples over the shortest)
-            const size_t max_dibits = n_bb / (SPS - 1) + (size_t)n_tiles + 64;
-            const size_t lim = dibit_stride < max_dibits ? dibit_stride : max_dibits;
-            launch_ev(k_ev_slice, dim3((unsigned)((lim + WV * 4 - 1) / (WV * 4)), (unsigned)h->C), dim3(WV), 0, st, nullptr, ev_done, e);
-            HIPCHK(h, hipGetLastError());
-            prof_mark(h, 4, st);
-            return P25FE_OK;
-        }
-        SliceArgsG l;
-        l.pl = planar_view(h, g); l.n = (long)n_bb; l.abs0 = abs_bb0; l.n_tiles = n_tiles;
-        l.outs = h->gouts.as<ScanOutG>(); l.gsum = h->gsum.as<TileSumG>(); l.recs = h->recs.as<TileRec>();
-        l.evl = h->evl.as<uint16_t>(); l.evg = h->evg.as<uint32_t>(); l.evthr = h->evthr.as<float>(); l.anchor_in = d_anchor_in;
-        l.dibits = d_dibits; l.dibit_stride = (long)dibit_stride;
-        l.sync_pos = (d_sync_pos && d_sync_dibit) ? d_sync_pos : nullptr; l.sync_dibit = d_sync_dibit;
-        l.sync_stride = (long)sync_stride; l.track = h->track; l.dibits2 = d_dibits2;
-        launch_ev(k_slice_g, dim3((unsigned)n_tiles, (unsigned)h->C), dim3(WV), 0, st, nullptr, ev_done, l);
-        HIPCHK(h, hipGetLastError());
-        prof_mark(h, 4, st);
-        return P25FE_OK;
-    }
-    if (!fix) {
+        view_scan(h, rc, &c);
+        c.gsum = h->gsum.as<TileSumG>(); c.outs = h->gouts.as<ScanOutG>(); c.gsg = h->gsg.as<GroupSumG>(); c.gpg = h->gpg.as<GroupPreG>();
+        c.track = h->track;
+        launch_ev(step == SCAN_WHOLE ? k_scan_tiles_g : step == SCAN_RANGE ? k_range_scan_g : k_scan_g_groups, grid, dim3(WV), 0, rc.stream,
+                  nullptr, ev_done, c);
+    } else {
         ScanArgs c;
-        scan_args(h, n_bb, abs_bb0, n_tiles, d_anchor_in, d_result, &c);
-        // K2 has just run: the whole scan (groups, then the range); otherwise only the range's, on the group aggregates that are there
-        if (scanned && n_tiles) launch_ev(k_scan_tiles, dim3((unsigned)n_groups_of(n_tiles), (unsigned)h->C), dim3(WV), 0, st, nullptr, slice ? nullptr : ev_done, c);
-        else launch_ev(k_range_scan, dim3((unsigned)h->C), dim3(WV), 0, st, nullptr, slice ? nullptr : ev_done, c);
-        HIPCHK(h, hipGetLastError());
-        if (!slice) ev_pending = false;
+        view_scan(h, rc, &c);
+        c.tsum = h->tsum.as<unsigned long long>(); c.outs = h->outs.as<ScanOut>(); c.gagg = h->gagg.as<GroupAgg>(); c.gpre = h->gpre.as<GroupPre>();
+        launch_ev(step == SCAN_WHOLE ? k_scan_tiles : k_range_scan, grid, dim3(WV), 0, rc.stream, nullptr, ev_done, c);
     }
-    prof_mark(h, 3, st);
-    if (!slice) {
-        if (ev_pending) HIPCHK(h, hipEventRecord(ev_done, st));      // (K2 was the last kernel: the event goes behind it)
-        prof_mark(h, 4, st);
-        return P25FE_OK;
-    }
-    SliceArgs l;
-    l.pl = planar_view(h, g); l.n = (long)n_bb; l.abs0 = abs_bb0; l.n_tiles = n_tiles;
-    l.outs = h->outs.as<ScanOut>(); l.recs = h->recs.as<TileRec>(); l.tsum = h->tsum.as<unsigned long long>();
-    l.evl = h->evl.as<uint16_t>(); l.evthr = h->evthr.as<float>(); l.anchor_in = d_anchor_in;
-    l.dibits = d_dibits; l.dibit_stride = (long)dibit_stride;
-    l.sync_pos = (d_sync_pos && d_sync_dibit) ? d_sync_pos : nullptr; l.sync_dibit = d_sync_dibit;
-    l.sync_stride = (long)sync_stride;
-    l.dibits2 = d_dibits2;
-    l.gpre = h->gpre.as<GroupPre>();
-    if (fix) l.fix = *fix; else memset(&l.fix, 0, sizeof l.fix);
-    // (pass 2 of a time shard: one extra workgroup runs the combine for the record beside the slicing ones)
-    launch_ev(k_slice, dim3((unsigned)n_tiles + (fix ? 1u : 0u), (unsigned)h->C), dim3(WV), 0, st, nullptr, ev_done, l);
     HIPCHK(h, hipGetLastError());
+    return P25FE_OK;
+}
+
+// K4, fixed-stride receiver
+static int launch_slice(p25fe_t* h, const RecvCall& rc)
+{
+    SliceArgs l;
+    view_planes(h, rc.range, &l); view_tiles(h, &l); view_dest(rc.range, rc.dest, &l);
+    l.n_tiles = n_tiles_of(rc.range); l.outs = h->outs.as<ScanOut>(); l.gpre = h->gpre.as<GroupPre>(); l.dibits2 = rc.dest.dibits2;
+    if (rc.fix) l.fix = *rc.fix; else memset(&l.fix, 0, sizeof l.fix);
+    // (pass 2 of a time shard: one extra workgroup runs the combine for the record beside the slicing ones)
+    launch_ev(k_slice, dim3((unsigned)l.n_tiles + (rc.fix ? 1u : 0u), (unsigned)h->C), dim3(WV), 0, rc.stream, nullptr, rc.ev_done, l);
+    HIPCHK(h, hipGetLastError());
+    return P25FE_OK;
+}
+
+// K4, general receiver (tracking clock / lock drops), on the carry-ins of SCAN_TILES_G
+static int launch_slice_g(p25fe_t* h, const RecvCall& rc)
+{
+    SliceArgsG l;
+    view_planes(h, rc.range, &l); view_general(h, &l); view_dest(rc.range, rc.dest, &l);
+    l.n_tiles = n_tiles_of(rc.range); l.outs = h->gouts.as<ScanOutG>(); l.recs = h->recs.as<TileRec>();
+    l.track = h->track; l.dibits2 = rc.dest.dibits2;
+    launch_ev(k_slice_g, dim3((unsigned)l.n_tiles, (unsigned)h->C), dim3(WV), 0, rc.stream, nullptr, rc.ev_done, l);
+    HIPCHK(h, hipGetLastError());
+    return P25FE_OK;
+}
+
+// SPEC 3.8c: the slicer by detection (k_ev_collect / k_ev_count / k_ev_scan / k_ev_slice) on the same carry-ins
+static int launch_slice_by_detection(p25fe_t* h, const RecvCall& rc)
+{
+    const size_t C = (size_t)h->C, n_bb = rc.range.n_bb;
+    const int n_tiles = n_tiles_of(rc.range);
+    hipStream_t st = rc.stream;
+    size_t cap_ev = (size_t)n_tiles * EVCAP;
+    const size_t bound = n_bb / (size_t)(W + 1) + (size_t)n_tiles + 8;
+    if (bound < cap_ev) cap_ev = bound;
+    const size_t stride = cap_ev + 2;
+    HIPCHK(h, h->evrec.ensure(C * stride * sizeof(EvRec)));
+    HIPCHK(h, h->evoff.ensure(C * (stride + 1) * sizeof(unsigned long long)));
+    {
+        const void* before = h->evnext.p;
+        HIPCHK(h, h->evnext.ensure(C * stride * sizeof(EvNext)));
+        if (h->evnext.p != before) HIPCHK(h, hipMemsetAsync(h->evnext.p, 0, h->evnext.cap, st));   // sequence numbers start above 0
+    }
+    EvArgs e;
+    view_planes(h, rc.range, &e); view_general(h, &e); view_dest(rc.range, rc.dest, &e);
+    e.n_tiles = n_tiles; e.outs = h->gouts.as<ScanOutG>();
+    e.rec = h->evrec.as<EvRec>(); e.nxt = h->evnext.as<EvNext>(); e.off = h->evoff.as<unsigned long long>();
+    e.ev_stride = (long)stride; e.seq = ++h->ev_seq; e.result = rc.dest.result;
+    hipLaunchKernelGGL(k_ev_collect, dim3((unsigned)n_tiles, (unsigned)h->C), dim3(WV), 0, st, e);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL(k_ev_count, dim3((unsigned)(n_tiles < 1024 ? n_tiles : 1024), (unsigned)h->C), dim3(WV), 0, st, e);
+    HIPCHK(h, hipGetLastError());
+    hipLaunchKernelGGL(k_ev_scan, dim3((unsigned)h->C), dim3(WV), 0, st, e);
+    HIPCHK(h, hipGetLastError());
+    // (a tracked period is within 1 / 1024 of the nominal one over long intervals and at least 9 samples over the shortest)
+    const size_t max_dibits = n_bb / (SPS - 1) + (size_t)n_tiles + 64;
+    const size_t lim = rc.dest.dibit_stride < max_dibits ? rc.dest.dibit_stride : max_dibits;
+    launch_ev(k_ev_slice, dim3((unsigned)((lim + WV * 4 - 1) / (WV * 4)), (unsigned)h->C), dim3(WV), 0, st, nullptr, rc.ev_done, e);
+    HIPCHK(h, hipGetLastError());
+    return P25FE_OK;
+}
+
+// The receive chain on the planar scratch: K2 (rc.detect), K3, K4 (rc.slice) in order, with the profiling marks behind each.
+// rc.ev_done rides on the LAST kernel launched; if none was, it is recorded on the stream.
+static int launch_recv(p25fe_t* h, const RecvCall& rc)
+{
+    const int n_tiles = n_tiles_of(rc.range);
+    const bool detect = rc.detect && n_tiles != 0, slice = rc.slice && n_tiles != 0, scan = rc.fix == nullptr;
+    hipStream_t st = rc.stream;
+    int e = detect ? launch_detect(h, rc) : P25FE_OK;
+    if (e) return e;
+    prof_mark(h, 2, st);
+    if (scan && (e = launch_scan(h, rc, detect ? SCAN_WHOLE : SCAN_RANGE, slice ? nullptr : rc.ev_done)) != P25FE_OK) return e;
+    prof_mark(h, 3, st);
+    if (slice) {
+        if (!rc.gen) e = launch_slice(h, rc);
+        else if ((e = launch_scan(h, rc, SCAN_TILES_G, nullptr)) == P25FE_OK) e = rc.reslice ? launch_slice_by_detection(h, rc) : launch_slice_g(h, rc);
+        if (e) return e;
+    }
+    if (rc.ev_done && !scan && !slice) HIPCHK(h, hipEventRecord(rc.ev_done, st));
     prof_mark(h, 4, st);
     return P25FE_OK;
+}
+
+// K1 into the planar scratch (nothing if the range holds no baseband sample), under the open profiling slot's event pair.
+// k1_done (nullable): fires when K1 has finished -- riding on its dispatch if h->ext_events -- and `waiter` waits for it.
+static int launch_k1_planar(p25fe_t* h, K1Launch& k, hipEvent_t k1_done, hipStream_t waiter)
+{
+    prof_mark(h, 0, k.stream);
+    bool attached = false;
+    if (p25fe_n_baseband_h(h, k.abs0, k.n)) {
+        prof_k1_events(h, &k.ev0, &k.ev1);
+        if (k1_done && h->ext_events) {
+            if (k.ev1) k1_done = k.ev1;                             // a sampled call: the profiling stop event doubles as "K1 done"
+            else k.ev1 = k1_done;
+            attached = true;
+        }
+        k.planar = true;
+        if (int rc = launch_k1(h, k)) return rc;
+    }
+    if (k1_done) {
+        if (!attached) HIPCHK(h, hipEventRecord(k1_done, k.stream));
+        HIPCHK(h, hipStreamWaitEvent(waiter, k1_done, 0));
+    }
+    return P25FE_OK;
+}
+
+// Planar front end, then the receive chain (on rc.stream, which may be another stream than K1's: then k1_done orders the two)
+static int launch_planar_recv(p25fe_t* h, K1Launch& k, const RecvCall& rc, hipEvent_t k1_done = nullptr)
+{
+    if (int e = launch_k1_planar(h, k, k1_done, rc.stream)) return e;
+    if (rc.range.n_bb) prof_mark(h, 1, k.stream);
+    return launch_recv(h, rc);
 }
 
 // SPEC 3.8c needs the whole range in one call.  The calls that see the stream in pieces (host streaming chunks, host windows, the
@@ -1055,34 +1123,6 @@ static void shard_invalidate(p25fe_t* h)
     h->sh_head_done = false; h->sh_head_flagged = false;
 }
 
-static int pipe_join(p25fe_t* h, hipStream_t st);
-// stages 6-7 on a LINEAR device baseband: planarize, detect, scan, slice
-static int dev_slice(p25fe_t* h, const float* d_bb, size_t bb_stride, size_t n_hist_bb, size_t n_bb,
-                     uint64_t abs_bb0, const p25fe_anchor_t* d_anchor_in, uint8_t* d_dibits,
-                     size_t dibit_stride, int64_t* d_sync_pos, uint64_t* d_sync_dibit, size_t sync_stride,
-                     p25fe_result_t* d_result, hipStream_t st)
-{
-    if (n_bb > MAX_RANGE_BB) return P25FE_ERR_ARG;
-    shard_invalidate(h);
-    if (int jrc = pipe_join(h, st)) return jrc;
-    const long view0 = (long)abs_bb0 - h->look;          // first processed index: the tracking clock runs h->look samples late
-    int rc = ensure_slice_scratch(h, n_bb ? n_bb : 1);
-    if (rc) return rc;
-    RecvCall rcall = recv_call(h);
-    rcall.reslice = h->track == P25FE_CLOCK_TRACKING_RESLICE;      // the whole range is in memory: SPEC 3.8c applies
-    h->rs_n = 0;                                         // the lock drops belong to this call
-    if (n_bb == 0)        // empty range: only the scan runs (zero tiles) and hands the anchor through
-        return launch_scan_slice(h, 0, view0, d_anchor_in, d_dibits, dibit_stride, nullptr, nullptr, 0, d_result,
-                                 false, st, rcall, false);
-    rc = launch_planarize(h, d_bb, bb_stride, n_hist_bb, n_bb, st);
-    if (rc) return rc;
-    rc = launch_detect(h, n_bb, view0, st, rcall, false);
-    if (rc) return rc;
-    prof_mark(h, 2, st);
-    return launch_scan_slice(h, n_bb, view0, d_anchor_in, d_dibits, dibit_stride, d_sync_pos, d_sync_dibit,
-                             sync_stride, d_result, true, st, rcall, true);
-}
-
 extern "C" {
 
 // --------------------------------------------------------------------------------------------
@@ -1093,8 +1133,10 @@ int p25fe_demod_dev(p25fe_t* h, const void* d_iq, int fmt, size_t ch_stride, siz
 {
     if (!h || !d_iq || !d_bb) return P25FE_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    return launch_frontend(h, d_iq, fmt, ch_stride, n_hist, n, abs0, 0, d_bb, bb_stride, d_power_dbm,
-                           (hipStream_t)stream);
+    K1Launch k;
+    k.src = d_iq; k.fmt = fmt; k.ch_stride = ch_stride; k.n_hist = n_hist; k.n = n; k.abs0 = abs0;
+    k.bb = d_bb; k.bb_stride = bb_stride; k.power_dbm = d_power_dbm; k.stream = (hipStream_t)stream;
+    return launch_k1(h, k);
 }
 
 size_t p25fe_n_predecim(uint64_t abs0, size_t n)
@@ -1141,16 +1183,6 @@ int p25fe_channelise_dev(p25fe_t* h, const float* d_iq, size_t n_hist, size_t n,
     return P25FE_OK;
 }
 
-int p25fe_slice_dev(p25fe_t* h, const float* d_bb, size_t bb_stride, size_t n_hist_bb, size_t n_bb, uint64_t abs_bb0,
-                    const p25fe_anchor_t* d_anchor_in, uint8_t* d_dibits, size_t dibit_stride, int64_t* d_sync_pos,
-                    uint64_t* d_sync_dibit, size_t sync_stride, p25fe_result_t* d_result, void* stream)
-{
-    if (!h || !d_bb || !d_dibits || !d_result) return P25FE_ERR_ARG;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    return dev_slice(h, d_bb, bb_stride, n_hist_bb, n_bb, abs_bb0, d_anchor_in, d_dibits, dibit_stride, d_sync_pos,
-                     d_sync_dibit, sync_stride, d_result, (hipStream_t)stream);
-}
-
 // Every entry point that uses the receiver's scratch first makes its stream wait for receive kernels that
 // p25fe_run_dev_pipelined left running on the handle's own stream (no-op when nothing is pending).
 static int pipe_join(p25fe_t* h, hipStream_t st)
@@ -1163,6 +1195,32 @@ static int pipe_join(p25fe_t* h, hipStream_t st)
             h->rx_joined[l] = st; h->rx_joined_any[l] = true;
         }
     return P25FE_OK;
+}
+
+int p25fe_slice_dev(p25fe_t* h, const float* d_bb, size_t bb_stride, size_t n_hist_bb, size_t n_bb, uint64_t abs_bb0,
+                    const p25fe_anchor_t* d_anchor_in, uint8_t* d_dibits, size_t dibit_stride, int64_t* d_sync_pos,
+                    uint64_t* d_sync_dibit, size_t sync_stride, p25fe_result_t* d_result, void* stream)
+{
+    if (!h || !d_bb || !d_dibits || !d_result) return P25FE_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (n_bb > MAX_RANGE_BB) return P25FE_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    shard_invalidate(h);
+    if (int jrc = pipe_join(h, st)) return jrc;
+    int rc = ensure_slice_scratch(h, n_bb ? n_bb : 1);
+    if (rc) return rc;
+    RecvCall rcall = recv_call(h);
+    rcall.reslice = h->track == P25FE_CLOCK_TRACKING_RESLICE;      // the whole range is in memory: SPEC 3.8c applies
+    h->rs_n = 0;                                         // the lock drops belong to this call
+    rcall.range.n_bb = n_bb; rcall.range.anchor_in = d_anchor_in;
+    rcall.range.abs_bb0 = (long)abs_bb0 - h->look;       // first processed index: the tracking clock runs h->look samples late
+    rcall.dest.dibits = d_dibits; rcall.dest.dibit_stride = dibit_stride; rcall.dest.result = d_result;
+    rcall.dest.sync_pos = d_sync_pos; rcall.dest.sync_dibit = d_sync_dibit; rcall.dest.sync_stride = sync_stride;
+    rcall.stream = st;
+    // stages 6-7 on a LINEAR device baseband: planarize, detect, scan, slice (an empty range: only the scan runs and hands the anchor through)
+    if (n_bb)
+        if ((rc = launch_planarize(h, d_bb, bb_stride, n_hist_bb, n_bb, st)) != P25FE_OK) return rc;
+    return launch_recv(h, rcall);
 }
 
 int p25fe_join_dev(p25fe_t* h, void* stream)
@@ -1236,87 +1294,51 @@ static int pipe_open(p25fe_t* h, hipStream_t st, int depth = 2)
     return P25FE_OK;
 }
 
-int p25fe_run_dev_pipelined(p25fe_t* h, const void* d_iq, int fmt, size_t ch_stride, size_t n, uint8_t* d_dibits,
-                            size_t dibit_stride, p25fe_result_t* d_result, void* stream)
+// A device-resident capture from the start of a stream: K1 straight into the polyphase layout (+ sign planes; the 240 history
+// positions in front of the stream come out as the zeros of a fresh DemodTask), then the receive chain -- on the caller's stream,
+// or (pipelined) on the handle's receive stream in the next scratch set, beside the caller's next K1.
+static int run_dev(p25fe_t* h, const void* d_iq, int fmt, size_t ch_stride, size_t n, const RecvDest& dest, hipStream_t st, bool pipelined)
 {
-    if (!h || !d_iq || !d_dibits || !d_result || p25fe_n_baseband_h(h, 0, n) > MAX_RANGE_BB) return P25FE_ERR_ARG;
+    if (!h || !d_iq || !dest.dibits || !dest.result || p25fe_n_baseband_h(h, 0, n) > MAX_RANGE_BB) return P25FE_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = (hipStream_t)stream;
     shard_invalidate(h);
-    if (int orc = pipe_open(h, st, h->run_depth)) return orc;
+    if (int orc = pipelined ? pipe_open(h, st, h->run_depth) : pipe_join(h, st)) return orc;
     const int lane = h->lane;
     const size_t n_bb = p25fe_n_baseband_h(h, 0, n);
-    int rc = P25FE_OK;
-    const PlanarGeo g(n_bb);
-    hipEvent_t k1_done = h->ev_k1[lane];
-    bool k1_done_attached = false;
-    rc = ensure_slice_scratch(h, n_bb ? n_bb : 1);   // (growing a buffer frees the old one: hipFree synchronises the device)
+    int rc = ensure_slice_scratch(h, n_bb ? n_bb : 1);   // (growing a buffer frees the old one: hipFree synchronises the device)
     if (rc) return rc;
     RecvCall rcall = recv_call(h);
     rcall.reslice = h->track == P25FE_CLOCK_TRACKING_RESLICE;      // the whole range is in memory: SPEC 3.8c applies
     h->rs_n = 0;
-    if (n_bb) {
-        prof_begin(h);
-        prof_mark(h, 0, st);
-        hipEvent_t e0, e1;
-        prof_k1_events(h, &e0, &e1);
-        if (h->ext_events) {
-            if (e1) k1_done = e1;                    // a sampled call: the profiling stop event doubles as "K1 done"
-            else e1 = k1_done;
-            k1_done_attached = true;
-        }
-        rc = launch_frontend(h, d_iq, fmt, ch_stride, 0, n, 0, -(long)PLPAD - h->look, nullptr, 0, nullptr, st, &g, 0, e0, e1);
-        if (rc) return rc;
-        prof_mark(h, 1, st);
-    }
-    if (!k1_done_attached) HIPCHK(h, hipEventRecord(k1_done, st));
-    HIPCHK(h, hipStreamWaitEvent(h->rx_stream, k1_done, 0));
-    if (n_bb) {
-        rc = launch_detect(h, n_bb, -h->look, h->rx_stream, rcall, false);
-        if (rc) return rc;
-        prof_mark(h, 2, h->rx_stream);
-    }
-    rc = launch_scan_slice(h, n_bb, -h->look, nullptr, d_dibits, dibit_stride, nullptr, nullptr, 0, d_result, n_bb != 0, h->rx_stream,
-                           rcall, n_bb != 0, h->ext_events ? h->ev_rx[lane] : nullptr);
+    rcall.range.n_bb = n_bb; rcall.range.abs_bb0 = -h->look;
+    rcall.dest = dest;
+    rcall.stream = pipelined ? h->rx_stream : st;
+    if (pipelined && h->ext_events) rcall.ev_done = h->ev_rx[lane];
+    K1Launch k;
+    k.src = d_iq; k.fmt = fmt; k.ch_stride = ch_stride; k.n = n; k.stream = st;
+    if (n_bb) prof_begin(h);
+    rc = launch_planar_recv(h, k, rcall, pipelined ? h->ev_k1[lane] : nullptr);
     h->prof_slot = -1;
-    if (rc) return rc;
+    if (rc || !pipelined) return rc;
     if (!h->ext_events) HIPCHK(h, hipEventRecord(h->ev_rx[lane], h->rx_stream));
     h->rx_pending[lane] = true;
     return P25FE_OK;
 }
 
+int p25fe_run_dev_pipelined(p25fe_t* h, const void* d_iq, int fmt, size_t ch_stride, size_t n, uint8_t* d_dibits,
+                            size_t dibit_stride, p25fe_result_t* d_result, void* stream)
+{
+    RecvDest dest;
+    dest.dibits = d_dibits; dest.dibit_stride = dibit_stride; dest.result = d_result;
+    return run_dev(h, d_iq, fmt, ch_stride, n, dest, (hipStream_t)stream, /*pipelined=*/true);
+}
+
 int p25fe_run_dev(p25fe_t* h, const void* d_iq, int fmt, size_t ch_stride, size_t n, uint8_t* d_dibits,
                   size_t dibit_stride, p25fe_result_t* d_result, void* stream)
 {
-    if (!h || !d_iq || !d_dibits || !d_result || p25fe_n_baseband_h(h, 0, n) > MAX_RANGE_BB) return P25FE_ERR_ARG;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    hipStream_t st = (hipStream_t)stream;
-    shard_invalidate(h);
-    if (int jrc = pipe_join(h, st)) return jrc;
-    const size_t n_bb = p25fe_n_baseband_h(h, 0, n);
-    int rc = ensure_slice_scratch(h, n_bb ? n_bb : 1);
-    if (rc) return rc;
-    RecvCall rcall = recv_call(h);
-    rcall.reslice = h->track == P25FE_CLOCK_TRACKING_RESLICE;      // the whole range is in memory: SPEC 3.8c applies
-    h->rs_n = 0;
-    if (n_bb == 0)
-        return launch_scan_slice(h, 0, -h->look, nullptr, d_dibits, dibit_stride, nullptr, nullptr, 0, d_result, false, st, rcall, false);
-    const PlanarGeo g(n_bb);
-    prof_begin(h);
-    prof_mark(h, 0, st);
-    hipEvent_t e0, e1;
-    prof_k1_events(h, &e0, &e1);
-    // K1 writes the baseband straight into the polyphase layout (+ sign planes); the 240 history positions in front
-    // of the stream come out as the zeros of a fresh DemodTask (outputs of an all-zero input)
-    rc = launch_frontend(h, d_iq, fmt, ch_stride, 0, n, 0, -(long)PLPAD - h->look, nullptr, 0, nullptr, st, &g, 0, e0, e1);
-    if (rc) return rc;
-    prof_mark(h, 1, st);
-    rc = launch_detect(h, n_bb, -h->look, st, rcall, false);
-    if (rc) return rc;
-    prof_mark(h, 2, st);
-    rc = launch_scan_slice(h, n_bb, -h->look, nullptr, d_dibits, dibit_stride, nullptr, nullptr, 0, d_result, true, st, rcall, true);
-    h->prof_slot = -1;
-    return rc;
+    RecvDest dest;
+    dest.dibits = d_dibits; dest.dibit_stride = dibit_stride; dest.result = d_result;
+    return run_dev(h, d_iq, fmt, ch_stride, n, dest, (hipStream_t)stream, /*pipelined=*/false);
 }
 
 // --------------------------------------------------------------------------------------------
@@ -1339,37 +1361,22 @@ static int shard_pass1_part(p25fe_t* h, const void* d_iq, int fmt, size_t ch_str
     const long abs_bb0 = (long)p25fe_n_baseband_h(h, 0, (size_t)abs0) - h->look;      // first processed baseband index of this shard
     int rc = ensure_slice_scratch(h, n_bb ? n_bb : 1);
     if (rc) return rc;
-    const PlanarGeo g(n_bb);
     // the receiver's 240 history samples are recomputed from the IQ halo (zeros before the start of the stream)
+    K1Launch k;
+    k.src = d_iq; k.fmt = fmt; k.ch_stride = ch_stride; k.n_hist = n_hist; k.n = n; k.abs0 = abs0; k.planar = true; k.stream = st;
     if (do_main) {
         prof_begin(h);
-        prof_mark(h, 0, st);
-        hipEvent_t k1_done = h->sh_pipe ? h->ev_k1[h->lane] : nullptr;
-        bool k1_done_attached = false;
-        if (n_bb) {
-            // K1's event pair rides on THIS launch: with the split form it times the main launch alone (the head segment
-            // that follows the halo wait is one workgroup), so an RCCL wait between the two is not in K1's figure
-            hipEvent_t e0, e1;
-            prof_k1_events(h, &e0, &e1);
-            if (h->sh_pipe && h->ext_events) {
-                if (e1) k1_done = e1;                               // a sampled call: the profiling stop event doubles as "K1 done"
-                else e1 = k1_done;
-                k1_done_attached = true;
-            }
-            rc = launch_frontend(h, d_iq, fmt, ch_stride, n_hist, n, abs0, -(long)PLPAD - h->look, nullptr, 0, nullptr, st, &g,
-                                 do_head ? 0 : 1, e0, e1);
-            if (rc) return rc;
-        }
-        if (h->sh_pipe) {
-            // pipelined step: everything behind this launch runs on the receive stream, which waits for it here
-            // (K1 on a CU-masked stream of its own, to keep a few CUs free for the exchanges that run beside it, was tried: the
-            // masked launch itself ran 30 - 60 % slower -- profiles/r05_shard_pipelined.txt)
-            if (!k1_done_attached) HIPCHK(h, hipEventRecord(k1_done, st));
-            HIPCHK(h, hipStreamWaitEvent(h->rx_stream, k1_done, 0));
-        }
+        // K1's event pair rides on THIS launch: with the split form it times the main launch alone (the head segment
+        // that follows the halo wait is one workgroup), so an RCCL wait between the two is not in K1's figure.
+        // Pipelined step: everything behind this launch runs on the receive stream, which waits for it here
+        // (K1 on a CU-masked stream of its own, to keep a few CUs free for the exchanges that run beside it, was tried: the
+        // masked launch itself ran 30 - 60 % slower -- profiles/r05_shard_pipelined.txt)
+        k.part = do_head ? K1_ALL : K1_MAIN;
+        rc = launch_k1_planar(h, k, h->sh_pipe ? h->ev_k1[h->lane] : nullptr, h->rx_stream);
+        if (rc) return rc;
         h->sh_main_nbb = n_bb; h->sh_main_abs0 = abs0;
         h->sh_head_done = do_head;
-        do_head = false;                                            // (part 0 = every segment)
+        do_head = false;                                            // (K1_ALL = every segment)
     } else {
         if (h->sh_main_nbb != n_bb || h->sh_main_abs0 != abs0) return P25FE_ERR_ARG;     // head / finish without its main launch
     }
@@ -1390,8 +1397,9 @@ static int shard_pass1_part(p25fe_t* h, const void* d_iq, int fmt, size_t ch_str
                 ++h->sh_seq;
                 if (h->sh_seq == 0u) ++h->sh_seq;
             }
-            rc = launch_frontend(h, d_iq, fmt, ch_stride, n_hist, n, abs0, -(long)PLPAD - h->look, nullptr, 0, nullptr, st, &g, 2, nullptr, nullptr,
-                                 nullptr, &head_end, own_stream ? h->sh_flag.as<unsigned>() : nullptr, h->sh_seq);
+            k.part = K1_HEAD; k.ev0 = k.ev1 = nullptr; k.head_end = &head_end;
+            k.done_flag = own_stream ? h->sh_flag.as<unsigned>() : nullptr; k.done_seq = h->sh_seq;
+            rc = launch_k1(h, k);
             if (rc) return rc;
             if (own_stream && head_end > 0) {                       // (no head workgroup, no flag: nothing to wait for)
                 h->sh_head_flagged = true;
@@ -1402,15 +1410,13 @@ static int shard_pass1_part(p25fe_t* h, const void* d_iq, int fmt, size_t ch_str
     }
     if (!do_finish) return P25FE_OK;
     prof_mark(h, 1, st);
-    const RecvCall rcall = recv_call(h);
+    RecvCall rcall = recv_call(h);
     h->rs_n = 0;
-    if (n_bb) {
-        rc = launch_detect(h, n_bb, abs_bb0, st, rcall, h->sh_head_flagged);
-        if (rc) return rc;
-    }
+    rcall.range.n_bb = n_bb; rcall.range.abs_bb0 = abs_bb0;
+    rcall.dest.result = d_result;
+    rcall.slice = false; rcall.wait_head = h->sh_head_flagged; rcall.stream = st;
+    rc = launch_recv(h, rcall);
     h->sh_head_flagged = false;
-    prof_mark(h, 2, st);
-    rc = launch_scan_slice(h, n_bb, abs_bb0, nullptr, nullptr, 0, nullptr, nullptr, 0, d_result, false, st, rcall, n_bb != 0);
     h->prof_slot = -1;
     if (rc) return rc;
     h->sh_valid = true; h->sh_nbb = n_bb; h->sh_abs_bb0 = abs_bb0; h->sh_gen = rcall.gen; h->sh_scan_fresh = true;
@@ -1480,18 +1486,28 @@ int p25fe_shard_pipe_end(p25fe_t* h, void* last_stream)
     return P25FE_OK;
 }
 
+// Pass 2 of a shard: K3 / K4 on what pass 1's K2 left in the scratch (the lock drops are in its summaries), no K2
+static RecvCall shard_pass2_call(const p25fe_t* h, const p25fe_anchor_t* d_anchor_in, uint8_t* d_dibits, size_t dibit_stride, p25fe_result_t* d_result,
+                                 hipStream_t st)
+{
+    RecvCall c = recv_call(h);
+    c.gen = h->sh_gen;
+    c.detect = false;
+    c.range.n_bb = h->sh_nbb; c.range.abs_bb0 = h->sh_abs_bb0; c.range.anchor_in = d_anchor_in;
+    c.dest.dibits = d_dibits; c.dest.dibit_stride = dibit_stride; c.dest.result = d_result;
+    c.stream = st;
+    return c;
+}
+
 int p25fe_shard_pass2(p25fe_t* h, const p25fe_anchor_t* d_anchor_in, uint8_t* d_dibits, size_t dibit_stride,
                       p25fe_result_t* d_result, void* stream)
 {
     if (!h || !d_dibits || !d_result || !h->sh_valid) return P25FE_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    prof_begin(h);
-    prof_mark(h, 2, (hipStream_t)stream);
-    RecvCall rcall = recv_call(h);
-    rcall.gen = h->sh_gen;                               // K3 / K4 read what pass 1's K2 left (the lock drops are in its summaries)
+    RecvCall rcall = shard_pass2_call(h, d_anchor_in, d_dibits, dibit_stride, d_result, (hipStream_t)stream);
     h->sh_scan_fresh = false;                            // the re-scan below rewrites the groups' carry-ins with THIS carry-in
-    const int rc = launch_scan_slice(h, h->sh_nbb, h->sh_abs_bb0, d_anchor_in, d_dibits, dibit_stride, nullptr, nullptr,
-                                     0, d_result, true, (hipStream_t)stream, rcall, false);
+    prof_begin(h);
+    const int rc = launch_recv(h, rcall);
     h->prof_slot = -1;
     return rc;
 }
@@ -1505,38 +1521,24 @@ int p25fe_shard_pass2_dev(p25fe_t* h, const p25fe_result_t* d_summaries, const u
         return P25FE_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     hipStream_t st = (hipStream_t)stream;
-    RecvCall rcall = recv_call(h);
-    rcall.gen = h->sh_gen;
-    if (rcall.gen || !h->sh_scan_fresh) {
-        // tracking clock / lock drops inside the shard (or a p25fe_shard_pass2 has already rewritten pass 1's scan): the combine
-        // as its own (one-thread) launch, then the re-scan of the shard's groups + slicer with that carry-in
+    RecvCall rcall = shard_pass2_call(h, d_anchor_in + rank, d_dibits, dibit_stride, d_result, st);
+    rcall.dest.dibits2 = d_dibits_dup;
+    ShardFix fx;
+    if (rcall.gen || !h->sh_scan_fresh || h->sh_nbb == 0) {
+        // tracking clock / lock drops inside the shard (or a p25fe_shard_pass2 has already rewritten pass 1's scan; or a shard without a
+        // baseband sample, which has no slicer tile to run the combine in: never the hot path): the combine as its own (one-thread)
+        // launch, then the re-scan of the shard's groups + slicer with that carry-in
         h->sh_scan_fresh = false;
         hipLaunchKernelGGL(k_shard_resolve, dim3(1), dim3(64), 0, st, d_summaries, d_shard_bb0, d_shard_bb_n, (int)n_shards, h->track,
                            d_anchor_in, d_dibit_offset);
         HIPCHK(h, hipGetLastError());
-        prof_begin(h);
-        prof_mark(h, 2, st);
-        const int rc = launch_scan_slice(h, h->sh_nbb, h->sh_abs_bb0, d_anchor_in + rank, d_dibits, dibit_stride, nullptr, nullptr, 0,
-                                         d_result, true, st, rcall, false, nullptr, d_dibits_dup);
-        h->prof_slot = -1;
-        return rc;
-    }
-    ShardFix fx;
-    fx.summ = d_summaries; fx.bb0 = d_shard_bb0; fx.bbn = d_shard_bb_n; fx.n_shards = (int)n_shards; fx.rank = (int)rank;
-    fx.anc_out = d_anchor_in; fx.off_out = d_dibit_offset; fx.result = d_result;
-    prof_begin(h);
-    prof_mark(h, 2, st);
-    int rc;
-    if (h->sh_nbb == 0) {
-        // a shard without a baseband sample has no slicer tile to run the combine in: separate launches (never the hot path)
-        hipLaunchKernelGGL(k_shard_resolve, dim3(1), dim3(64), 0, st, d_summaries, d_shard_bb0, d_shard_bb_n, (int)n_shards, h->track,
-                           d_anchor_in, d_dibit_offset);
-        HIPCHK(h, hipGetLastError());
-        rc = launch_scan_slice(h, 0, h->sh_abs_bb0, d_anchor_in + rank, d_dibits, dibit_stride, nullptr, nullptr, 0, d_result, true, st, rcall, false);
     } else {
-        rc = launch_scan_slice(h, h->sh_nbb, h->sh_abs_bb0, nullptr, d_dibits, dibit_stride, nullptr, nullptr, 0, d_result, true, st, rcall,
-                               true, nullptr, d_dibits_dup, &fx);
+        fx.summ = d_summaries; fx.bb0 = d_shard_bb0; fx.bbn = d_shard_bb_n; fx.n_shards = (int)n_shards; fx.rank = (int)rank;
+        fx.anc_out = d_anchor_in; fx.off_out = d_dibit_offset; fx.result = d_result;
+        rcall.range.anchor_in = nullptr; rcall.fix = &fx;
     }
+    prof_begin(h);
+    const int rc = launch_recv(h, rcall);
     h->prof_slot = -1;
     return rc;
 }
@@ -1662,6 +1664,15 @@ static void commit_iq(p25fe_t* h, int fmt, size_t n, const Staged& s)
     h->abs_iq += n;
 }
 
+// K1 on the staged chunk, from the stream's position on
+static K1Launch staged_k1(const p25fe_t* h, int fmt, size_t n, const Staged& s)
+{
+    K1Launch k;
+    k.src = s.dev + SHARD_HALO * fmt_bytes(fmt); k.fmt = fmt; k.ch_stride = s.stride; k.n_hist = s.n_hist; k.n = n; k.abs0 = h->abs_iq;
+    k.stream = h->stream;
+    return k;
+}
+
 static int demod_host(p25fe_t* h, const void* iq, int fmt, size_t n, float* bb, size_t bb_cap, size_t* n_out,
                       float* power_dbm)
 {
@@ -1679,8 +1690,9 @@ static int demod_host(p25fe_t* h, const void* iq, int fmt, size_t n, float* bb, 
     float *d_bb, *d_pw;
     float* h_bb = ar.take<float>(C * bb_stride, &d_bb);
     float* h_pw = ar.take<float>(C, &d_pw);
-    rc = launch_frontend(h, sg.dev + SHARD_HALO * fmt_bytes(fmt), fmt, sg.stride, sg.n_hist, n, h->abs_iq, 0, d_bb, bb_stride,
-                         power_dbm ? d_pw : nullptr, h->stream);
+    K1Launch k = staged_k1(h, fmt, n, sg);
+    k.bb = d_bb; k.bb_stride = bb_stride; k.power_dbm = power_dbm ? d_pw : nullptr;
+    rc = launch_k1(h, k);
     if (rc) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (size_t c = 0; c < C; ++c) memcpy(bb + c * bb_cap, h_bb + c * bb_stride, nb * sizeof(float));
@@ -1756,14 +1768,22 @@ static int recv_finish(p25fe_t* h, const RecvOut& o, size_t n_bb, uint8_t* dibit
     return P25FE_OK;
 }
 
-static void chunk_recv_args(p25fe_t* h, const RecvOut& o, size_t n_bb, long view0, bool want_sync, bool want_tail, ChunkRecvArgs* c)
+// the receive side of a host-buffer call: n_bb samples behind the stream's position, the pinned outputs
+static RecvCall host_recv_call(const p25fe_t* h, const RecvOut& o, size_t n_bb, bool want_sync)
 {
-    const PlanarGeo g(n_bb);
-    c->pl = planar_view(h, g); c->n = (long)n_bb; c->abs0 = view0;
-    c->recs = h->recs.as<TileRec>(); c->tsum = h->tsum.as<unsigned long long>(); c->evl = h->evl.as<uint16_t>(); c->evthr = h->evthr.as<float>();
-    c->anchor_in = o.d_anc; c->result = o.d_res; c->dibits = o.d_dib; c->dibit_stride = (long)o.dstride;
-    c->sync_pos = want_sync ? o.d_spos : nullptr; c->sync_dibit = want_sync ? o.d_sdib : nullptr; c->sync_stride = (long)o.sstride;
-    c->tail = want_tail ? o.d_tail : nullptr; c->look = (int)h->look; c->n_baseband = n_bb;
+    RecvCall c = recv_call(h);                                      // (a pending p25fe_resync_at_dev list belongs to this call: cleared once it has succeeded)
+    c.range.n_bb = n_bb; c.range.abs_bb0 = (long)h->abs_bb - h->look; c.range.anchor_in = o.d_anc;
+    c.dest.dibits = o.d_dib; c.dest.dibit_stride = o.dstride; c.dest.result = o.d_res;
+    c.dest.sync_pos = want_sync ? o.d_spos : nullptr; c.dest.sync_dibit = want_sync ? o.d_sdib : nullptr; c.dest.sync_stride = o.sstride;
+    c.stream = h->stream;
+    return c;
+}
+// ... and the same for the one-tile receiver of the chunk kernels
+static void chunk_recv_args(const p25fe_t* h, const RecvCall& rc, float* d_tail, ChunkRecvArgs* c)
+{
+    view_planes(h, rc.range, c); view_tiles(h, c); view_dest(rc.range, rc.dest, c);
+    c->result = rc.dest.result; c->n_baseband = rc.range.n_bb;
+    c->tail = d_tail; c->look = (int)h->look;
     c->done = nullptr; c->seq = 0u;
 }
 
@@ -1824,10 +1844,10 @@ int p25fe_slice(p25fe_t* h, const float* bb, size_t n, uint8_t* dibits, size_t c
     ChunkRecvArgs polled;
     polled.done = nullptr; polled.seq = 0u;
     const size_t hist = h->abs_bb < BBPAD ? (size_t)h->abs_bb : BBPAD;
-    const long view0 = (long)h->abs_bb - h->look;
-    if (!h->track && !h->rs_n && n <= (size_t)TS) {
+    const RecvCall rcall = host_recv_call(h, o, n, sync_cap != 0);
+    if (!rcall.gen && n <= (size_t)TS) {
         RecvChunkArgs a;
-        chunk_recv_args(h, o, n, view0, sync_cap != 0, false, &a.r);
+        chunk_recv_args(h, rcall, nullptr, &a.r);
         chunk_poll_arm(h, o, &a.r);
         polled = a.r;
         const PlanarGeo g(n);
@@ -1836,13 +1856,8 @@ int p25fe_slice(p25fe_t* h, const float* bb, size_t n, uint8_t* dibits, size_t c
         hipLaunchKernelGGL(k_recv_chunk, dim3((unsigned)C), dim3(WV), 0, h->stream, a);
         HIPCHK(h, hipGetLastError());
     } else {
-        const RecvCall rcall = recv_call(h);                        // (a pending p25fe_resync_at_dev list belongs to this call: cleared below, once it has succeeded)
         rc = launch_planarize(h, db + BBPAD, bb_stride, hist, n, h->stream);
-        if (rc) return rc;
-        rc = launch_detect(h, n, view0, h->stream, rcall, false);
-        if (rc) return rc;
-        rc = launch_scan_slice(h, n, view0, o.d_anc, o.d_dib, o.dstride, sync_cap ? o.d_spos : nullptr,
-                               sync_cap ? o.d_sdib : nullptr, o.sstride, o.d_res, true, h->stream, rcall, true);
+        if (!rc) rc = launch_recv(h, rcall);
         if (rc) return rc;
     }
     rc = chunk_wait(h, o, polled);
@@ -1853,15 +1868,6 @@ int p25fe_slice(p25fe_t* h, const float* bb, size_t n, uint8_t* dibits, size_t c
     for (size_t c = 0; c < C; ++c)                                   // the tail: last BBPAD samples of [tail | new]
         memcpy(h->tail_bb.data() + c * BBPAD, hb + c * bb_stride + n, BBPAD * sizeof(float));
     return P25FE_OK;
-}
-
-// launch of the fused chunk kernel: K1 (planar) + receiver tail
-static int launch_chunk(p25fe_t* h, const void* d_x, int fmt, size_t ch_stride, size_t n_hist, size_t n, uint64_t abs0,
-                        const ChunkRecvArgs& r)
-{
-    const PlanarGeo g(p25fe_n_baseband_h(h, abs0, n));
-    return launch_frontend(h, d_x, fmt, ch_stride, n_hist, n, abs0, -(long)PLPAD - h->look, nullptr, 0, nullptr, h->stream, &g, 0,
-                           nullptr, nullptr, &r);
 }
 
 static int run_host(p25fe_t* h, const void* iq, int fmt, size_t n, uint8_t* dibits, size_t cap, size_t* n_dibits)
@@ -1886,31 +1892,23 @@ static int run_host(p25fe_t* h, const void* iq, int fmt, size_t n, uint8_t* dibi
     if (rc) return rc;
     rc = ensure_slice_scratch(h, nb);
     if (rc) return rc;
-    const size_t eb = fmt_bytes(fmt);
-    const long view0 = (long)h->abs_bb - h->look;
-    const PlanarGeo g(nb);
+    const RecvCall rcall = host_recv_call(h, o, nb, false);
     ChunkRecvArgs cr;
-    chunk_recv_args(h, o, nb, view0, false, true, &cr);
-    bool one_launch = false;
-    if (!h->track && !h->rs_n && nb <= (size_t)TS) {
+    chunk_recv_args(h, rcall, o.d_tail, &cr);
+    K1Launch k = staged_k1(h, fmt, n, sg);
+    if (!rcall.gen && nb <= (size_t)TS) {
+        // ONE launch: K1 (planar) + the receiver, run by each channel's last workgroup
         chunk_poll_arm(h, o, &cr);
-        rc = launch_chunk(h, sg.dev + SHARD_HALO * eb, fmt, sg.stride, sg.n_hist, n, h->abs_iq, cr);
+        k.planar = true; k.chunk = &cr;
+        rc = launch_k1(h, k);
         if (rc) return rc;
-        one_launch = true;
     } else {
         // the baseband stays in HBM; the receiver's history is recomputed from the IQ history, like a shard's from its halo
-        const RecvCall rcall = recv_call(h);
-        rc = launch_frontend(h, sg.dev + SHARD_HALO * eb, fmt, sg.stride, sg.n_hist, n, h->abs_iq, -(long)PLPAD - h->look, nullptr, 0,
-                             nullptr, h->stream, &g);
-        if (rc) return rc;
-        rc = launch_detect(h, nb, view0, h->stream, rcall, false);
-        if (rc) return rc;
-        rc = launch_scan_slice(h, nb, view0, o.d_anc, o.d_dib, o.dstride, nullptr, nullptr, 0, o.d_res, true, h->stream, rcall, true);
+        rc = launch_planar_recv(h, k, rcall);
         if (rc) return rc;
         hipLaunchKernelGGL(k_tail_extract, dim3((unsigned)C), dim3(WV), 0, h->stream, cr);
         HIPCHK(h, hipGetLastError());
     }
-    if (!one_launch) cr.done = nullptr;
     rc = chunk_wait(h, o, cr);
     if (rc) return rc;
     rc = recv_finish(h, o, nb, dibits, cap, n_dibits, nullptr, nullptr, 0, nullptr);
@@ -2017,7 +2015,8 @@ int p25fe_run_host_windows(p25fe_t* h, const void* iq, int fmt, size_t n, size_t
     memcpy(h_anc, h->anchor.data(), C * sizeof(p25fe_anchor_t));
     for (size_t c = 0; c < C; ++c) memcpy(h_hist + c * SHARD_HALO * eb, h->hist_iq.data() + c * SHARD_HALO * 8, SHARD_HALO * eb);
     p25fe_anchor_t* d_anc = h->win_anc.as<p25fe_anchor_t>();        // [2][C]: the carry-in of window k lives in half k & 1
-    const RecvCall rcall = recv_call(h);                             // (a pending lock-drop list holds absolute indices: every window sees it)
+    RecvCall rcall = recv_call(h);                                   // (a pending lock-drop list holds absolute indices: every window sees it)
+    rcall.dest.dibit_stride = dstride; rcall.stream = st;
     std::vector<uint64_t> total(C, 0);
     double ms_h2d = 0.0, ms_comp = 0.0;
     int status = P25FE_OK;
@@ -2071,15 +2070,14 @@ int p25fe_run_host_windows(p25fe_t* h, const void* iq, int fmt, size_t n, size_t
         if (k == 0) { WINCHK(hipMemcpyAsync(d_anc, h_anc, C * sizeof(p25fe_anchor_t), hipMemcpyHostToDevice, st)); }
         WINCHK(hipEventRecord(ev[2], st));
         const size_t nb = p25fe_n_baseband_h(h, abs0, wn);
-        const long view0 = (long)(h->abs_bb + nb_done) - h->look;
         p25fe_result_t* d_res = h->win_res.as<p25fe_result_t>() + (k % R) * C;
         uint8_t* d_dib = h->win_dib[b].as<uint8_t>();
         const PlanarGeo g(nb ? nb : 1);
-        if (nb) {
-            rc = launch_frontend(h, dev + SHARD_HALO * eb, fmt, stride, n_hist, wn, abs0, -(long)PLPAD - h->look, nullptr, 0, nullptr, st, &g);
-            if (!rc) rc = launch_detect(h, nb, view0, st, rcall, false);
-        }
-        if (!rc) rc = launch_scan_slice(h, nb, view0, d_anc + (size_t)b * C, d_dib, dstride, nullptr, nullptr, 0, d_res, nb != 0, st, rcall, nb != 0);
+        K1Launch k1;
+        k1.src = dev + SHARD_HALO * eb; k1.fmt = fmt; k1.ch_stride = stride; k1.n_hist = n_hist; k1.n = wn; k1.abs0 = abs0; k1.stream = st;
+        rcall.range.n_bb = nb; rcall.range.abs_bb0 = (long)(h->abs_bb + nb_done) - h->look; rcall.range.anchor_in = d_anc + (size_t)b * C;
+        rcall.dest.dibits = d_dib; rcall.dest.result = d_res;
+        rc = launch_planar_recv(h, k1, rcall);
         if (rc) { status = rc; break; }
         hipLaunchKernelGGL(k_anchors_from_results, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, st, d_res, d_anc + (size_t)(b ^ 1) * C, (int)C);
         if (k + 1 == n_win && nb) {                                  // the baseband tail for a later p25fe_slice on this handle
