@@ -23,8 +23,6 @@ using namespace p25k;
 
 namespace {
 
-constexpr size_t HISTPAD = 704;      // >= HIST_IQ_MAX (702 with 64 + 64 + 64 taps), multiple of 8: keeps 16-B alignment for u8 and cf32
-static_assert(HISTPAD >= (size_t)HIST_IQ_MAX && HISTPAD % 8 == 0, "stream history covers the longest filters");
 constexpr size_t BBPAD = 256;        // >= HIST_BB (240) + the tracking clock's lookahead, multiple of 4
 constexpr size_t SHARD_HALO = 2560;                     // samples (20 KB of cf32): K1 recomputes one block (320 + 2) of baseband history in front of a
                                                        // shard and needs up to 127 decimator outputs (64-tap post-discriminator and channel filters;
@@ -32,9 +30,12 @@ constexpr size_t SHARD_HALO = 2560;                     // samples (20 KB of cf3
 static_assert(SHARD_HALO >= (size_t)(DEC * (PLPAD + CLK_L + 160) + TMAX) && 160 >= TMAX + TMAX - 1 && SHARD_HALO % 8 == 0, "shard halo");
 constexpr uint32_t STATE_MAGIC = 0x50323546u;          // "P25F"
 
+// device memory, freed with its owner
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    DevBuf() = default; DevBuf(const DevBuf&) = delete; DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { release(); }
     hipError_t ensure(size_t bytes)
     {
         if (bytes <= cap) return hipSuccess;
@@ -48,12 +49,20 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
+// ... holding elements of one type: sized by count, read without a cast
+template <class T> struct DevArr {
+    DevBuf buf;
+    hipError_t ensure(size_t count) { return buf.ensure(count * sizeof(T)); }
+    T* get() const { return static_cast<T*>(buf.p); }
+};
 
 // pinned host memory that the device reads and writes in place (the streaming entry points' staging and result buffers)
 struct PinBuf {
     void* p = nullptr;          // host view
     void* dp = nullptr;         // device view of the same bytes
     size_t cap = 0;
+    PinBuf() = default; PinBuf(const PinBuf&) = delete; PinBuf& operator=(const PinBuf&) = delete;
+    ~PinBuf() { release(); }
     hipError_t ensure(size_t bytes)
     {
         if (bytes <= cap) return hipSuccess;
@@ -87,8 +96,6 @@ struct Arena {
     }
 };
 
-
-
 // Kernel launch with optional events ATTACHED TO THE DISPATCH (hipExtLaunchKernelGGL): the start / stop events are
 // signalled by the kernel's own AQL packet, where hipEventRecord would put one more barrier packet (and its release) in
 // front of the next kernel of the stream.
@@ -101,19 +108,217 @@ inline void launch_ev(void (*kern)(Args...), dim3 grid, dim3 block, size_t lds, 
 }
 inline size_t fmt_bytes(int fmt) { return fmt == P25FE_FMT_CF32 ? 8 : 2; }
 
-}  // namespace
-
 static_assert(BBPAD == (size_t)TAILN && BBPAD >= (size_t)HIST_BB + CLK_L, "baseband tail kept between calls");
 
 constexpr int MAX_LANES = 4;
-// p25fe::sh_flag: words 0 / 1 the head segment's flag and ticket, 2 / 3 the queue probe's pair, 4 "a detection gave up waiting for the head"
+// ShardCtx::flag: words 0 / 1 the head segment's flag and ticket, 2 / 3 the queue probe's pair, 4 "a detection gave up waiting for the head"
 constexpr int SH_FLAG_WORDS = 8, SH_FLAG_ERR = 4;
+constexpr int PROF_RING = 64, PROF_SAMPLE = 8;
 
+// One set of the receiver's scratch: K1's planes and everything K2 .. K4 hand each other.  A receive chain writes nothing else but the caller's
+// outputs and the per-handle buffers listed at struct p25fe, so chains on different sets may overlap.  Sized on first use (ensure_slice_scratch).
+struct RxScratch {
+    DevArr<float> pl_f; DevArr<uint32_t> pl_bits;                            // planar baseband and its sign planes (K1 or k_planarize)
+    DevArr<uint16_t> evl; DevArr<float> evthr;                               // K2: the tiles' detections and their thresholds
+    DevArr<TileRec> recs; DevArr<unsigned long long> tsum; DevArr<ScanOut> outs;
+    DevArr<GroupAgg> gagg; DevArr<GroupPre> gpre; DevArr<unsigned> gtick;    // K3 (k_scan_tiles): group aggregates, group carry-ins, the arrival counters (zero between launches)
+    DevArr<TileSumG> gsum; DevArr<ScanOutG> gouts; DevArr<uint32_t> evg;     // general receiver only (tracking clock / lock drops): allocated on first use
+    DevArr<GroupSumG> gsg; DevArr<GroupPreG> gpg;
+};
+
+// A scratch set and what orders its users.  A pipelined call runs K1 (caller's stream) -> K2 .. K4 (the handle's receive stream) -> the next K1
+// into the same set `depth` calls later: ev_k1 makes the receive stream wait for K1, ev_rx the set's next user for the chain.  (The pipelined
+// shard step rotates through up to MAX_LANES sets: its chain holds exchanges that only find room on the chip when a K1 drains, so it spans several.)
+struct Lane {
+    RxScratch s;
+    hipEvent_t ev_k1 = nullptr, ev_rx = nullptr;
+    bool pending = false;                  // ev_rx stands for receive kernels that may still be running on this set
+    hipStream_t joined = nullptr; bool joined_any = false;   // the stream that has already been made to wait for ev_rx (valid while pending && joined_any)
+};
+
+// The set a pipelined call of `depth` sets takes next, and where the one it retires goes.  With `cur` the current id and
+// q[0 .. MAX_LANES-2] the others:  new_cur = q[0]; q[0 .. d-3] = q[1 .. d-2]; q[d-2] = cur; cur = new_cur  (depth 2: a plain exchange;
+// a handle that only ever uses one depth d walks 0, 1, ..., d-1, 0, ...).  Entries of q at and beyond d-1 do not move.
+static inline void rotate_lanes(int* cur, int* q, int depth)
+{
+    const int next = q[0];
+    for (int k = 0; k + 2 < depth; ++k) q[k] = q[k + 1];
+    q[depth - 2] = *cur;
+    *cur = next;
+}
+
+// A time shard between its passes.  The planar baseband and the tile summaries stay in the current scratch set; the flags say what is there:
+//   entry point                    requires               leaves
+//   main   (pass1, _main, _k1)     --                     invalidate(); main_out for this range; head_done = the launch held the head's segments too
+//   head   (pass1_head)            main_out, same range   unless head_done: the head goes out on the caller's stream, head_flagged = it has a workgroup; head_done
+//   finish (pass1, _finish)        main_out, same range   the head goes out here unless head_done; K2 (waits for flag >= seq if head_flagged), K3; finish_pass1()
+//   pass 2                         valid                  !scan_fresh (K3 rewrites the groups' carry-ins)
+//   pass 2 dev                     valid                  the closed form on pass 1's scan iff !gen && scan_fresh && nbb != 0, else !scan_fresh
+//   pipe_begin; pipe_end           !pipe; pipe            invalidate(), pipe; !pipe
+//   any other user of the scratch  --                     invalidate(): a stale head, finish or pass 2 is refused
+struct ShardCtx {
+    bool valid = false;                    // pass 1 is complete: nbb, abs_bb0, gen describe what pass 2 finds in the scratch
+    bool main_out = false;                 // the main K1 launch of (main_nbb, main_abs0) is out, waiting for p25fe_shard_pass1_finish
+    size_t main_nbb = 0; uint64_t main_abs0 = 0;
+    bool head_done = false;                // ... and its head segment has been launched too
+    bool head_flagged = false;             // ... by p25fe_shard_pass1_head: the detection's first tiles wait for flag >= seq
+    DevBuf flag;                           // SH_FLAG_WORDS words (above)
+    unsigned seq = 0; int head_tile_max = -1;
+    size_t nbb = 0; long abs_bb0 = 0;
+    bool gen = false;                      // pass 1 ran the general receiver (pass 2 reads its summaries)
+    bool pipe = false;                     // between p25fe_shard_pipe_begin and _end: the shard passes do not join the receive stream (they ARE its work)
+    bool scan_fresh = false;               // the groups' carry-ins (`gpre`) are still pass 1's (no carry-in): p25fe_shard_pass2 rewrites them
+    bool main_is(size_t n_bb, uint64_t abs0) const { return main_out && main_nbb == n_bb && main_abs0 == abs0; }
+    void invalidate() { valid = false; main_out = false; head_done = false; head_flagged = false; }
+    void finish_pass1(size_t n_bb, long bb0, bool general) { valid = true; nbb = n_bb; abs_bb0 = bb0; gen = general; scan_fresh = true; main_out = false; head_done = false; }
+};
+
+// state blob: header | IQ history raw | baseband tail | anchors | totals
+struct StateHeader { uint32_t magic, abi; int32_t n_channels, fmt_locked; uint64_t abs_iq, abs_bb; };
+
+// Where the stream stands (the streaming entry points; per channel, all of it host side)
+struct StreamState {
+    uint64_t abs_iq = 0, abs_bb = 0;       // IQ samples consumed; baseband samples consumed by the slicer
+    int fmt_locked = -1;
+    std::vector<char> hist_iq;             // [C][SHARD_HALO] raw samples (8 bytes reserved per sample)
+    std::vector<float> tail_bb;            // [C][BBPAD]
+    std::vector<p25fe_anchor_t> anchor;    // [C]
+    std::vector<uint64_t> total_dibits;    // [C]
+    void reset(size_t C)                   // (may throw)
+    {
+        abs_iq = 0; fmt_locked = -1; abs_bb = 0;
+        anchor.assign(C, p25fe_anchor_t{0, 0.f, 0.f, 0.f, 0, SPS, 1}); total_dibits.assign(C, 0);
+        hist_iq.assign(C * SHARD_HALO * 8, 0); tail_bb.assign(C * BBPAD, 0.f);
+    }
+    bool format_refused(int fmt) const { return fmt_locked >= 0 && fmt_locked != fmt && abs_iq > 0; }
+    size_t n_hist() const { return abs_iq < SHARD_HALO ? (size_t)abs_iq : SHARD_HALO; }   // valid samples of the history
+    // n new samples per channel have been consumed (channel c's at fresh + c * row_bytes): the last SHARD_HALO samples of
+    // [history | new] become the history
+    void commit_iq(size_t C, int fmt, size_t n, const char* fresh, size_t row_bytes)
+    {
+        const size_t eb = fmt_bytes(fmt);
+        for (size_t c = 0; c < C; ++c) {
+            char* hist = hist_iq.data() + c * SHARD_HALO * 8;
+            const char* src = fresh + c * row_bytes;
+            if (n >= SHARD_HALO) memcpy(hist, src + (n - SHARD_HALO) * eb, SHARD_HALO * eb);
+            else { memmove(hist, hist + n * eb, (SHARD_HALO - n) * eb); memcpy(hist + (SHARD_HALO - n) * eb, src, n * eb); }
+        }
+        fmt_locked = fmt; abs_iq += n;
+    }
+    // Channel c's baseband tail for a later p25fe_slice after a call that produced nb samples: the newest BBPAD.  `fresh` [TAILN] is what
+    // k_tail_extract read from the planes, which hold HIST_BB + look samples in front of the call's first; what is older (a very short chunk)
+    // comes from the previous tail.  (That branch has nb - BBPAD + j < -(HIST_BB + look) <= 0, hence j + nb < BBPAD: inside the tail.)
+    void merge_tail(size_t c, size_t nb, long look, const float* fresh)
+    {
+        float* t = tail_bb.data() + c * BBPAD;
+        float merged[BBPAD];
+        for (size_t j = 0; j < (size_t)BBPAD; ++j) {
+            const long m = (long)nb - (long)BBPAD + (long)j;        // index relative to this call's first baseband sample
+            merged[j] = m >= -(long)(HIST_BB + look) ? fresh[j] : t[j + nb];
+        }
+        memcpy(t, merged, sizeof merged);
+    }
+    // the blob behind its header: these four, in this order
+    struct Sec { void* p; size_t bytes; };
+    void sections(Sec s[4])
+    {
+        s[0] = {hist_iq.data(), hist_iq.size()}; s[1] = {tail_bb.data(), tail_bb.size() * sizeof(float)};
+        s[2] = {anchor.data(), anchor.size() * sizeof(p25fe_anchor_t)}; s[3] = {total_dibits.data(), total_dibits.size() * sizeof(uint64_t)};
+    }
+    size_t blob_size() { Sec s[4]; sections(s); return sizeof(StateHeader) + s[0].bytes + s[1].bytes + s[2].bytes + s[3].bytes; }
+    void write(char* p)
+    {
+        StateHeader hd = {STATE_MAGIC, P25FE_ABI_VERSION, (int32_t)anchor.size(), fmt_locked, abs_iq, abs_bb};
+        memcpy(p, &hd, sizeof hd); p += sizeof hd;
+        Sec s[4]; sections(s);
+        for (int k = 0; k < 4; ++k) { memcpy(p, s[k].p, s[k].bytes); p += s[k].bytes; }
+    }
+    // false, and nothing taken over, if the blob is not one of a handle with this many channels and this clock (`track`)
+    bool read(const char* p, int track)
+    {
+        StateHeader hd;
+        memcpy(&hd, p, sizeof hd); p += sizeof hd;
+        if (hd.magic != STATE_MAGIC || hd.abi != P25FE_ABI_VERSION || hd.n_channels != (int32_t)anchor.size()) return false;
+        if (hd.fmt_locked != -1 && hd.fmt_locked != P25FE_FMT_U8 && hd.fmt_locked != P25FE_FMT_CF32) return false;
+        Sec s[4]; sections(s);
+        // a blob is data from outside: every anchor's clock must be a usable period before anything is taken over
+        for (size_t c = 0; c < anchor.size(); ++c) {
+            p25fe_anchor_t a;
+            memcpy(&a, p + s[0].bytes + s[1].bytes + c * sizeof a, sizeof a);
+            // (0 / 0 reads as 10 / 1: include/p25fe.h)
+            if (!(a.period_d == 0 && a.period_n == 0) && !clock_plausible(a.period_d, a.period_n)) return false;
+            if (!track && a.valid != 0 && !(a.period_d == 0 && a.period_n == 0) && !(a.period_d == SPS && a.period_n == 1)) return false;
+        }
+        for (int k = 0; k < 4; ++k) { memcpy(s[k].p, p, s[k].bytes); p += s[k].bytes; }
+        fmt_locked = hd.fmt_locked; abs_iq = hd.abs_iq; abs_bb = hd.abs_bb;
+        return true;
+    }
+};
+
+// Profiling ring: PROF_RING calls x 5 events (before K1, after K1, K2, K3, K4).  An entry point opens a slot with begin() and closes it
+// with end(); the launchers in between mark the open slot, if there is one.
+struct Prof {
+    bool on = false;
+    int level = 1;                         // 1: events around every kernel, 2: around K1 only (two records per call, not five), 3: that on a sample of the calls
+    std::vector<hipEvent_t> ev;
+    std::vector<uint8_t> mask;             // per slot: which of its five events were recorded
+    uint64_t calls = 0, seq = 0;           // seq: level 3, calls seen (every PROF_SAMPLE-th is recorded)
+    int slot = -1;                         // slot being recorded by the current call
+    void begin()
+    {
+        // level 3: only every PROF_SAMPLE-th call carries events (the two records around K1 are two more packets between kernels, ~4 us each)
+        if (on && level == 3 && (seq++ % PROF_SAMPLE) != 0) { slot = -1; return; }
+        slot = on ? (int)(calls++ % PROF_RING) : -1;
+        if (slot >= 0) mask[(size_t)slot] = 0;
+    }
+    void end() { slot = -1; }
+    // ext_events (the handle's): K1's pair rides on its dispatch (k1_events) instead of being recorded
+    void mark(int idx, hipStream_t st, bool ext_events)
+    {
+        if (slot < 0 || (idx > 1 && level != 1) || (idx <= 1 && ext_events)) return;      // levels 2, 3: only the two events around K1
+        if (hipEventRecord(ev[(size_t)slot * 5 + idx], st) == hipSuccess) mask[(size_t)slot] |= (uint8_t)(1u << idx);
+    }
+    // the open slot's pair for K1's own dispatch (null when this call is not sampled): the kernel's begin / end time stamps, no extra packet
+    void k1_events(bool ext_events, hipEvent_t* e0, hipEvent_t* e1)
+    {
+        *e0 = *e1 = nullptr;
+        if (slot < 0 || !ext_events) return;
+        *e0 = ev[(size_t)slot * 5 + 0]; *e1 = ev[(size_t)slot * 5 + 1];
+        mask[(size_t)slot] |= 3u;
+    }
+};
+
+// p25fe_run_host_windows: two device windows, dibit rows and result records in a ring, the copy streams and their events
+struct Windows {
+    DevBuf buf[2], dib[2], res, anc;
+    PinBuf stage[2], out;
+    hipStream_t cs = nullptr, os = nullptr;
+    hipEvent_t ev[4][5] = {};              // per ring slot: H2D begin / end, compute begin / end, results on the host
+    hipError_t ensure()                    // the streams and events, once
+    {
+        if (cs) return hipSuccess;
+        hipError_t e = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(&os, hipStreamNonBlocking);
+        for (auto& slot : ev) for (hipEvent_t& x : slot) if (e == hipSuccess) e = hipEventCreate(&x);
+        return e;
+    }
+};
+
+}  // namespace (the handle's parts: nothing of them is exported)
+
+// The handle.  Every call uses the scratch set lanes[cur].s; a pipelined call first moves on to the next one (pipe_open).  A set keeps
+// its id, which is its index in `lanes`.
+// Device buffers that are per HANDLE on purpose, although chains on different sets use them, and what that rests on:
+//  power_partial, chunk_cnt  K1's own: written and consumed inside one K1 launch (+ k_power_finish behind it).  Safe while a handle's K1s go down one
+//                            stream: the pipelined calls keep K1 on the caller's, the chunk calls' is h->stream (synchronised before they return).
+//  evrec, evnext, evoff      the detection list of symbol_clock = 2: only p25fe_run_dev* and p25fe_slice_dev use it, either on the one receive
+//                            stream or, unpipelined, on the caller's stream behind pipe_join; ev_seq tells the calls' entries apart.
+//  sh.flag                   one shard is between its passes at a time; K2 waits for flag >= seq, seq only grows, and the heads of consecutive
+//                            (pipelined) steps finish in order while the caller gives them one stream (p25fe_rccl.cpp does).
 struct p25fe {
+    // configuration: written by p25fe_create only
     p25fe_config_t cfg;
-    int C = 1;
-    int last_hip = 0;
-    int n_cu = 256;
+    int C = 1, n_cu = 256;
     Taps taps;                             // resolved numbers: padded tables, the u8 table, the discriminator's scale
     int k1_p = 5;                          // FIR outputs per thread
     int variant = P25FE_VARIANT_BUILTIN;   // which front-end kernels run (p25fe_kernel_variant)
@@ -121,79 +326,30 @@ struct p25fe {
     int phase = P25FE_DECIM_PHASE;         // p25fe_config_t.decim_phase: baseband sample m comes from input 5 m + phase
     int n_avg = BOX;                       // post-discriminator filter: taps in use (the table is taps.avg)
     bool u8_lut_mode = false;              // the u8 table is not affine: the specialised kernels look it up in LDS (the generic ones always do)
-    DevBuf d_taps;                         // device copy (generic kernels: everything; specialised ones: the u8 table, if not affine)
-    hipModule_t jit_mod = nullptr;         // specialised kernels (p25fe_jit.cpp): [format][linear, planar, chunk]
-    hipFunction_t jit_fn[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
-    hipStream_t stream = nullptr;          // for the host-pointer calls
-
     int track = 0;                         // p25fe_config_t.symbol_clock without its flag bits (docs/SPEC.md 3.8b)
     bool causal_ok = false;                // P25FE_CLOCK_CAUSAL_OK: mode 2 may run as mode 1 in the calls that see the stream in pieces
     long look = 0;                         // samples the receiver runs behind the baseband (2 with the tracking clock)
-    // lock drops for the next receiver-running call (p25fe_resync_at_dev); consumed by it
-    const long* rs_idx = nullptr;
-    size_t rs_n = 0, rs_stride = 0;
-    // scratch
-    DevBuf pl_f, pl_bits, evl, evthr, recs, tsum, outs, power_partial, chunk_cnt;
-    DevBuf gagg, gpre, gtick;              // K3 (k_scan_tiles): group aggregates, group carry-ins, the arrival counters (zero between launches)
-    PinBuf hin, hbb, hout;                 // streaming entry points: staged input ([history | new] IQ, [tail | new] baseband), results
-    DevBuf gsum, gouts, evg, gsg, gpg;     // general receiver only (tracking clock / lock drops): allocated on first use
-    DevBuf evrec, evnext, evoff;           // SPEC 3.8c (symbol_clock = 2, resident ranges): the list of detections, allocated on first use
-    unsigned long long ev_seq = 0;         // ... and the sequence number that marks an EvNext entry as this call's
-    // p25fe_run_dev_pipelined: a second set of the receiver's scratch (the member names above always are the set of the
-    // current call; the sets are swapped per call), the stream the receive kernels run on, and the events that order
-    // K1 (caller's stream) -> K2..K4 (rx_stream) -> next K1 into the same set two calls later
-    // (p25fe_run_dev_pipelined rotates through two sets; the pipelined shard step through up to MAX_LANES: its chain behind K1
-    // holds exchanges that only find room on the chip when a K1 launch drains, so it spans more than one K1.)  A set keeps its id
-    // (`lane` = the current one's); the events and the pending flags are indexed by it.
-    struct RxSet { DevBuf pl_f, pl_bits, evl, evthr, recs, tsum, outs, gsum, gouts, evg, gagg, gpre, gtick, gsg, gpg; int id = 0; };
-    RxSet spare[MAX_LANES - 1];
-    hipStream_t rx_stream = nullptr;
-    hipEvent_t ev_k1[MAX_LANES] = {}, ev_rx[MAX_LANES] = {};
-    bool rx_pending[MAX_LANES] = {};
-    hipStream_t rx_joined[MAX_LANES] = {};           // stream that has already been made to wait for ev_rx[l] (valid while rx_pending[l])
-    bool rx_joined_any[MAX_LANES] = {};
-    int lane = 0;
-    int sh_depth = MAX_LANES;              // sets the pipelined shard step rotates through (P25FE_SHARD_PIPE_DEPTH)
-    int run_depth = 2;                     // sets p25fe_run_dev_pipelined rotates through (P25FE_PIPE_DEPTH)
-    // p25fe_run_host_windows: two device windows, dibit rows and result records in a ring, the copy streams and their events
-    DevBuf win_buf[2], win_dib[2], win_res, win_anc;
-    PinBuf win_stage[2], win_out;
-    hipStream_t win_cs = nullptr, win_os = nullptr;
-    hipEvent_t win_ev[4][5] = {};          // per ring slot: H2D begin / end, compute begin / end, results on the host
     bool ext_events = true;                // events ride on the kernel dispatches (hipExtLaunchKernelGGL) instead of separate records
     int rx_cus = 0;                        // > 0: the receive stream is confined to this many CUs (hipExtStreamCreateWithCUMask)
-    // stream state (per channel, channel-major in the device buffers)
+    int run_depth = 2;                     // sets p25fe_run_dev_pipelined rotates through (P25FE_PIPE_DEPTH)
+    int sh_depth = MAX_LANES;              // sets the pipelined shard step rotates through (P25FE_SHARD_PIPE_DEPTH)
+
+    int last_hip = 0;
+    DevBuf d_taps;                         // device copy (generic kernels: everything; specialised ones: the u8 table, if not affine)
+    hipModule_t jit_mod = nullptr;         // specialised kernels (p25fe_jit.cpp): [format][linear, planar, chunk]
+    hipFunction_t jit_fn[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
+    hipStream_t stream = nullptr, rx_stream = nullptr;   // for the host-pointer calls; for the receive chains of the pipelined calls
+    const long* rs_idx = nullptr; size_t rs_n = 0, rs_stride = 0;    // lock drops for the next receiver-running call (p25fe_resync_at_dev); consumed by it
+    Lane lanes[MAX_LANES];
+    int cur = 0, lane_q[MAX_LANES - 1] = {1, 2, 3};    // the current set's id, the others' in the order they come up (rotate_lanes)
+    Lane& lane() { return lanes[cur]; }
+    RxScratch& rx() { return lanes[cur].s; }
+    const RxScratch& rx() const { return lanes[cur].s; }
+    DevBuf power_partial, chunk_cnt, evrec, evnext, evoff;
+    unsigned long long ev_seq = 0;         // marks an EvNext entry as this call's
+    PinBuf hin, hbb, hout;                 // streaming entry points: staged input ([history | new] IQ, [tail | new] baseband), results
     unsigned chunk_seq = 0;                // completion sequence number of the one-launch chunk calls
-    uint64_t abs_iq = 0;                   // IQ samples consumed
-    int fmt_locked = -1;
-    std::vector<char> hist_iq;             // [C][SHARD_HALO] raw samples (8 bytes reserved per sample), host side
-    uint64_t abs_bb = 0;                   // baseband samples consumed by the slicer
-    std::vector<float> tail_bb;            // [C][BBPAD], host side
-    std::vector<p25fe_anchor_t> anchor;    // [C]
-    std::vector<uint64_t> total_dibits;    // [C]
-    // profiling ring: PROF_RING calls x 5 events (before K1, after K1, K2, K3, K4)
-    bool prof_on = false;
-    int prof_level = 1;             // 1: events around every kernel, 2: around K1 only (two records per call, not five)
-    std::vector<hipEvent_t> prof_ev;
-    std::vector<uint8_t> prof_mask;        // per slot: which of its five events were recorded
-    uint64_t prof_calls = 0;
-    uint64_t prof_seq = 0;                 // level 3: calls seen (every PROF_SAMPLE-th is recorded)
-    int prof_slot = -1;                    // slot being recorded by the current call
-    // shard context between pass1 and pass2 (the planar baseband and the tile summaries stay in the scratch buffers;
-    // every other entry point that touches them clears sh_nbb, so a stale pass 2 fails instead of slicing garbage)
-    bool sh_valid = false;
-    size_t sh_main_nbb = (size_t)-1;       // shard whose main K1 launch is out, waiting for p25fe_shard_pass1_finish
-    uint64_t sh_main_abs0 = 0;
-    bool sh_head_done = false;             // ... and whose head segment has been launched too (p25fe_shard_pass1_head)
-    bool sh_head_flagged = false;          // ... by p25fe_shard_pass1_head: the detection's first tiles wait for sh_flag == sh_seq
-    DevBuf sh_flag;                        // one word a one-thread kernel behind the head writes
-    unsigned sh_seq = 0;
-    int sh_head_tile_max = -1;
-    size_t sh_nbb = 0;
-    long sh_abs_bb0 = 0;
-    bool sh_gen = false;                   // pass 1 ran the general receiver (pass 2 reads its summaries)
-    bool sh_pipe = false;                  // between p25fe_shard_pipe_begin and _end: the shard passes do not join the receive stream (they ARE its work)
-    bool sh_scan_fresh = false;            // the groups' carry-ins (`gpre`) are still pass 1's (no carry-in): p25fe_shard_pass2 rewrites them
+    Windows win; StreamState state; Prof prof; ShardCtx sh;
 };
 
 // geometry of the planar scratch for n_bb owned baseband samples (p25fe_recv.hip: Planar)
@@ -212,9 +368,6 @@ struct PlanarGeo {
 // Symbol indices are 32-bit in the receive kernels: a range holds < 2^31 symbols (124 h of one channel).  Checked by every
 // entry point BEFORE it sizes scratch for the range, so that an absurd length is an argument error, not an allocation failure.
 constexpr size_t MAX_RANGE_BB = (size_t)0x7ff00000u * 10u;
-
-constexpr int PROF_RING = 64;
-constexpr int PROF_SAMPLE = 8;
 
 // --------------------------------------------------------------------------------------------
 // p25fe_config_t -> the numbers the kernels run with.  No device needed (p25fe_specialize runs on a build host).
@@ -471,15 +624,9 @@ size_t p25fe_shard_halo(void) { return SHARD_HALO; }
 int p25fe_reset(p25fe_t* h)
 {
     if (!h) return P25FE_ERR_ARG;
-    h->abs_iq = 0;
-    h->fmt_locked = -1;
-    h->abs_bb = 0;
     h->rs_idx = nullptr; h->rs_n = 0; h->rs_stride = 0;             // a pending lock-drop list belonged to the old stream
     try {                                                           // no exception crosses the C boundary
-        h->anchor.assign((size_t)h->C, p25fe_anchor_t{0, 0.f, 0.f, 0.f, 0, SPS, 1});
-        h->total_dibits.assign((size_t)h->C, 0);
-        h->hist_iq.assign((size_t)h->C * SHARD_HALO * 8, 0);
-        h->tail_bb.assign((size_t)h->C * BBPAD, 0.f);
+        h->state.reset((size_t)h->C);
     } catch (...) {
         return P25FE_ERR_NOMEM;
     }
@@ -515,7 +662,7 @@ int p25fe_create(const p25fe_config_t* cfg, p25fe_t** out)
     h->long_taps = rs.long_taps;
     h->u8_lut_mode = !rs.lut_affine;
     h->variant = rs.dflt ? P25FE_VARIANT_BUILTIN : P25FE_VARIANT_GENERIC;
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return P25FE_ERR_HIP; }
+    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { p25fe_destroy(h); return P25FE_ERR_HIP; }
     hipError_t e = hipSuccess;
     {
         const char* pv = getenv("P25FE_K1_P");            // tuning knob: FIR outputs per lane (5 default, 3)
@@ -526,7 +673,6 @@ int p25fe_create(const p25fe_config_t* cfg, p25fe_t** out)
         h->ext_events = !(ee && atoi(ee) == 0);
         const char* rc_ = getenv("P25FE_RX_CUS");
         h->rx_cus = rc_ ? atoi(rc_) : 0;
-        for (int k = 0; k < MAX_LANES - 1; ++k) h->spare[k].id = k + 1;
         const char* pd = getenv("P25FE_SHARD_PIPE_DEPTH");            // (measurement knob: 2 .. MAX_LANES)
         if (pd && atoi(pd) >= 2 && atoi(pd) <= MAX_LANES) h->sh_depth = atoi(pd);
         // The general receiver's chain (tracking clock) is the longer one: 150 - 230 us beside a K1 of 275.  Round 5's held a 512-thread
@@ -538,7 +684,7 @@ int p25fe_create(const p25fe_config_t* cfg, p25fe_t** out)
     }
     if (e == hipSuccess) e = h->d_taps.ensure(sizeof(Taps));
     if (e == hipSuccess) e = hipMemcpy(h->d_taps.p, &h->taps, sizeof(Taps), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipStreamDestroy(h->stream); h->d_taps.release(); delete h; return P25FE_ERR_HIP; }
+    if (e != hipSuccess) { p25fe_destroy(h); return P25FE_ERR_HIP; }
     // Numbers other than the build's own: the same kernels with THOSE numbers as immediates (cached code object, else
     // hipRTC -- seconds, once per set of numbers and library build); the generic LDS-tap kernels if that is off or fails.
     {
@@ -584,67 +730,22 @@ int p25fe_create(const p25fe_config_t* cfg, p25fe_t** out)
     return P25FE_OK;
 }
 
+// What has an order: the streams drain and go, then the module and the events; `delete h` frees every buffer after that.
 void p25fe_destroy(p25fe_t* h)
 {
     if (!h) return;
     (void)hipSetDevice(h->cfg.device);
-    if (h->stream) { (void)hipStreamSynchronize(h->stream); (void)hipStreamDestroy(h->stream); }
-    if (h->rx_stream) { (void)hipStreamSynchronize(h->rx_stream); (void)hipStreamDestroy(h->rx_stream); }
+    for (hipStream_t st : {h->stream, h->rx_stream, h->win.cs, h->win.os})
+        if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
     if (h->jit_mod) (void)hipModuleUnload(h->jit_mod);
-    if (h->win_cs) { (void)hipStreamSynchronize(h->win_cs); (void)hipStreamDestroy(h->win_cs); }
-    if (h->win_os) { (void)hipStreamSynchronize(h->win_os); (void)hipStreamDestroy(h->win_os); }
-    for (auto& slot : h->win_ev) for (hipEvent_t e : slot) if (e) (void)hipEventDestroy(e);
-    for (int b = 0; b < 2; ++b) { h->win_buf[b].release(); h->win_dib[b].release(); h->win_stage[b].release(); }
-    h->win_res.release(); h->win_anc.release(); h->win_out.release();
-    for (int l = 0; l < MAX_LANES; ++l) {
-        if (h->ev_k1[l]) (void)hipEventDestroy(h->ev_k1[l]);
-        if (h->ev_rx[l]) (void)hipEventDestroy(h->ev_rx[l]);
-    }
-    for (auto& a : h->spare) {
-        DevBuf* alt[] = {&a.pl_f, &a.pl_bits, &a.evl, &a.evthr, &a.recs, &a.tsum, &a.outs, &a.gsum, &a.gouts, &a.evg, &a.gagg, &a.gpre, &a.gtick, &a.gsg, &a.gpg};
-        for (DevBuf* b : alt) b->release();
-    }
-    h->gsum.release(); h->gouts.release(); h->evg.release(); h->gsg.release(); h->gpg.release();
-    h->evrec.release(); h->evnext.release(); h->evoff.release();
-    DevBuf* bufs[] = {&h->pl_f, &h->pl_bits, &h->evl, &h->evthr, &h->recs, &h->tsum, &h->outs, &h->power_partial, &h->chunk_cnt, &h->d_taps, &h->sh_flag,
-                      &h->gagg, &h->gpre, &h->gtick};
-    for (DevBuf* b : bufs) b->release();
-    h->hin.release(); h->hbb.release(); h->hout.release();
-    for (auto& e : h->prof_ev) if (e) (void)hipEventDestroy(e);
+    for (auto& slot : h->win.ev) for (hipEvent_t e : slot) if (e) (void)hipEventDestroy(e);
+    for (Lane& l : h->lanes)
+        for (hipEvent_t e : {l.ev_k1, l.ev_rx}) if (e) (void)hipEventDestroy(e);
+    for (auto& e : h->prof.ev) if (e) (void)hipEventDestroy(e);
     delete h;
 }
 
 }  // extern "C"
-
-// --------------------------------------------------------------------------------------------
-// profiling hook
-// --------------------------------------------------------------------------------------------
-static void prof_begin(p25fe_t* h)
-{
-    // level 3: only every PROF_SAMPLE-th call carries events (the two records around K1 are two more packets between
-    // consecutive kernels, ~4 us each)
-    if (h->prof_on && h->prof_level == 3 && (h->prof_seq++ % PROF_SAMPLE) != 0) { h->prof_slot = -1; return; }
-    h->prof_slot = h->prof_on ? (int)(h->prof_calls++ % PROF_RING) : -1;
-    if (h->prof_slot >= 0) h->prof_mask[(size_t)h->prof_slot] = 0;
-}
-static void prof_mark(p25fe_t* h, int idx, hipStream_t st)
-{
-    if (h->prof_slot >= 0 && (idx <= 1 || h->prof_level == 1)) {    // levels 2, 3: only the two events around K1
-        if (idx <= 1 && h->ext_events) return;                      // K1's pair rides on its dispatch: prof_k1_events
-        if (hipEventRecord(h->prof_ev[(size_t)h->prof_slot * 5 + idx], st) == hipSuccess)
-            h->prof_mask[(size_t)h->prof_slot] |= (uint8_t)(1u << idx);
-    }
-}
-// The pair of events of the current profiling slot for K1's own dispatch (null when this call is not sampled): the
-// kernel's begin / end time stamps, no extra packet on the stream.
-static void prof_k1_events(p25fe_t* h, hipEvent_t* e0, hipEvent_t* e1)
-{
-    *e0 = *e1 = nullptr;
-    if (h->prof_slot < 0 || !h->ext_events) return;
-    *e0 = h->prof_ev[(size_t)h->prof_slot * 5 + 0];
-    *e1 = h->prof_ev[(size_t)h->prof_slot * 5 + 1];
-    h->prof_mask[(size_t)h->prof_slot] |= 3u;
-}
 
 // --------------------------------------------------------------------------------------------
 // internal launchers
@@ -756,8 +857,8 @@ static int k1_plan(const p25fe_t* h, const K1Launch& L, K1Plan* p)
     a.done_flag = L.planar ? L.done_flag : nullptr; a.done_seq = L.done_seq;
     if (L.planar) {
         const PlanarGeo g(n_out);
-        a.bbp = h->pl_f.as<float>(); a.bbp_ch_stride = (long)g.floats();
-        a.bits = h->pl_bits.as<uint8_t>(); a.bits_ch_stride = (long)(4 * g.words());
+        a.bbp = h->rx().pl_f.get(); a.bbp_ch_stride = (long)g.floats();
+        a.bits = reinterpret_cast<uint8_t*>(h->rx().pl_bits.get()); a.bits_ch_stride = (long)(4 * g.words());   // (K1 stores the sign words' bytes)
     }
     // LDS per workgroup: [d carry | window] (+ taps: generic kernels) (+ the u8 table: generic u8 kernels, and specialised ones
     // whose table is not affine).  Immediate-coefficient kernels never touch the taps area at the end of the layout: not
@@ -837,31 +938,23 @@ static int launch_k1(p25fe_t* h, const K1Launch& L)
     return P25FE_OK;
 }
 
+// the current scratch set, large enough for n_bb owned baseband samples per channel
 static int ensure_slice_scratch(p25fe_t* h, size_t n_bb)
 {
     const size_t C = (size_t)h->C;
     const PlanarGeo g(n_bb);
-    HIPCHK(h, h->pl_f.ensure(C * g.floats() * sizeof(float)));
-    HIPCHK(h, h->pl_bits.ensure(C * g.words() * sizeof(uint32_t)));
-    HIPCHK(h, h->evl.ensure(C * g.n_tiles * EVCAP * sizeof(uint16_t)));
-    HIPCHK(h, h->evthr.ensure(C * g.n_tiles * EVTHR_N * 3 * sizeof(float)));
-    HIPCHK(h, h->recs.ensure(C * g.n_tiles * sizeof(TileRec)));
-    HIPCHK(h, h->tsum.ensure(C * g.n_tiles * sizeof(unsigned long long)));
-    HIPCHK(h, h->outs.ensure(C * g.n_tiles * sizeof(ScanOut)));
-    const size_t ng = (size_t)n_groups_of((int)g.n_tiles);
-    {
-        HIPCHK(h, h->gagg.ensure(C * ng * sizeof(GroupAgg)));
-        HIPCHK(h, h->gpre.ensure(C * ng * sizeof(GroupPre)));
-        const void* before = h->gtick.p;
-        HIPCHK(h, h->gtick.ensure(C * (ng + 1) * sizeof(unsigned)));
-        if (h->gtick.p != before) HIPCHK(h, hipMemset(h->gtick.p, 0, h->gtick.cap));    // a fresh buffer: the counters start at zero and return to it
-    }
+    const size_t nt = C * g.n_tiles, ng = C * (size_t)n_groups_of((int)g.n_tiles);
+    RxScratch& s = h->rx();
+    HIPCHK(h, s.pl_f.ensure(C * g.floats())); HIPCHK(h, s.pl_bits.ensure(C * g.words()));
+    HIPCHK(h, s.evl.ensure(nt * EVCAP)); HIPCHK(h, s.evthr.ensure(nt * EVTHR_N * 3));
+    HIPCHK(h, s.recs.ensure(nt)); HIPCHK(h, s.tsum.ensure(nt)); HIPCHK(h, s.outs.ensure(nt));
+    HIPCHK(h, s.gagg.ensure(ng)); HIPCHK(h, s.gpre.ensure(ng));
+    const unsigned* before = s.gtick.get();
+    HIPCHK(h, s.gtick.ensure(ng + C));
+    if (s.gtick.get() != before) HIPCHK(h, hipMemset(s.gtick.get(), 0, s.gtick.buf.cap));    // a fresh buffer: the counters start at zero and return to it
     if (h->track || h->rs_n) {                                       // the general receiver's summaries and carry-ins
-        HIPCHK(h, h->gsum.ensure(C * g.n_tiles * sizeof(TileSumG)));
-        HIPCHK(h, h->gouts.ensure(C * g.n_tiles * sizeof(ScanOutG)));
-        HIPCHK(h, h->evg.ensure(C * g.n_tiles * EVCAP * sizeof(uint32_t)));
-        HIPCHK(h, h->gsg.ensure(C * ng * sizeof(GroupSumG)));
-        HIPCHK(h, h->gpg.ensure(C * ng * sizeof(GroupPreG)));
+        HIPCHK(h, s.gsum.ensure(nt)); HIPCHK(h, s.gouts.ensure(nt)); HIPCHK(h, s.evg.ensure(nt * EVCAP));
+        HIPCHK(h, s.gsg.ensure(ng)); HIPCHK(h, s.gpg.ensure(ng));
     }
     return P25FE_OK;
 }
@@ -914,8 +1007,8 @@ static inline int n_tiles_of(const RecvRange& r) { return r.n_bb ? (int)PlanarGe
 static Planar planar_view(const p25fe_t* h, const PlanarGeo& g)
 {
     Planar p;
-    p.f = h->pl_f.as<float>(); p.f_ch = (long)g.floats();
-    p.bits = h->pl_bits.as<uint32_t>(); p.bits_ch = (long)g.words();
+    p.f = h->rx().pl_f.get(); p.f_ch = (long)g.floats();
+    p.bits = h->rx().pl_bits.get(); p.bits_ch = (long)g.words();
     return p;
 }
 
@@ -924,13 +1017,13 @@ static Planar planar_view(const p25fe_t* h, const PlanarGeo& g)
 template <class A> static void view_planes(const p25fe_t* h, const RecvRange& r, A* a)       // K2, K4 (all forms), the chunk receiver
 {
     a->pl = planar_view(h, PlanarGeo(r.n_bb)); a->n = (long)r.n_bb; a->abs0 = r.abs_bb0;
-    a->evl = h->evl.as<uint16_t>(); a->evthr = h->evthr.as<float>();
+    a->evl = h->rx().evl.get(); a->evthr = h->rx().evthr.get();
 }
-template <class A> static void view_tiles(const p25fe_t* h, A* a) { a->recs = h->recs.as<TileRec>(); a->tsum = h->tsum.as<unsigned long long>(); }
-template <class A> static void view_general(const p25fe_t* h, A* a) { a->gsum = h->gsum.as<TileSumG>(); a->evg = h->evg.as<uint32_t>(); }
+template <class A> static void view_tiles(const p25fe_t* h, A* a) { a->recs = h->rx().recs.get(); a->tsum = h->rx().tsum.get(); }
+template <class A> static void view_general(const p25fe_t* h, A* a) { a->gsum = h->rx().gsum.get(); a->evg = h->rx().evg.get(); }
 template <class A> static void view_scan(const p25fe_t* h, const RecvCall& rc, A* a)         // K3, both receivers
 {
-    a->recs = h->recs.as<TileRec>(); a->tickets = h->gtick.as<unsigned>();
+    a->recs = h->rx().recs.get(); a->tickets = h->rx().gtick.get();
     a->n_tiles = n_tiles_of(rc.range); a->n = (long)rc.range.n_bb; a->abs0 = rc.range.abs_bb0; a->n_baseband = rc.range.n_bb;
     a->anchor_in = rc.range.anchor_in; a->result = rc.dest.result;
 }
@@ -947,8 +1040,8 @@ static int launch_planarize(p25fe_t* h, const float* d_bb, size_t bb_stride, siz
     const PlanarGeo g(n_bb);
     PlanarizeArgs a;
     a.bb = d_bb; a.bb_stride = (long)bb_stride; a.n_hist = (long)n_hist_bb; a.n = (long)n_bb;
-    a.f = h->pl_f.as<float>(); a.f_ch = (long)g.floats();
-    a.bits = h->pl_bits.as<uint32_t>(); a.bits_ch = (long)g.words(); a.n_blocks = (long)g.n_blocks;
+    a.f = h->rx().pl_f.get(); a.f_ch = (long)g.floats();
+    a.bits = h->rx().pl_bits.get(); a.bits_ch = (long)g.words(); a.n_blocks = (long)g.n_blocks;
     a.shift = (int)h->look;
     hipLaunchKernelGGL(k_planarize, dim3((unsigned)((g.n_blocks + 1) / 2), (unsigned)h->C), dim3(WV * SPS), 0, st, a);
     HIPCHK(h, hipGetLastError());
@@ -961,8 +1054,8 @@ static int launch_detect(p25fe_t* h, const RecvCall& rc)
     DetArgs d;
     d.head_flag = nullptr; d.head_seq = 0u; d.head_tile_max = -1; d.head_err = nullptr;
     if (rc.wait_head) {
-        d.head_flag = h->sh_flag.as<unsigned>(); d.head_seq = h->sh_seq; d.head_tile_max = h->sh_head_tile_max;
-        d.head_err = h->sh_flag.as<unsigned>() + SH_FLAG_ERR;
+        d.head_flag = h->sh.flag.as<unsigned>(); d.head_seq = h->sh.seq; d.head_tile_max = h->sh.head_tile_max;
+        d.head_err = h->sh.flag.as<unsigned>() + SH_FLAG_ERR;
     }
     view_planes(h, rc.range, &d); view_tiles(h, &d); view_general(h, &d);
     d.n_tiles = n_tiles_of(rc.range); d.opt = rc.opt;
@@ -982,14 +1075,14 @@ static int launch_scan(p25fe_t* h, const RecvCall& rc, ScanStep step, hipEvent_t
     if (rc.gen) {
         ScanArgsG c;
         view_scan(h, rc, &c);
-        c.gsum = h->gsum.as<TileSumG>(); c.outs = h->gouts.as<ScanOutG>(); c.gsg = h->gsg.as<GroupSumG>(); c.gpg = h->gpg.as<GroupPreG>();
+        c.gsum = h->rx().gsum.get(); c.outs = h->rx().gouts.get(); c.gsg = h->rx().gsg.get(); c.gpg = h->rx().gpg.get();
         c.track = h->track;
         launch_ev(step == SCAN_WHOLE ? k_scan_tiles_g : step == SCAN_RANGE ? k_range_scan_g : k_scan_g_groups, grid, dim3(WV), 0, rc.stream,
                   nullptr, ev_done, c);
     } else {
         ScanArgs c;
         view_scan(h, rc, &c);
-        c.tsum = h->tsum.as<unsigned long long>(); c.outs = h->outs.as<ScanOut>(); c.gagg = h->gagg.as<GroupAgg>(); c.gpre = h->gpre.as<GroupPre>();
+        c.tsum = h->rx().tsum.get(); c.outs = h->rx().outs.get(); c.gagg = h->rx().gagg.get(); c.gpre = h->rx().gpre.get();
         launch_ev(step == SCAN_WHOLE ? k_scan_tiles : k_range_scan, grid, dim3(WV), 0, rc.stream, nullptr, ev_done, c);
     }
     HIPCHK(h, hipGetLastError());
@@ -1001,7 +1094,7 @@ static int launch_slice(p25fe_t* h, const RecvCall& rc)
 {
     SliceArgs l;
     view_planes(h, rc.range, &l); view_tiles(h, &l); view_dest(rc.range, rc.dest, &l);
-    l.n_tiles = n_tiles_of(rc.range); l.outs = h->outs.as<ScanOut>(); l.gpre = h->gpre.as<GroupPre>(); l.dibits2 = rc.dest.dibits2;
+    l.n_tiles = n_tiles_of(rc.range); l.outs = h->rx().outs.get(); l.gpre = h->rx().gpre.get(); l.dibits2 = rc.dest.dibits2;
     if (rc.fix) l.fix = *rc.fix; else memset(&l.fix, 0, sizeof l.fix);
     // (pass 2 of a time shard: one extra workgroup runs the combine for the record beside the slicing ones)
     launch_ev(k_slice, dim3((unsigned)l.n_tiles + (rc.fix ? 1u : 0u), (unsigned)h->C), dim3(WV), 0, rc.stream, nullptr, rc.ev_done, l);
@@ -1014,7 +1107,7 @@ static int launch_slice_g(p25fe_t* h, const RecvCall& rc)
 {
     SliceArgsG l;
     view_planes(h, rc.range, &l); view_general(h, &l); view_dest(rc.range, rc.dest, &l);
-    l.n_tiles = n_tiles_of(rc.range); l.outs = h->gouts.as<ScanOutG>(); l.recs = h->recs.as<TileRec>();
+    l.n_tiles = n_tiles_of(rc.range); l.outs = h->rx().gouts.get(); l.recs = h->rx().recs.get();
     l.track = h->track; l.dibits2 = rc.dest.dibits2;
     launch_ev(k_slice_g, dim3((unsigned)l.n_tiles, (unsigned)h->C), dim3(WV), 0, rc.stream, nullptr, rc.ev_done, l);
     HIPCHK(h, hipGetLastError());
@@ -1040,7 +1133,7 @@ static int launch_slice_by_detection(p25fe_t* h, const RecvCall& rc)
     }
     EvArgs e;
     view_planes(h, rc.range, &e); view_general(h, &e); view_dest(rc.range, rc.dest, &e);
-    e.n_tiles = n_tiles; e.outs = h->gouts.as<ScanOutG>();
+    e.n_tiles = n_tiles; e.outs = h->rx().gouts.get();
     e.rec = h->evrec.as<EvRec>(); e.nxt = h->evnext.as<EvNext>(); e.off = h->evoff.as<unsigned long long>();
     e.ev_stride = (long)stride; e.seq = ++h->ev_seq; e.result = rc.dest.result;
     hipLaunchKernelGGL(k_ev_collect, dim3((unsigned)n_tiles, (unsigned)h->C), dim3(WV), 0, st, e);
@@ -1066,16 +1159,16 @@ static int launch_recv(p25fe_t* h, const RecvCall& rc)
     hipStream_t st = rc.stream;
     int e = detect ? launch_detect(h, rc) : P25FE_OK;
     if (e) return e;
-    prof_mark(h, 2, st);
+    h->prof.mark(2, st, h->ext_events);
     if (scan && (e = launch_scan(h, rc, detect ? SCAN_WHOLE : SCAN_RANGE, slice ? nullptr : rc.ev_done)) != P25FE_OK) return e;
-    prof_mark(h, 3, st);
+    h->prof.mark(3, st, h->ext_events);
     if (slice) {
         if (!rc.gen) e = launch_slice(h, rc);
         else if ((e = launch_scan(h, rc, SCAN_TILES_G, nullptr)) == P25FE_OK) e = rc.reslice ? launch_slice_by_detection(h, rc) : launch_slice_g(h, rc);
         if (e) return e;
     }
     if (rc.ev_done && !scan && !slice) HIPCHK(h, hipEventRecord(rc.ev_done, st));
-    prof_mark(h, 4, st);
+    h->prof.mark(4, st, h->ext_events);
     return P25FE_OK;
 }
 
@@ -1083,10 +1176,10 @@ static int launch_recv(p25fe_t* h, const RecvCall& rc)
 // k1_done (nullable): fires when K1 has finished -- riding on its dispatch if h->ext_events -- and `waiter` waits for it.
 static int launch_k1_planar(p25fe_t* h, K1Launch& k, hipEvent_t k1_done, hipStream_t waiter)
 {
-    prof_mark(h, 0, k.stream);
+    h->prof.mark(0, k.stream, h->ext_events);
     bool attached = false;
     if (p25fe_n_baseband_h(h, k.abs0, k.n)) {
-        prof_k1_events(h, &k.ev0, &k.ev1);
+        h->prof.k1_events(h->ext_events, &k.ev0, &k.ev1);
         if (k1_done && h->ext_events) {
             if (k.ev1) k1_done = k.ev1;                             // a sampled call: the profiling stop event doubles as "K1 done"
             else k.ev1 = k1_done;
@@ -1106,7 +1199,7 @@ static int launch_k1_planar(p25fe_t* h, K1Launch& k, hipEvent_t k1_done, hipStre
 static int launch_planar_recv(p25fe_t* h, K1Launch& k, const RecvCall& rc, hipEvent_t k1_done = nullptr)
 {
     if (int e = launch_k1_planar(h, k, k1_done, rc.stream)) return e;
-    if (rc.range.n_bb) prof_mark(h, 1, k.stream);
+    if (rc.range.n_bb) h->prof.mark(1, k.stream, h->ext_events);
     return launch_recv(h, rc);
 }
 
@@ -1114,14 +1207,6 @@ static int launch_planar_recv(p25fe_t* h, K1Launch& k, const RecvCall& rc, hipEv
 // passes of a time shard) can only run 3.8b's causal rule; a handle that asked for 3.8c gets that ONLY if it said so
 // (P25FE_CLOCK_CAUSAL_OK) -- otherwise the call is refused instead of quietly returning another receiver's dibits.
 static inline bool piecewise_refused(const p25fe_t* h) { return h->track == P25FE_CLOCK_TRACKING_RESLICE && !h->causal_ok; }
-
-// every entry point that overwrites the receiver's scratch: a shard's pass-1 context is gone
-static void shard_invalidate(p25fe_t* h)
-{
-    h->sh_valid = false;
-    h->sh_main_nbb = (size_t)-1;             // a later p25fe_shard_pass1_finish must not pair with a main launch whose planes are gone
-    h->sh_head_done = false; h->sh_head_flagged = false;
-}
 
 extern "C" {
 
@@ -1189,10 +1274,10 @@ static int pipe_join(p25fe_t* h, hipStream_t st)
 {
     // The events stay pending until the lane is reused: a later call on ANOTHER stream must wait too (the receive
     // kernels may still be running and share the scratch with whatever that call launches).
-    for (int l = 0; l < MAX_LANES; ++l)
-        if (h->rx_pending[l] && !(h->rx_joined_any[l] && h->rx_joined[l] == st)) {
-            HIPCHK(h, hipStreamWaitEvent(st, h->ev_rx[l], 0));
-            h->rx_joined[l] = st; h->rx_joined_any[l] = true;
+    for (Lane& l : h->lanes)
+        if (l.pending && !(l.joined_any && l.joined == st)) {
+            HIPCHK(h, hipStreamWaitEvent(st, l.ev_rx, 0));
+            l.joined = st; l.joined_any = true;
         }
     return P25FE_OK;
 }
@@ -1205,7 +1290,7 @@ int p25fe_slice_dev(p25fe_t* h, const float* d_bb, size_t bb_stride, size_t n_hi
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (n_bb > MAX_RANGE_BB) return P25FE_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
-    shard_invalidate(h);
+    h->sh.invalidate();
     if (int jrc = pipe_join(h, st)) return jrc;
     int rc = ensure_slice_scratch(h, n_bb ? n_bb : 1);
     if (rc) return rc;
@@ -1230,8 +1315,6 @@ int p25fe_join_dev(p25fe_t* h, void* stream)
     return pipe_join(h, (hipStream_t)stream);
 }
 
-// The preamble of a pipelined call: the receive stream and its events exist, the OTHER scratch set becomes the current one, and
-// `st` (where K1 is about to overwrite that set's planes) waits for the receive kernels that last read it, two calls back.
 static int ensure_rx_stream(p25fe_t* h)
 {
     if (!h->rx_stream) {
@@ -1263,34 +1346,23 @@ static int ensure_rx_stream(p25fe_t* h)
     }
     return P25FE_OK;
 }
+// The preamble of a pipelined call: the receive stream and the lanes' events exist, the NEXT scratch set becomes the current one, and
+// `st` (where K1 is about to overwrite that set's planes) waits for the receive kernels that last read it, `depth` calls back.
 static int pipe_open(p25fe_t* h, hipStream_t st, int depth = 2)
 {
     if (int rc = ensure_rx_stream(h)) return rc;
-    for (int l = 0; l < MAX_LANES; ++l) {                            // (per event: a failed creation is retried by the next call)
-        if (!h->ev_k1[l]) HIPCHK(h, hipEventCreateWithFlags(&h->ev_k1[l], hipEventDisableTiming));
-        if (!h->ev_rx[l]) HIPCHK(h, hipEventCreateWithFlags(&h->ev_rx[l], hipEventDisableTiming));
+    for (Lane& l : h->lanes) {                                       // (per event: a failed creation is retried by the next call)
+        if (!l.ev_k1) HIPCHK(h, hipEventCreateWithFlags(&l.ev_k1, hipEventDisableTiming));
+        if (!l.ev_rx) HIPCHK(h, hipEventCreateWithFlags(&l.ev_rx, hipEventDisableTiming));
     }
-    // the other scratch set becomes the current one; it was last read by the receive kernels of the call before the
-    // previous one, which this call's K1 (it overwrites the planes) has to wait for
-    {
-        p25fe::RxSet& a = h->spare[0];
-        std::swap(h->pl_f, a.pl_f); std::swap(h->pl_bits, a.pl_bits); std::swap(h->evl, a.evl);
-        std::swap(h->evthr, a.evthr); std::swap(h->recs, a.recs); std::swap(h->tsum, a.tsum);
-        std::swap(h->outs, a.outs);
-        std::swap(h->gagg, a.gagg); std::swap(h->gpre, a.gpre); std::swap(h->gtick, a.gtick);
-        std::swap(h->gsum, a.gsum); std::swap(h->gouts, a.gouts); std::swap(h->evg, a.evg);
-        std::swap(h->gsg, a.gsg); std::swap(h->gpg, a.gpg);
-        std::swap(h->lane, a.id);
-        // the set just retired goes behind the other spare ones of this depth (depth 2: a plain swap)
-        for (int k = 0; k + 2 < depth && k + 1 < MAX_LANES - 1; ++k) std::swap(h->spare[k], h->spare[k + 1]);
-    }
-    const int lane = h->lane;
-    if (h->rx_pending[lane]) {
+    rotate_lanes(&h->cur, h->lane_q, depth);
+    Lane& l = h->lane();
+    if (l.pending) {
         const bool nowait = P25FE_M_PIPE_NOWAIT();                   // (false in the product: measurement hook, p25fe_kernels.hip)
-        if (!nowait && !(h->rx_joined_any[lane] && h->rx_joined[lane] == st)) HIPCHK(h, hipStreamWaitEvent(st, h->ev_rx[lane], 0));
-        h->rx_pending[lane] = false;
+        if (!nowait && !(l.joined_any && l.joined == st)) HIPCHK(h, hipStreamWaitEvent(st, l.ev_rx, 0));
+        l.pending = false;
     }
-    h->rx_joined_any[lane] = false;
+    l.joined_any = false;
     return P25FE_OK;
 }
 
@@ -1301,9 +1373,9 @@ static int run_dev(p25fe_t* h, const void* d_iq, int fmt, size_t ch_stride, size
 {
     if (!h || !d_iq || !dest.dibits || !dest.result || p25fe_n_baseband_h(h, 0, n) > MAX_RANGE_BB) return P25FE_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    shard_invalidate(h);
+    h->sh.invalidate();
     if (int orc = pipelined ? pipe_open(h, st, h->run_depth) : pipe_join(h, st)) return orc;
-    const int lane = h->lane;
+    Lane& lane = h->lane();
     const size_t n_bb = p25fe_n_baseband_h(h, 0, n);
     int rc = ensure_slice_scratch(h, n_bb ? n_bb : 1);   // (growing a buffer frees the old one: hipFree synchronises the device)
     if (rc) return rc;
@@ -1313,15 +1385,15 @@ static int run_dev(p25fe_t* h, const void* d_iq, int fmt, size_t ch_stride, size
     rcall.range.n_bb = n_bb; rcall.range.abs_bb0 = -h->look;
     rcall.dest = dest;
     rcall.stream = pipelined ? h->rx_stream : st;
-    if (pipelined && h->ext_events) rcall.ev_done = h->ev_rx[lane];
+    if (pipelined && h->ext_events) rcall.ev_done = lane.ev_rx;
     K1Launch k;
     k.src = d_iq; k.fmt = fmt; k.ch_stride = ch_stride; k.n = n; k.stream = st;
-    if (n_bb) prof_begin(h);
-    rc = launch_planar_recv(h, k, rcall, pipelined ? h->ev_k1[lane] : nullptr);
-    h->prof_slot = -1;
+    if (n_bb) h->prof.begin();
+    rc = launch_planar_recv(h, k, rcall, pipelined ? lane.ev_k1 : nullptr);
+    h->prof.end();
     if (rc || !pipelined) return rc;
-    if (!h->ext_events) HIPCHK(h, hipEventRecord(h->ev_rx[lane], h->rx_stream));
-    h->rx_pending[lane] = true;
+    if (!h->ext_events) HIPCHK(h, hipEventRecord(lane.ev_rx, h->rx_stream));
+    lane.pending = true;
     return P25FE_OK;
 }
 
@@ -1352,10 +1424,10 @@ static int shard_pass1_part(p25fe_t* h, const void* d_iq, int fmt, size_t ch_str
     const bool do_main = (what & SH_MAIN) != 0, do_finish = (what & SH_RECV) != 0;
     bool do_head = (what & SH_HEAD) != 0;
     if (!h || !d_iq || (do_finish && !d_result) || p25fe_n_baseband_h(h, abs0, n) > MAX_RANGE_BB || piecewise_refused(h)) return P25FE_ERR_ARG;
-    if (do_main) shard_invalidate(h);
+    if (do_main) h->sh.invalidate();
     if (n_hist < SHARD_HALO && n_hist != abs0) return P25FE_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (!h->sh_pipe)
+    if (!h->sh.pipe)
         if (int jrc = pipe_join(h, st)) return jrc;
     const size_t n_bb = p25fe_n_baseband_h(h, abs0, n);
     const long abs_bb0 = (long)p25fe_n_baseband_h(h, 0, (size_t)abs0) - h->look;      // first processed baseband index of this shard
@@ -1365,62 +1437,61 @@ static int shard_pass1_part(p25fe_t* h, const void* d_iq, int fmt, size_t ch_str
     K1Launch k;
     k.src = d_iq; k.fmt = fmt; k.ch_stride = ch_stride; k.n_hist = n_hist; k.n = n; k.abs0 = abs0; k.planar = true; k.stream = st;
     if (do_main) {
-        prof_begin(h);
+        h->prof.begin();
         // K1's event pair rides on THIS launch: with the split form it times the main launch alone (the head segment
         // that follows the halo wait is one workgroup), so an RCCL wait between the two is not in K1's figure.
         // Pipelined step: everything behind this launch runs on the receive stream, which waits for it here
         // (K1 on a CU-masked stream of its own, to keep a few CUs free for the exchanges that run beside it, was tried: the
         // masked launch itself ran 30 - 60 % slower -- profiles/r05_shard_pipelined.txt)
         k.part = do_head ? K1_ALL : K1_MAIN;
-        rc = launch_k1_planar(h, k, h->sh_pipe ? h->ev_k1[h->lane] : nullptr, h->rx_stream);
+        rc = launch_k1_planar(h, k, h->sh.pipe ? h->lane().ev_k1 : nullptr, h->rx_stream);
         if (rc) return rc;
-        h->sh_main_nbb = n_bb; h->sh_main_abs0 = abs0;
-        h->sh_head_done = do_head;
+        h->sh.main_out = true; h->sh.main_nbb = n_bb; h->sh.main_abs0 = abs0;
+        h->sh.head_done = do_head;
         do_head = false;                                            // (K1_ALL = every segment)
     } else {
-        if (h->sh_main_nbb != n_bb || h->sh_main_abs0 != abs0) return P25FE_ERR_ARG;     // head / finish without its main launch
+        if (!h->sh.main_is(n_bb, abs0)) return P25FE_ERR_ARG;       // head / finish without its main launch
     }
-    if ((do_head || do_finish) && !h->sh_head_done) {
+    if ((do_head || do_finish) && !h->sh.head_done) {
         // the segments whose input reaches into the halo.  They share no byte of the planes with the main launch's
         // (SEG_HALO in p25fe_kernels.hip), so this launch may run BESIDE it on another stream (p25fe_shard_pass1_head).
         long head_end = 0;                                          // planar positions [0, head_end) are the head's
         const bool own_stream = !do_finish;                         // launched on its own (another stream's)
-        h->sh_head_flagged = false;
+        h->sh.head_flagged = false;
         if (n_bb) {
             if (own_stream) {
                 // the launch's last workgroup publishes "the head is in memory"; the detection's first tiles wait for that
                 // word instead of the whole stream waiting for an event
-                if (!h->sh_flag.p) {
-                    HIPCHK(h, h->sh_flag.ensure(SH_FLAG_WORDS * sizeof(unsigned)));
-                    HIPCHK(h, hipMemsetAsync(h->sh_flag.p, 0, SH_FLAG_WORDS * sizeof(unsigned), st));
+                if (!h->sh.flag.p) {
+                    HIPCHK(h, h->sh.flag.ensure(SH_FLAG_WORDS * sizeof(unsigned)));
+                    HIPCHK(h, hipMemsetAsync(h->sh.flag.p, 0, SH_FLAG_WORDS * sizeof(unsigned), st));
                 }
-                ++h->sh_seq;
-                if (h->sh_seq == 0u) ++h->sh_seq;
+                ++h->sh.seq;
+                if (h->sh.seq == 0u) ++h->sh.seq;
             }
             k.part = K1_HEAD; k.ev0 = k.ev1 = nullptr; k.head_end = &head_end;
-            k.done_flag = own_stream ? h->sh_flag.as<unsigned>() : nullptr; k.done_seq = h->sh_seq;
+            k.done_flag = own_stream ? h->sh.flag.as<unsigned>() : nullptr; k.done_seq = h->sh.seq;
             rc = launch_k1(h, k);
             if (rc) return rc;
             if (own_stream && head_end > 0) {                       // (no head workgroup, no flag: nothing to wait for)
-                h->sh_head_flagged = true;
-                h->sh_head_tile_max = (int)(head_end / TS);         // a tile reads planes up to its own end (+ one sign word): tiles past the head's never touch it
+                h->sh.head_flagged = true;
+                h->sh.head_tile_max = (int)(head_end / TS);         // a tile reads planes up to its own end (+ one sign word): tiles past the head's never touch it
             }
         }
-        h->sh_head_done = true;
+        h->sh.head_done = true;
     }
     if (!do_finish) return P25FE_OK;
-    prof_mark(h, 1, st);
+    h->prof.mark(1, st, h->ext_events);
     RecvCall rcall = recv_call(h);
     h->rs_n = 0;
     rcall.range.n_bb = n_bb; rcall.range.abs_bb0 = abs_bb0;
     rcall.dest.result = d_result;
-    rcall.slice = false; rcall.wait_head = h->sh_head_flagged; rcall.stream = st;
+    rcall.slice = false; rcall.wait_head = h->sh.head_flagged; rcall.stream = st;
     rc = launch_recv(h, rcall);
-    h->sh_head_flagged = false;
-    h->prof_slot = -1;
+    h->sh.head_flagged = false;
+    h->prof.end();
     if (rc) return rc;
-    h->sh_valid = true; h->sh_nbb = n_bb; h->sh_abs_bb0 = abs_bb0; h->sh_gen = rcall.gen; h->sh_scan_fresh = true;
-    h->sh_main_nbb = (size_t)-1; h->sh_head_done = false;
+    h->sh.finish_pass1(n_bb, abs_bb0, rcall.gen);
     return P25FE_OK;
 }
 
@@ -1458,11 +1529,11 @@ int p25fe_shard_pass1_finish(p25fe_t* h, const void* d_iq, int fmt, size_t ch_st
 // it, every later pass is given the receive stream.  _end marks that stream's work as pending (p25fe_join_dev waits for it).
 int p25fe_shard_pipe_begin(p25fe_t* h, void* stream, void** rx_stream)
 {
-    if (!h || !rx_stream || h->sh_pipe) return P25FE_ERR_ARG;
+    if (!h || !rx_stream || h->sh.pipe) return P25FE_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    shard_invalidate(h);
+    h->sh.invalidate();
     if (int orc = pipe_open(h, (hipStream_t)stream, h->sh_depth)) return orc;
-    h->sh_pipe = true;
+    h->sh.pipe = true;
     *rx_stream = h->rx_stream;
     return P25FE_OK;
 }
@@ -1478,11 +1549,11 @@ int p25fe_rx_stream(p25fe_t* h, void** rx_stream)
 
 int p25fe_shard_pipe_end(p25fe_t* h, void* last_stream)
 {
-    if (!h || !h->sh_pipe) return P25FE_ERR_ARG;
-    h->sh_pipe = false;
+    if (!h || !h->sh.pipe) return P25FE_ERR_ARG;
+    h->sh.pipe = false;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipEventRecord(h->ev_rx[h->lane], last_stream ? (hipStream_t)last_stream : h->rx_stream));
-    h->rx_pending[h->lane] = true;
+    HIPCHK(h, hipEventRecord(h->lane().ev_rx, last_stream ? (hipStream_t)last_stream : h->rx_stream));
+    h->lane().pending = true;
     return P25FE_OK;
 }
 
@@ -1491,9 +1562,9 @@ static RecvCall shard_pass2_call(const p25fe_t* h, const p25fe_anchor_t* d_ancho
                                  hipStream_t st)
 {
     RecvCall c = recv_call(h);
-    c.gen = h->sh_gen;
+    c.gen = h->sh.gen;
     c.detect = false;
-    c.range.n_bb = h->sh_nbb; c.range.abs_bb0 = h->sh_abs_bb0; c.range.anchor_in = d_anchor_in;
+    c.range.n_bb = h->sh.nbb; c.range.abs_bb0 = h->sh.abs_bb0; c.range.anchor_in = d_anchor_in;
     c.dest.dibits = d_dibits; c.dest.dibit_stride = dibit_stride; c.dest.result = d_result;
     c.stream = st;
     return c;
@@ -1502,13 +1573,13 @@ static RecvCall shard_pass2_call(const p25fe_t* h, const p25fe_anchor_t* d_ancho
 int p25fe_shard_pass2(p25fe_t* h, const p25fe_anchor_t* d_anchor_in, uint8_t* d_dibits, size_t dibit_stride,
                       p25fe_result_t* d_result, void* stream)
 {
-    if (!h || !d_dibits || !d_result || !h->sh_valid) return P25FE_ERR_ARG;
+    if (!h || !d_dibits || !d_result || !h->sh.valid) return P25FE_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     RecvCall rcall = shard_pass2_call(h, d_anchor_in, d_dibits, dibit_stride, d_result, (hipStream_t)stream);
-    h->sh_scan_fresh = false;                            // the re-scan below rewrites the groups' carry-ins with THIS carry-in
-    prof_begin(h);
+    h->sh.scan_fresh = false;                            // the re-scan below rewrites the groups' carry-ins with THIS carry-in
+    h->prof.begin();
     const int rc = launch_recv(h, rcall);
-    h->prof_slot = -1;
+    h->prof.end();
     return rc;
 }
 
@@ -1516,7 +1587,7 @@ int p25fe_shard_pass2_dev(p25fe_t* h, const p25fe_result_t* d_summaries, const u
                           size_t n_shards, size_t rank, p25fe_anchor_t* d_anchor_in, uint64_t* d_dibit_offset, uint8_t* d_dibits,
                           size_t dibit_stride, uint8_t* d_dibits_dup, p25fe_result_t* d_result, void* stream)
 {
-    if (!h || !d_summaries || !d_shard_bb0 || !d_shard_bb_n || !d_anchor_in || !d_dibit_offset || !d_dibits || !d_result || !h->sh_valid ||
+    if (!h || !d_summaries || !d_shard_bb0 || !d_shard_bb_n || !d_anchor_in || !d_dibit_offset || !d_dibits || !d_result || !h->sh.valid ||
         n_shards == 0 || n_shards > 0x7fffffffu || rank >= n_shards || h->C != 1)
         return P25FE_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -1524,11 +1595,11 @@ int p25fe_shard_pass2_dev(p25fe_t* h, const p25fe_result_t* d_summaries, const u
     RecvCall rcall = shard_pass2_call(h, d_anchor_in + rank, d_dibits, dibit_stride, d_result, st);
     rcall.dest.dibits2 = d_dibits_dup;
     ShardFix fx;
-    if (rcall.gen || !h->sh_scan_fresh || h->sh_nbb == 0) {
+    if (rcall.gen || !h->sh.scan_fresh || h->sh.nbb == 0) {
         // tracking clock / lock drops inside the shard (or a p25fe_shard_pass2 has already rewritten pass 1's scan; or a shard without a
         // baseband sample, which has no slicer tile to run the combine in: never the hot path): the combine as its own (one-thread)
         // launch, then the re-scan of the shard's groups + slicer with that carry-in
-        h->sh_scan_fresh = false;
+        h->sh.scan_fresh = false;
         hipLaunchKernelGGL(k_shard_resolve, dim3(1), dim3(64), 0, st, d_summaries, d_shard_bb0, d_shard_bb_n, (int)n_shards, h->track,
                            d_anchor_in, d_dibit_offset);
         HIPCHK(h, hipGetLastError());
@@ -1537,9 +1608,9 @@ int p25fe_shard_pass2_dev(p25fe_t* h, const p25fe_result_t* d_summaries, const u
         fx.anc_out = d_anchor_in; fx.off_out = d_dibit_offset; fx.result = d_result;
         rcall.range.anchor_in = nullptr; rcall.fix = &fx;
     }
-    prof_begin(h);
+    h->prof.begin();
     const int rc = launch_recv(h, rcall);
-    h->prof_slot = -1;
+    h->prof.end();
     return rc;
 }
 
@@ -1566,10 +1637,10 @@ int p25fe_shard_resolve_dev(p25fe_t* h, const p25fe_result_t* d_summaries, const
 int p25fe_shard_head_check(p25fe_t* h)
 {
     if (!h) return P25FE_ERR_ARG;
-    if (!h->sh_flag.p) return P25FE_OK;                              // no head segment has ever run on a stream of its own
+    if (!h->sh.flag.p) return P25FE_OK;                              // no head segment has ever run on a stream of its own
     HIPCHK(h, hipSetDevice(h->cfg.device));
     unsigned err = 0u;
-    HIPCHK(h, hipMemcpy(&err, h->sh_flag.as<unsigned>() + SH_FLAG_ERR, sizeof err, hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(&err, h->sh.flag.as<unsigned>() + SH_FLAG_ERR, sizeof err, hipMemcpyDeviceToHost));
     return err ? P25FE_ERR_TIMEOUT : P25FE_OK;
 }
 
@@ -1579,11 +1650,11 @@ int p25fe_streams_share_queue(p25fe_t* h, void* stream_a, void* stream_b, int* s
     *shared = 0;
     if (stream_a == stream_b) { *shared = 1; return P25FE_OK; }
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (!h->sh_flag.p) {
-        HIPCHK(h, h->sh_flag.ensure(SH_FLAG_WORDS * sizeof(unsigned)));
-        HIPCHK(h, hipMemset(h->sh_flag.p, 0, SH_FLAG_WORDS * sizeof(unsigned)));
+    if (!h->sh.flag.p) {
+        HIPCHK(h, h->sh.flag.ensure(SH_FLAG_WORDS * sizeof(unsigned)));
+        HIPCHK(h, hipMemset(h->sh.flag.p, 0, SH_FLAG_WORDS * sizeof(unsigned)));
     }
-    unsigned* w = h->sh_flag.as<unsigned>() + 2;                     // (words 0 / 1 are the head segment's flag and ticket)
+    unsigned* w = h->sh.flag.as<unsigned>() + 2;                     // (words 0 / 1 are the head segment's flag and ticket)
     HIPCHK(h, hipStreamSynchronize((hipStream_t)stream_a));
     HIPCHK(h, hipStreamSynchronize((hipStream_t)stream_b));
     int votes = 0;
@@ -1640,35 +1711,28 @@ int p25fe_shard_compact_from_dev(p25fe_t* h, const uint8_t* d_gathered, size_t c
 struct Staged { size_t stride, n_hist; char* host; const char* dev; };
 static int stage_iq(p25fe_t* h, const void* iq, int fmt, size_t n, Staged* s)
 {
-    if (h->fmt_locked >= 0 && h->fmt_locked != fmt && h->abs_iq > 0) return P25FE_ERR_FORMAT;
+    if (h->state.format_refused(fmt)) return P25FE_ERR_FORMAT;
     const size_t C = (size_t)h->C, eb = fmt_bytes(fmt);
     s->stride = SHARD_HALO + round_up(n, 8) + 8;                     // samples, multiple of 8: owned sample 0 stays 16-B aligned
     HIPCHK(h, h->hin.ensure(C * s->stride * eb));
     s->host = static_cast<char*>(h->hin.p);
     s->dev = static_cast<const char*>(h->hin.dp);
-    s->n_hist = h->abs_iq < SHARD_HALO ? (size_t)h->abs_iq : SHARD_HALO;
+    s->n_hist = h->state.n_hist();
     for (size_t c = 0; c < C; ++c) {
         char* row = s->host + c * s->stride * eb;
-        memcpy(row, h->hist_iq.data() + c * SHARD_HALO * 8, SHARD_HALO * eb);
+        memcpy(row, h->state.hist_iq.data() + c * SHARD_HALO * 8, SHARD_HALO * eb);
         if (n) memcpy(row + SHARD_HALO * eb, static_cast<const char*>(iq) + c * n * eb, n * eb);
     }
     return P25FE_OK;
 }
-// the call succeeded: the last SHARD_HALO samples of [history | new] become the history
-static void commit_iq(p25fe_t* h, int fmt, size_t n, const Staged& s)
-{
-    const size_t C = (size_t)h->C, eb = fmt_bytes(fmt);
-    for (size_t c = 0; c < C; ++c)
-        memcpy(h->hist_iq.data() + c * SHARD_HALO * 8, s.host + (c * s.stride + n) * eb, SHARD_HALO * eb);
-    h->fmt_locked = fmt;
-    h->abs_iq += n;
-}
+// the call succeeded: the stream moves on behind the staged samples
+static void commit_iq(p25fe_t* h, int fmt, size_t n, const Staged& s) { h->state.commit_iq((size_t)h->C, fmt, n, s.host + SHARD_HALO * fmt_bytes(fmt), s.stride * fmt_bytes(fmt)); }
 
 // K1 on the staged chunk, from the stream's position on
 static K1Launch staged_k1(const p25fe_t* h, int fmt, size_t n, const Staged& s)
 {
     K1Launch k;
-    k.src = s.dev + SHARD_HALO * fmt_bytes(fmt); k.fmt = fmt; k.ch_stride = s.stride; k.n_hist = s.n_hist; k.n = n; k.abs0 = h->abs_iq;
+    k.src = s.dev + SHARD_HALO * fmt_bytes(fmt); k.fmt = fmt; k.ch_stride = s.stride; k.n_hist = s.n_hist; k.n = n; k.abs0 = h->state.abs_iq;
     k.stream = h->stream;
     return k;
 }
@@ -1678,7 +1742,7 @@ static int demod_host(p25fe_t* h, const void* iq, int fmt, size_t n, float* bb, 
 {
     if (!h || (!iq && n) || !bb || !n_out) return P25FE_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    const size_t nb = p25fe_n_baseband_h(h, h->abs_iq, n);
+    const size_t nb = p25fe_n_baseband_h(h, h->state.abs_iq, n);
     if (nb > bb_cap) return P25FE_ERR_CAPACITY;
     const size_t C = (size_t)h->C;
     Staged sg;
@@ -1742,7 +1806,7 @@ static int recv_out(p25fe_t* h, size_t n_bb, size_t sync_cap, RecvOut* o)
     o->sdib = ar.take<uint64_t>(C * sync_cap, &o->d_sdib);
     o->tail = ar.take<float>(C * TAILN, &o->d_tail);
     o->done = ar.take<unsigned>(C, &o->d_done);
-    memcpy(o->anc, h->anchor.data(), sizeof(p25fe_anchor_t) * C);
+    memcpy(o->anc, h->state.anchor.data(), sizeof(p25fe_anchor_t) * C);
     return P25FE_OK;
 }
 // after the synchronisation: capacity check, copy-out, receiver state
@@ -1758,13 +1822,13 @@ static int recv_finish(p25fe_t* h, const RecvOut& o, size_t n_bb, uint8_t* dibit
         const size_t ns = r.n_sync < sync_cap ? (size_t)r.n_sync : sync_cap;
         if (ns && sync_pos) memcpy(sync_pos + c * sync_cap, o.spos + c * o.sstride, ns * sizeof(int64_t));
         if (sync_dibit)
-            for (size_t k = 0; k < ns; ++k) sync_dibit[c * sync_cap + k] = o.sdib[c * o.sstride + k] + h->total_dibits[c];
+            for (size_t k = 0; k < ns; ++k) sync_dibit[c * sync_cap + k] = o.sdib[c * o.sstride + k] + h->state.total_dibits[c];
         n_dibits[c] = (size_t)r.n_dibits;
         if (n_sync) n_sync[c] = (size_t)r.n_sync;
-        h->anchor[c] = r.anchor_out;
-        h->total_dibits[c] += r.n_dibits;
+        h->state.anchor[c] = r.anchor_out;
+        h->state.total_dibits[c] += r.n_dibits;
     }
-    h->abs_bb += n_bb;
+    h->state.abs_bb += n_bb;
     return P25FE_OK;
 }
 
@@ -1772,7 +1836,7 @@ static int recv_finish(p25fe_t* h, const RecvOut& o, size_t n_bb, uint8_t* dibit
 static RecvCall host_recv_call(const p25fe_t* h, const RecvOut& o, size_t n_bb, bool want_sync)
 {
     RecvCall c = recv_call(h);                                      // (a pending p25fe_resync_at_dev list belongs to this call: cleared once it has succeeded)
-    c.range.n_bb = n_bb; c.range.abs_bb0 = (long)h->abs_bb - h->look; c.range.anchor_in = o.d_anc;
+    c.range.n_bb = n_bb; c.range.abs_bb0 = (long)h->state.abs_bb - h->look; c.range.anchor_in = o.d_anc;
     c.dest.dibits = o.d_dib; c.dest.dibit_stride = o.dstride; c.dest.result = o.d_res;
     c.dest.sync_pos = want_sync ? o.d_spos : nullptr; c.dest.sync_dibit = want_sync ? o.d_sdib : nullptr; c.dest.sync_stride = o.sstride;
     c.stream = h->stream;
@@ -1825,7 +1889,7 @@ int p25fe_slice(p25fe_t* h, const float* bb, size_t n, uint8_t* dibits, size_t c
     const size_t C = (size_t)h->C;
     if (n == 0) { for (size_t c = 0; c < C; ++c) { n_dibits[c] = 0; if (n_sync) n_sync[c] = 0; } return P25FE_OK; }
     if (cap < n / SPS + 1) return P25FE_ERR_CAPACITY;               // worst case of an undisturbed lock, checked before any state moves
-    shard_invalidate(h);
+    h->sh.invalidate();
     if (int jrc = pipe_join(h, h->stream)) return jrc;
     // stage [tail | new] per channel
     const size_t bb_stride = round_up(BBPAD + n + 4, 4);
@@ -1833,7 +1897,7 @@ int p25fe_slice(p25fe_t* h, const float* bb, size_t n, uint8_t* dibits, size_t c
     float* hb = static_cast<float*>(h->hbb.p);
     const float* db = static_cast<const float*>(h->hbb.dp);
     for (size_t c = 0; c < C; ++c) {
-        memcpy(hb + c * bb_stride, h->tail_bb.data() + c * BBPAD, BBPAD * sizeof(float));
+        memcpy(hb + c * bb_stride, h->state.tail_bb.data() + c * BBPAD, BBPAD * sizeof(float));
         memcpy(hb + c * bb_stride + BBPAD, bb + c * n, n * sizeof(float));
     }
     RecvOut o;
@@ -1843,7 +1907,7 @@ int p25fe_slice(p25fe_t* h, const float* bb, size_t n, uint8_t* dibits, size_t c
     if (rc) return rc;
     ChunkRecvArgs polled;
     polled.done = nullptr; polled.seq = 0u;
-    const size_t hist = h->abs_bb < BBPAD ? (size_t)h->abs_bb : BBPAD;
+    const size_t hist = h->state.abs_bb < BBPAD ? (size_t)h->state.abs_bb : BBPAD;
     const RecvCall rcall = host_recv_call(h, o, n, sync_cap != 0);
     if (!rcall.gen && n <= (size_t)TS) {
         RecvChunkArgs a;
@@ -1852,7 +1916,7 @@ int p25fe_slice(p25fe_t* h, const float* bb, size_t n, uint8_t* dibits, size_t c
         polled = a.r;
         const PlanarGeo g(n);
         a.bb = db + BBPAD; a.bb_stride = (long)bb_stride; a.n_hist = (long)hist;
-        a.f = h->pl_f.as<float>(); a.bits = h->pl_bits.as<uint32_t>(); a.n_blocks = (long)g.n_blocks;
+        a.f = h->rx().pl_f.get(); a.bits = h->rx().pl_bits.get(); a.n_blocks = (long)g.n_blocks;
         hipLaunchKernelGGL(k_recv_chunk, dim3((unsigned)C), dim3(WV), 0, h->stream, a);
         HIPCHK(h, hipGetLastError());
     } else {
@@ -1866,7 +1930,7 @@ int p25fe_slice(p25fe_t* h, const float* bb, size_t n, uint8_t* dibits, size_t c
     if (rc) return rc;                                               // (P25FE_ERR_CAPACITY: nothing has moved, the lock-drop list included -- repeat the call)
     h->rs_n = 0;
     for (size_t c = 0; c < C; ++c)                                   // the tail: last BBPAD samples of [tail | new]
-        memcpy(h->tail_bb.data() + c * BBPAD, hb + c * bb_stride + n, BBPAD * sizeof(float));
+        memcpy(h->state.tail_bb.data() + c * BBPAD, hb + c * bb_stride + n, BBPAD * sizeof(float));
     return P25FE_OK;
 }
 
@@ -1875,9 +1939,9 @@ static int run_host(p25fe_t* h, const void* iq, int fmt, size_t n, uint8_t* dibi
     if (!h || (!iq && n) || !dibits || !n_dibits || piecewise_refused(h)) return P25FE_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const size_t C = (size_t)h->C;
-    const size_t nb = p25fe_n_baseband_h(h, h->abs_iq, n);
+    const size_t nb = p25fe_n_baseband_h(h, h->state.abs_iq, n);
     if (cap < nb / SPS + 1) return P25FE_ERR_CAPACITY;              // worst case of an undisturbed lock, checked before any state moves
-    shard_invalidate(h);
+    h->sh.invalidate();
     if (int jrc = pipe_join(h, h->stream)) return jrc;
     Staged sg;
     int rc = stage_iq(h, iq, fmt, n, &sg);
@@ -1915,17 +1979,7 @@ static int run_host(p25fe_t* h, const void* iq, int fmt, size_t n, uint8_t* dibi
     if (rc) return rc;
     h->rs_n = 0;                                                     // the lock-drop list is consumed by a call that succeeded
     commit_iq(h, fmt, n, sg);
-    // baseband tail for a later p25fe_slice on this handle: the newest TAILN samples, those older than what the planes hold
-    // (a very short chunk) come from the previous tail
-    for (size_t c = 0; c < C; ++c) {
-        float* t = h->tail_bb.data() + c * BBPAD;
-        float merged[BBPAD];
-        for (size_t j = 0; j < (size_t)BBPAD; ++j) {
-            const long m = (long)nb - (long)BBPAD + (long)j;        // index relative to this call's first baseband sample
-            merged[j] = m >= -(long)(HIST_BB + h->look) ? o.tail[c * TAILN + j] : t[j + nb];
-        }
-        memcpy(t, merged, sizeof merged);
-    }
+    for (size_t c = 0; c < C; ++c) h->state.merge_tail(c, nb, h->look, o.tail + c * TAILN);
     return P25FE_OK;
 }
 
@@ -1948,12 +2002,12 @@ int p25fe_run_host_windows(p25fe_t* h, const void* iq, int fmt, size_t n, size_t
 {
     if (!h || (!iq && n) || !dibits || !n_dibits || (fmt != P25FE_FMT_CF32 && fmt != P25FE_FMT_U8) || piecewise_refused(h)) return P25FE_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (h->fmt_locked >= 0 && h->fmt_locked != fmt && h->abs_iq > 0) return P25FE_ERR_FORMAT;
+    if (h->state.format_refused(fmt)) return P25FE_ERR_FORMAT;
     const size_t C = (size_t)h->C, eb = fmt_bytes(fmt);
     if (window == 0) window = (size_t)(64u << 20) / eb;
     window &= ~(size_t)7;                                           // every window's first sample stays 16-byte aligned
     if (window < 8192) window = 8192;
-    const size_t nb_total = p25fe_n_baseband_h(h, h->abs_iq, n);
+    const size_t nb_total = p25fe_n_baseband_h(h, h->state.abs_iq, n);
     if (cap < nb_total / SPS + 1) return P25FE_ERR_CAPACITY;        // worst case of an undisturbed lock, before any state moves
     if (stats) memset(stats, 0, sizeof *stats);
     for (size_t c = 0; c < C; ++c) n_dibits[c] = 0;
@@ -1963,16 +2017,12 @@ int p25fe_run_host_windows(p25fe_t* h, const void* iq, int fmt, size_t n, size_t
         if (stats) { stats->n_windows = 1; }
         return rc1;
     }
-    shard_invalidate(h);
+    h->sh.invalidate();
     if (int jrc = pipe_join(h, h->stream)) return jrc;
     const auto t_begin = std::chrono::steady_clock::now();
     constexpr int R = 4;
-    if (!h->win_cs) {
-        HIPCHK(h, hipStreamCreateWithFlags(&h->win_cs, hipStreamNonBlocking));
-        HIPCHK(h, hipStreamCreateWithFlags(&h->win_os, hipStreamNonBlocking));
-        for (auto& slot : h->win_ev) for (hipEvent_t& e : slot) HIPCHK(h, hipEventCreate(&e));
-    }
-    hipStream_t st = h->stream, cs = h->win_cs, os = h->win_os;
+    HIPCHK(h, h->win.ensure());
+    hipStream_t st = h->stream, cs = h->win.cs, os = h->win.os;
     // A remainder of fewer than 8 samples (it may not even yield a baseband sample) rides with the window in front of it -- every
     // window of the pipeline then produces baseband, and the tail handed to a later p25fe_slice is always the last window's.
     size_t n_win = (n + window - 1) / window;
@@ -1986,16 +2036,16 @@ int p25fe_run_host_windows(p25fe_t* h, const void* iq, int fmt, size_t n, size_t
     int rc = ensure_slice_scratch(h, nb_win);
     if (rc) return rc;
     for (int b = 0; b < 2; ++b) {
-        HIPCHK(h, h->win_buf[b].ensure(C * stride * eb));
-        HIPCHK(h, h->win_dib[b].ensure(C * dstride));
+        HIPCHK(h, h->win.buf[b].ensure(C * stride * eb));
+        HIPCHK(h, h->win.dib[b].ensure(C * dstride));
     }
-    HIPCHK(h, h->win_res.ensure((size_t)R * C * sizeof(p25fe_result_t)));
-    HIPCHK(h, h->win_anc.ensure(2 * C * sizeof(p25fe_anchor_t)));
+    HIPCHK(h, h->win.res.ensure((size_t)R * C * sizeof(p25fe_result_t)));
+    HIPCHK(h, h->win.anc.ensure(2 * C * sizeof(p25fe_anchor_t)));
     // pinned: per ring slot the result records, per parity a dibit row block, the baseband tail, the carry-in anchors, the history
     const size_t out_bytes = (size_t)R * round_up(C * sizeof(p25fe_result_t), 64) + 2 * round_up(C * dstride, 64) +
                              round_up(C * TAILN * sizeof(float), 64) + round_up(C * sizeof(p25fe_anchor_t), 64) + round_up(C * SHARD_HALO * eb, 64);
-    HIPCHK(h, h->win_out.ensure(out_bytes));
-    Arena ar(h->win_out);
+    HIPCHK(h, h->win.out.ensure(out_bytes));
+    Arena ar(h->win.out);
     p25fe_result_t *h_res[R], *dv_unused_r;
     for (int q = 0; q < R; ++q) h_res[q] = ar.take<p25fe_result_t>(C, &dv_unused_r);
     uint8_t *h_dib[2], *dv_unused_b;
@@ -2011,17 +2061,17 @@ int p25fe_run_host_windows(p25fe_t* h, const void* iq, int fmt, size_t n, size_t
         else (void)hipGetLastError();
     }
     if (!pinned)
-        for (int b = 0; b < 2; ++b) HIPCHK(h, h->win_stage[b].ensure(C * (SHARD_HALO + window + 8) * eb));
-    memcpy(h_anc, h->anchor.data(), C * sizeof(p25fe_anchor_t));
-    for (size_t c = 0; c < C; ++c) memcpy(h_hist + c * SHARD_HALO * eb, h->hist_iq.data() + c * SHARD_HALO * 8, SHARD_HALO * eb);
-    p25fe_anchor_t* d_anc = h->win_anc.as<p25fe_anchor_t>();        // [2][C]: the carry-in of window k lives in half k & 1
+        for (int b = 0; b < 2; ++b) HIPCHK(h, h->win.stage[b].ensure(C * (SHARD_HALO + window + 8) * eb));
+    memcpy(h_anc, h->state.anchor.data(), C * sizeof(p25fe_anchor_t));
+    for (size_t c = 0; c < C; ++c) memcpy(h_hist + c * SHARD_HALO * eb, h->state.hist_iq.data() + c * SHARD_HALO * 8, SHARD_HALO * eb);
+    p25fe_anchor_t* d_anc = h->win.anc.as<p25fe_anchor_t>();        // [2][C]: the carry-in of window k lives in half k & 1
     RecvCall rcall = recv_call(h);                                   // (a pending lock-drop list holds absolute indices: every window sees it)
     rcall.dest.dibit_stride = dstride; rcall.stream = st;
     std::vector<uint64_t> total(C, 0);
     double ms_h2d = 0.0, ms_comp = 0.0;
     int status = P25FE_OK;
     auto drain = [&](size_t j) -> int {                              // window j's dibits are on the host: append them
-        hipEvent_t* ev = h->win_ev[j % R];
+        hipEvent_t* ev = h->win.ev[j % R];
         HIPCHK(h, hipEventSynchronize(ev[4]));
         float t = 0.f;
         if (hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) ms_h2d += t; else (void)hipGetLastError();
@@ -2040,22 +2090,22 @@ int p25fe_run_host_windows(p25fe_t* h, const void* iq, int fmt, size_t n, size_t
 #define WINCHK(expr) if (const hipError_t e__ = (expr); e__ != hipSuccess) { h->last_hip = (int)e__; status = P25FE_ERR_HIP; break; } else (void)0
     for (size_t k = 0; k < n_win && status == P25FE_OK; ++k) {
         const size_t off = k * window, wn = k + 1 == n_win ? n - off : window;
-        const uint64_t abs0 = h->abs_iq + off;
-        const size_t n_hist = k == 0 ? (h->abs_iq < SHARD_HALO ? (size_t)h->abs_iq : SHARD_HALO) : SHARD_HALO;
+        const uint64_t abs0 = h->state.abs_iq + off;
+        const size_t n_hist = k == 0 ? h->state.n_hist() : SHARD_HALO;
         const int b = (int)(k & 1);
-        hipEvent_t* ev = h->win_ev[k % R];
-        char* dev = h->win_buf[b].as<char>();
+        hipEvent_t* ev = h->win.ev[k % R];
+        char* dev = h->win.buf[b].as<char>();
         // ---- copy stream: [halo | window] in ONE copy.  The halo of window k >= 1 is simply the SHARD_HALO samples in front of
         // it in the caller's capture (16 KB more per window); only window 0 takes it from the handle's history.  (A device-to-
         // device copy of the previous window's tail put a second operation between every two H2D copies: 7 - 9 % of the call.)
-        if (k >= 2) { WINCHK(hipStreamWaitEvent(cs, h->win_ev[(k - 2) % R][3], 0)); }      // the kernels of window k - 2 have read this buffer
+        if (k >= 2) { WINCHK(hipStreamWaitEvent(cs, h->win.ev[(k - 2) % R][3], 0)); }      // the kernels of window k - 2 have read this buffer
         const size_t lead = k == 0 ? 0 : SHARD_HALO;                // samples in front of the window that travel with it
         if (k == 0) { WINCHK(hipMemcpy2DAsync(dev, stride * eb, h_hist, SHARD_HALO * eb, SHARD_HALO * eb, C, hipMemcpyHostToDevice, cs)); }
         const char* src = static_cast<const char*>(iq) + (off - lead) * eb;
         size_t spitch = n * eb;
         if (!pinned) {
-            if (k >= 2) { WINCHK(hipEventSynchronize(h->win_ev[(k - 2) % R][1])); }       // the copy engine is done with this staging window
-            char* sg = static_cast<char*>(h->win_stage[b].p);
+            if (k >= 2) { WINCHK(hipEventSynchronize(h->win.ev[(k - 2) % R][1])); }       // the copy engine is done with this staging window
+            char* sg = static_cast<char*>(h->win.stage[b].p);
             for (size_t c = 0; c < C; ++c) memcpy(sg + c * (lead + wn) * eb, src + c * n * eb, (lead + wn) * eb);
             src = sg; spitch = (lead + wn) * eb;
         }
@@ -2066,16 +2116,16 @@ int p25fe_run_host_windows(p25fe_t* h, const void* iq, int fmt, size_t n, size_t
         WINCHK(hipEventRecord(ev[1], cs));
         // ---- compute stream
         WINCHK(hipStreamWaitEvent(st, ev[1], 0));
-        if (k >= 2) { WINCHK(hipStreamWaitEvent(st, h->win_ev[(k - 2) % R][4], 0)); }      // window k - 2's dibit rows have left this device row block
+        if (k >= 2) { WINCHK(hipStreamWaitEvent(st, h->win.ev[(k - 2) % R][4], 0)); }      // window k - 2's dibit rows have left this device row block
         if (k == 0) { WINCHK(hipMemcpyAsync(d_anc, h_anc, C * sizeof(p25fe_anchor_t), hipMemcpyHostToDevice, st)); }
         WINCHK(hipEventRecord(ev[2], st));
         const size_t nb = p25fe_n_baseband_h(h, abs0, wn);
-        p25fe_result_t* d_res = h->win_res.as<p25fe_result_t>() + (k % R) * C;
-        uint8_t* d_dib = h->win_dib[b].as<uint8_t>();
+        p25fe_result_t* d_res = h->win.res.as<p25fe_result_t>() + (k % R) * C;
+        uint8_t* d_dib = h->win.dib[b].as<uint8_t>();
         const PlanarGeo g(nb ? nb : 1);
         K1Launch k1;
         k1.src = dev + SHARD_HALO * eb; k1.fmt = fmt; k1.ch_stride = stride; k1.n_hist = n_hist; k1.n = wn; k1.abs0 = abs0; k1.stream = st;
-        rcall.range.n_bb = nb; rcall.range.abs_bb0 = (long)(h->abs_bb + nb_done) - h->look; rcall.range.anchor_in = d_anc + (size_t)b * C;
+        rcall.range.n_bb = nb; rcall.range.abs_bb0 = (long)(h->state.abs_bb + nb_done) - h->look; rcall.range.anchor_in = d_anc + (size_t)b * C;
         rcall.dest.dibits = d_dib; rcall.dest.result = d_res;
         rc = launch_planar_recv(h, k1, rcall);
         if (rc) { status = rc; break; }
@@ -2109,29 +2159,15 @@ int p25fe_run_host_windows(p25fe_t* h, const void* iq, int fmt, size_t n, size_t
     h->rs_n = 0;                                                     // a pending lock-drop list is consumed by a call that succeeded
     // ---- the handle's stream state after the capture
     const p25fe_result_t* last = h_res[(n_win - 1) % R];
+    const size_t nb_last = p25fe_n_baseband_h(h, h->state.abs_iq + (n_win - 1) * window, n - (n_win - 1) * window);   // (> 0: a window is at least 8 192 samples)
     for (size_t c = 0; c < C; ++c) {
         n_dibits[c] = (size_t)total[c];
-        h->anchor[c] = last[c].anchor_out;
-        h->total_dibits[c] += total[c];
-        // the last SHARD_HALO samples of [old history | capture]
-        char* hist = h->hist_iq.data() + c * SHARD_HALO * 8;
-        const char* srcc = static_cast<const char*>(iq) + c * n * eb;
-        if (n >= SHARD_HALO) memcpy(hist, srcc + (n - SHARD_HALO) * eb, SHARD_HALO * eb);
-        else { memmove(hist, hist + n * eb, (SHARD_HALO - n) * eb); memcpy(hist + (SHARD_HALO - n) * eb, srcc, n * eb); }
-        const size_t nb_last = p25fe_n_baseband_h(h, h->abs_iq + (n_win - 1) * window, n - (n_win - 1) * window);   // (> 0: a window is at least 8 192 samples)
-        float* t = h->tail_bb.data() + c * BBPAD;
-        if (nb_last) {
-            float merged[BBPAD];
-            for (size_t j = 0; j < (size_t)BBPAD; ++j) {
-                const long m = (long)nb_last - (long)BBPAD + (long)j;
-                merged[j] = m >= -(long)(HIST_BB + h->look) ? h_tail[c * TAILN + j] : (j + nb_last < (size_t)BBPAD ? t[j + nb_last] : 0.0f);
-            }
-            memcpy(t, merged, sizeof merged);
-        }
+        h->state.anchor[c] = last[c].anchor_out;
+        h->state.total_dibits[c] += total[c];
+        if (nb_last) h->state.merge_tail(c, nb_last, h->look, h_tail + c * TAILN);
     }
-    h->fmt_locked = fmt;
-    h->abs_iq += n;
-    h->abs_bb += nb_done;
+    h->state.commit_iq(C, fmt, n, static_cast<const char*>(iq), n * eb);
+    h->state.abs_bb += nb_done;
     if (stats) {
         stats->n_windows = n_win;
         stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
@@ -2177,7 +2213,6 @@ int p25fe_nid(p25fe_t* h, const uint8_t* dibits, size_t n_dibits, const uint64_t
         if (rc == P25FE_OK) e = hipMemcpyAsync(out, d_out.p, n_sync * sizeof(p25fe_nid_t), hipMemcpyDeviceToHost, h->stream);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    d_dib.release(); d_sd.release(); d_sp.release(); d_out.release();
     if (e != hipSuccess) { h->last_hip = (int)e; return P25FE_ERR_HIP; }
     return rc;
 }
@@ -2212,28 +2247,28 @@ int p25fe_profile_enable(p25fe_t* h, int on)
 {
     if (!h) return P25FE_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (on && h->prof_ev.empty()) {
+    if (on && h->prof.ev.empty()) {
         try {
-            h->prof_ev.assign((size_t)PROF_RING * 5, nullptr);
-            h->prof_mask.assign((size_t)PROF_RING, 0);
+            h->prof.ev.assign((size_t)PROF_RING * 5, nullptr);
+            h->prof.mask.assign((size_t)PROF_RING, 0);
         } catch (...) {
-            h->prof_ev.clear();
+            h->prof.ev.clear();
             return P25FE_ERR_NOMEM;
         }
-        for (auto& e : h->prof_ev) {
+        for (auto& e : h->prof.ev) {
             const hipError_t er = hipEventCreate(&e);
             if (er != hipSuccess) {                                 // all or nothing: a half-made ring is never indexed
-                for (auto& d : h->prof_ev) if (d) (void)hipEventDestroy(d);
-                h->prof_ev.clear();
+                for (auto& d : h->prof.ev) if (d) (void)hipEventDestroy(d);
+                h->prof.ev.clear();
                 h->last_hip = (int)er;
                 return P25FE_ERR_HIP;
             }
         }
     }
-    h->prof_on = on != 0;
-    h->prof_level = on == 2 ? 2 : (on == 3 ? 3 : 1);
-    h->prof_calls = 0;
-    h->prof_seq = 0;
+    h->prof.on = on != 0;
+    h->prof.level = on == 2 ? 2 : (on == 3 ? 3 : 1);
+    h->prof.calls = 0;
+    h->prof.seq = 0;
     return P25FE_OK;
 }
 
@@ -2241,18 +2276,18 @@ int p25fe_profile_read(p25fe_t* h, double ms[4], uint64_t* n_calls)
 {
     if (!h || !ms) return P25FE_ERR_ARG;
     for (int k = 0; k < 4; ++k) ms[k] = 0.0;
-    const uint64_t calls = h->prof_calls;
+    const uint64_t calls = h->prof.calls;
     const uint64_t kept = calls < (uint64_t)PROF_RING ? calls : (uint64_t)PROF_RING;
     uint64_t n_k1 = 0;
     for (uint64_t s = 0; s < kept; ++s) {
-        const unsigned m = h->prof_mask[s];                          // a slot holds the events its call recorded: all five
+        const unsigned m = h->prof.mask[s];                          // a slot holds the events its call recorded: all five
         if ((m & 3u) == 3u) ++n_k1;
         for (int k = 4; k >= 0; --k)                                 // (run_dev, shard pass 1) or 2..4 (shard pass 2)
-            if (m & (1u << k)) { HIPCHK(h, hipEventSynchronize(h->prof_ev[s * 5 + k])); break; }
+            if (m & (1u << k)) { HIPCHK(h, hipEventSynchronize(h->prof.ev[s * 5 + k])); break; }
         for (int k = 0; k < 4; ++k) {
             if ((m & (3u << k)) != (3u << k)) continue;
             float t = 0.f;
-            if (hipEventElapsedTime(&t, h->prof_ev[s * 5 + k], h->prof_ev[s * 5 + k + 1]) != hipSuccess) {
+            if (hipEventElapsedTime(&t, h->prof.ev[s * 5 + k], h->prof.ev[s * 5 + k + 1]) != hipSuccess) {
                 (void)hipGetLastError();                             // a slot whose launch had nothing to do (empty part of a shard)
                 if (k == 0 && n_k1) --n_k1;
                 continue;
@@ -2261,14 +2296,14 @@ int p25fe_profile_read(p25fe_t* h, double ms[4], uint64_t* n_calls)
         }
     }
     if (n_calls) *n_calls = n_k1;          // calls that ran K1 (a shard's pass 2 has a slot of its own without one)
-    h->prof_calls = 0;
+    h->prof.calls = 0;
     return P25FE_OK;
 }
 
 int p25fe_resync(p25fe_t* h)
 {
     if (!h) return P25FE_ERR_ARG;
-    for (auto& a : h->anchor) a.valid = 0;      // lock and, with it, the clock estimate (the next sync word starts from 10 / 1)
+    for (auto& a : h->state.anchor) a.valid = 0;      // lock and, with it, the clock estimate (the next sync word starts from 10 / 1)
     return P25FE_OK;
 }
 
@@ -2277,25 +2312,17 @@ int p25fe_resync_at_dev(p25fe_t* h, const int64_t* d_idx, size_t n_idx, size_t i
     if (!h || (n_idx && !d_idx) || n_idx > 0x7fffffffu || (h->C > 1 && n_idx && idx_stride < n_idx)) return P25FE_ERR_ARG;
     static_assert(sizeof(long) == sizeof(int64_t), "LP64");
     h->rs_idx = reinterpret_cast<const long*>(d_idx);
-    h->rs_n = n_idx;
-    h->rs_stride = idx_stride;
+    h->rs_n = n_idx; h->rs_stride = idx_stride;
     return P25FE_OK;
 }
 
 // --------------------------------------------------------------------------------------------
-// state blob: header | IQ history raw | baseband tail | anchors | totals
+// state blob (StreamState::write / read)
 // --------------------------------------------------------------------------------------------
-struct StateHeader {
-    uint32_t magic, abi;
-    int32_t n_channels, fmt_locked;
-    uint64_t abs_iq, abs_bb;
-};
-
 int p25fe_state_size(const p25fe_t* h, size_t* n)
 {
     if (!h || !n) return P25FE_ERR_ARG;
-    const size_t C = (size_t)h->C;
-    *n = sizeof(StateHeader) + C * SHARD_HALO * 8 + C * BBPAD * sizeof(float) + C * sizeof(p25fe_anchor_t) + C * sizeof(uint64_t);
+    *n = const_cast<p25fe_t*>(h)->state.blob_size();
     return P25FE_OK;
 }
 
@@ -2306,14 +2333,7 @@ int p25fe_state_export(const p25fe_t* hc, void* buf, size_t cap, size_t* n)
     if (!h || !buf || p25fe_state_size(h, &need)) return P25FE_ERR_ARG;
     if (n) *n = need;
     if (cap < need) return P25FE_ERR_CAPACITY;
-    const size_t C = (size_t)h->C;
-    char* p = static_cast<char*>(buf);
-    StateHeader hd = {STATE_MAGIC, P25FE_ABI_VERSION, h->C, h->fmt_locked, h->abs_iq, h->abs_bb};
-    memcpy(p, &hd, sizeof hd); p += sizeof hd;
-    memcpy(p, h->hist_iq.data(), C * SHARD_HALO * 8); p += C * SHARD_HALO * 8;       // the streaming state is host-side
-    memcpy(p, h->tail_bb.data(), C * BBPAD * sizeof(float)); p += C * BBPAD * sizeof(float);
-    memcpy(p, h->anchor.data(), C * sizeof(p25fe_anchor_t)); p += C * sizeof(p25fe_anchor_t);
-    memcpy(p, h->total_dibits.data(), C * sizeof(uint64_t));
+    h->state.write(static_cast<char*>(buf));
     return P25FE_OK;
 }
 
@@ -2321,27 +2341,7 @@ int p25fe_state_import(p25fe_t* h, const void* buf, size_t n)
 {
     size_t need = 0;
     if (!h || !buf || p25fe_state_size(h, &need) || n < need) return P25FE_ERR_ARG;
-    const char* p = static_cast<const char*>(buf);
-    StateHeader hd;
-    memcpy(&hd, p, sizeof hd); p += sizeof hd;
-    if (hd.magic != STATE_MAGIC || hd.abi != P25FE_ABI_VERSION || hd.n_channels != h->C) return P25FE_ERR_ARG;
-    if (hd.fmt_locked != -1 && hd.fmt_locked != P25FE_FMT_U8 && hd.fmt_locked != P25FE_FMT_CF32) return P25FE_ERR_ARG;
-    const size_t C = (size_t)h->C;
-    {   // a blob is data from outside: every anchor's clock must be a usable period before anything is taken over
-        const char* pa = p + C * SHARD_HALO * 8 + C * BBPAD * sizeof(float);
-        for (size_t c = 0; c < C; ++c) {
-            p25fe_anchor_t a;
-            memcpy(&a, pa + c * sizeof a, sizeof a);
-            // (0 / 0 reads as 10 / 1: include/p25fe.h)
-            if (!(a.period_d == 0 && a.period_n == 0) && !clock_plausible(a.period_d, a.period_n)) return P25FE_ERR_ARG;
-            if (!h->track && a.valid != 0 && !(a.period_d == 0 && a.period_n == 0) && !(a.period_d == SPS && a.period_n == 1)) return P25FE_ERR_ARG;
-        }
-    }
-    memcpy(h->hist_iq.data(), p, C * SHARD_HALO * 8); p += C * SHARD_HALO * 8;
-    memcpy(h->tail_bb.data(), p, C * BBPAD * sizeof(float)); p += C * BBPAD * sizeof(float);
-    memcpy(h->anchor.data(), p, C * sizeof(p25fe_anchor_t)); p += C * sizeof(p25fe_anchor_t);
-    memcpy(h->total_dibits.data(), p, C * sizeof(uint64_t));
-    h->fmt_locked = hd.fmt_locked; h->abs_iq = hd.abs_iq; h->abs_bb = hd.abs_bb;
+    if (!h->state.read(static_cast<const char*>(buf), h->track)) return P25FE_ERR_ARG;
     h->rs_idx = nullptr; h->rs_n = 0; h->rs_stride = 0;             // (absolute indices of another stream position)
     return P25FE_OK;
 }
