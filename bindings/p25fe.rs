@@ -16,6 +16,8 @@
 use std::os::raw::{c_char, c_int, c_void};
 
 pub const ABI_VERSION: i32 = 6;
+/// P25FE_MAX_POSITION: an abs0 / abs_bb0 (or a state blob's counter) from here on is P25FE_ERR_ARG
+pub const MAX_POSITION: u64 = 1 << 62;
 pub const MAX_TAPS: usize = 64;
 pub const FMT_CF32: c_int = 0;
 pub const FMT_U8: c_int = 1;

@@ -304,7 +304,22 @@ int p25fe_state_import(p25fe_t *h, const void *buf, size_t n);
  * channel's first owned sample in memory (0 at the start of a stream: history reads as zero,
  * exactly like the zero-initialised filters of DemodTask::new); abs0 is the absolute index of
  * the first owned sample in its stream (fixes the 5:1 grid, src/demod.rs:87-90).
- * All outputs are device pointers; nothing is synchronised. */
+ * All outputs are device pointers; nothing is synchronised.
+ * POSITIONS are 64-bit sample counts: a stream that runs for days passes 2^31 and 2^32 (the IQ
+ * index after 4 h 58 min at 240 ksps) and nothing changes there -- a range at position P computes
+ * what the same samples compute at any P' congruent to P modulo the stage's grid (5; 10 for the
+ * pre-decimator; 10 and 192 for the channeliser; the receiver has none), with every index that
+ * comes back shifted by the difference (docs/SPEC.md section 4).
+ * The one bound is P25FE_MAX_POSITION = 2^62: the kernels keep signed 64-bit indices and add a
+ * range's length on top.  What the host can see is checked and answers P25FE_ERR_ARG at 2^62 or
+ * more: abs0 (p25fe_demod_dev, p25fe_predecim_dev, p25fe_channelise_dev, the p25fe_shard_pass1
+ * forms), abs_bb0 (p25fe_slice_dev), shard_bb0[r] and shard_bb0[r] + shard_bb_n[r] of
+ * p25fe_shard_resolve, and in a blob given to p25fe_state_import the two counters and the `s` of
+ * every valid anchor.  Positions the library only ever sees in DEVICE memory are the caller's to
+ * keep below the bound and are not checked: p25fe_resync_at_dev indices (INT64_MAX is padding, no
+ * position), d_anchor_in, and the d_shard_bb0 of p25fe_shard_resolve_dev / p25fe_shard_pass2_dev.
+ * The count functions (p25fe_n_baseband, _h, p25fe_n_predecim) are exact for every uint64_t. */
+#define P25FE_MAX_POSITION ((uint64_t)1 << 62)
 
 /* stages 1-5: writes n_baseband(n, abs0) samples per channel to d_bb (+ c * bb_stride). */
 int p25fe_demod_dev(p25fe_t *h, const void *d_iq, int fmt, size_t ch_stride, size_t n_hist, size_t n,

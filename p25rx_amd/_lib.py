@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(HERE, "libp25fe.so")
 MAX_TAPS = 64
 ABI_VERSION = 6
 FMT_CF32, FMT_U8 = 0, 1
+MAX_POSITION = 1 << 62                   # P25FE_MAX_POSITION: abs0 / abs_bb0 from here on are P25FE_ERR_ARG
 
 OK, ERR_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_CAPACITY, ERR_FORMAT, ERR_NOMEM, ERR_JIT, ERR_TIMEOUT = 0, -1, -2, -3, -4, -5, -6, -7, -8
 CLOCK_FIXED, CLOCK_TRACKING, CLOCK_TRACKING_RESLICE, CLOCK_CAUSAL_OK = 0, 1, 2, 0x100

@@ -240,6 +240,7 @@ struct StreamState {
         memcpy(&hd, p, sizeof hd); p += sizeof hd;
         if (hd.magic != STATE_MAGIC || hd.abi != P25FE_ABI_VERSION || hd.n_channels != (int32_t)anchor.size()) return false;
         if (hd.fmt_locked != -1 && hd.fmt_locked != P25FE_FMT_U8 && hd.fmt_locked != P25FE_FMT_CF32) return false;
+        if (hd.abs_iq >= P25FE_MAX_POSITION || hd.abs_bb >= P25FE_MAX_POSITION) return false;
         Sec s[4]; sections(s);
         // a blob is data from outside: every anchor's clock must be a usable period before anything is taken over
         for (size_t c = 0; c < anchor.size(); ++c) {
@@ -248,6 +249,7 @@ struct StreamState {
             // (0 / 0 reads as 10 / 1: include/p25fe.h)
             if (!(a.period_d == 0 && a.period_n == 0) && !clock_plausible(a.period_d, a.period_n)) return false;
             if (!track && a.valid != 0 && !(a.period_d == 0 && a.period_n == 0) && !(a.period_d == SPS && a.period_n == 1)) return false;
+            if (a.valid != 0 && (a.s >= (int64_t)P25FE_MAX_POSITION || a.s <= -(int64_t)P25FE_MAX_POSITION)) return false;
         }
         for (int k = 0; k < 4; ++k) { memcpy(s[k].p, p, s[k].bytes); p += s[k].bytes; }
         fmt_locked = hd.fmt_locked; abs_iq = hd.abs_iq; abs_bb = hd.abs_bb;
@@ -368,6 +370,9 @@ struct PlanarGeo {
 // Symbol indices are 32-bit in the receive kernels: a range holds < 2^31 symbols (124 h of one channel).  Checked by every
 // entry point BEFORE it sizes scratch for the range, so that an absurd length is an argument error, not an allocation failure.
 constexpr size_t MAX_RANGE_BB = (size_t)0x7ff00000u * 10u;
+// Positions (abs0, abs_bb0, the counters of a state blob) are 64-bit sample counts kept as signed 64-bit indices inside the kernels,
+// with a range's length, the lookahead and the history added on top: P25FE_MAX_POSITION (include/p25fe.h) leaves that headroom.
+static inline bool position_refused(uint64_t pos) { return pos >= P25FE_MAX_POSITION; }
 
 // --------------------------------------------------------------------------------------------
 // p25fe_config_t -> the numbers the kernels run with.  No device needed (p25fe_specialize runs on a build host).
@@ -1216,7 +1221,7 @@ extern "C" {
 int p25fe_demod_dev(p25fe_t* h, const void* d_iq, int fmt, size_t ch_stride, size_t n_hist, size_t n, uint64_t abs0,
                     float* d_bb, size_t bb_stride, float* d_power_dbm, void* stream)
 {
-    if (!h || !d_iq || !d_bb) return P25FE_ERR_ARG;
+    if (!h || !d_iq || !d_bb || position_refused(abs0)) return P25FE_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     K1Launch k;
     k.src = d_iq; k.fmt = fmt; k.ch_stride = ch_stride; k.n_hist = n_hist; k.n = n; k.abs0 = abs0;
@@ -1233,7 +1238,7 @@ size_t p25fe_n_predecim(uint64_t abs0, size_t n)
 int p25fe_predecim_dev(p25fe_t* h, const float* d_iq, size_t ch_stride, size_t n_hist, size_t n, uint64_t abs0,
                        float* d_out, size_t out_stride, void* stream)
 {
-    if (!h || !d_iq || !d_out) return P25FE_ERR_ARG;
+    if (!h || !d_iq || !d_out || position_refused(abs0)) return P25FE_ERR_ARG;
     if ((reinterpret_cast<uintptr_t>(d_iq) & 15u) != 0 || (h->C > 1 && (ch_stride & 1))) return P25FE_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const size_t n_out = p25fe_n_predecim(abs0, n);
@@ -1253,7 +1258,7 @@ int p25fe_channelise_dev(p25fe_t* h, const float* d_iq, size_t n_hist, size_t n,
                          size_t out_stride, void* stream)
 {
     static_assert(P25FE_CHZ_CHANNELS_ABI == CZ_M, "header and spec disagree");
-    if (!h || !d_iq || !d_out) return P25FE_ERR_ARG;
+    if (!h || !d_iq || !d_out || position_refused(abs0)) return P25FE_ERR_ARG;
     if ((reinterpret_cast<uintptr_t>(d_iq) & 15u) != 0 || (reinterpret_cast<uintptr_t>(d_out) & 7u) != 0) return P25FE_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const size_t n_out = p25fe_n_predecim(abs0, n);
@@ -1286,7 +1291,7 @@ int p25fe_slice_dev(p25fe_t* h, const float* d_bb, size_t bb_stride, size_t n_hi
                     const p25fe_anchor_t* d_anchor_in, uint8_t* d_dibits, size_t dibit_stride, int64_t* d_sync_pos,
                     uint64_t* d_sync_dibit, size_t sync_stride, p25fe_result_t* d_result, void* stream)
 {
-    if (!h || !d_bb || !d_dibits || !d_result) return P25FE_ERR_ARG;
+    if (!h || !d_bb || !d_dibits || !d_result || position_refused(abs_bb0)) return P25FE_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (n_bb > MAX_RANGE_BB) return P25FE_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -1423,7 +1428,7 @@ static int shard_pass1_part(p25fe_t* h, const void* d_iq, int fmt, size_t ch_str
 {
     const bool do_main = (what & SH_MAIN) != 0, do_finish = (what & SH_RECV) != 0;
     bool do_head = (what & SH_HEAD) != 0;
-    if (!h || !d_iq || (do_finish && !d_result) || p25fe_n_baseband_h(h, abs0, n) > MAX_RANGE_BB || piecewise_refused(h)) return P25FE_ERR_ARG;
+    if (!h || !d_iq || (do_finish && !d_result) || position_refused(abs0) || p25fe_n_baseband_h(h, abs0, n) > MAX_RANGE_BB || piecewise_refused(h)) return P25FE_ERR_ARG;
     if (do_main) h->sh.invalidate();
     if (n_hist < SHARD_HALO && n_hist != abs0) return P25FE_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -1618,6 +1623,8 @@ int p25fe_shard_resolve(const p25fe_result_t* summaries, const uint64_t* shard_b
                         size_t n_shards, int symbol_clock, p25fe_anchor_t* anchor_in, uint64_t* dibit_offset)
 {
     if (!summaries || !shard_bb0 || !shard_bb_n || !anchor_in || !dibit_offset || n_shards > 0x7fffffffu) return P25FE_ERR_ARG;
+    for (size_t r = 0; r < n_shards; ++r)
+        if (position_refused(shard_bb0[r]) || position_refused(shard_bb_n[r]) || position_refused(shard_bb0[r] + shard_bb_n[r])) return P25FE_ERR_ARG;
     shard_resolve_impl(summaries, shard_bb0, shard_bb_n, (int)n_shards, symbol_clock, anchor_in, dibit_offset);
     return P25FE_OK;
 }

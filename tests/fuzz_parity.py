@@ -11,7 +11,8 @@ random indices (device lists per channel, and MessageReceiver::resync between ch
 entry points with the handle's state exported and imported at a random boundary.  Compared bit for bit: baseband (linear,
 device and host forms; power within 1e-3 dB), dibits, sync positions, sync dibit indices -- for the device-resident forms
 (demod_dev, slice_dev, run_dev, run_dev_pipelined), the streaming forms (demod_*, slice, run_*) under that chunking, and
-time shards at random cut points (one- and two-launch pass 1, lock drops, host and device resolve).  Any difference
+time shards at random cut points (one- and two-launch pass 1, lock drops, host and device resolve), and slice_dev and the shards
+once more at a random stream position past 2^31 / 2^32 / 2^40 / 2^56.  Any difference
 prints the scene's seed and stops with exit code 1; `tests/test_gpu_fuzz.py` runs a few fixed seeds under pytest."""
 import argparse
 import os
@@ -176,9 +177,10 @@ def run_scene(seed, O, FE, torch, verbose=False):
     res_ref = ref if s["clock"] != 2 else [tuple(x.astype(np.uint64) if k == 2 else x for k, x in enumerate(O.recv_range(ref_bb[c], cfg, drops[c])))
                                            for c in range(Cn)]
 
-    def set_drops(fe, lo=None, hi=None, skip=()):
-        """the drops inside [lo, hi) (all of them: None) as a device list [C, n], short rows padded with INT64_MAX"""
-        mine = [[q for q in drops[c] if (lo is None or lo <= q < hi) and q not in skip] for c in range(Cn)]
+    def set_drops(fe, lo=None, hi=None, skip=(), shift=0):
+        """the drops inside [lo, hi) (all of them: None) as a device list [C, n], short rows padded with INT64_MAX; shift: the
+        absolute index of the scene's baseband sample 0"""
+        mine = [[q + shift for q in drops[c] if (lo is None or lo <= q < hi) and q not in skip] for c in range(Cn)]
         k = max(len(x) for x in mine)
         if k:
             arr = np.full((Cn, k), np.iinfo(np.int64).max, dtype=np.int64)
@@ -286,6 +288,7 @@ def run_scene(seed, O, FE, torch, verbose=False):
 
     # ---- time shards at random (8-aligned) cut points: one channel, every shard handed the whole drop list, the two-launch
     # form on odd shards, host and device resolve
+    cuts = None
     if n_iq >= 64 and Cn == 1:
         k = int(rng.integers(2, 6))
         cuts = sorted(set([0, n_iq] + [int(x) // 8 * 8 for x in rng.integers(8, n_iq, size=k - 1)]))
@@ -324,6 +327,68 @@ def run_scene(seed, O, FE, torch, verbose=False):
                            "first_diff": [int(x) for x in np.nonzero(got_all[:m] != ref[0][0][:m])[0][:4]], "drops": drops[0],
                            "syncs": [int(x) for x in ref[0][1][:12]], "sync_dibit": [int(x) for x in ref[0][2][:12]]}
         check("time shards", np.array_equal(got_all, ref[0][0]))
+
+    # ---- the same scene at a stream position past 2^31 / 2^32 / 2^40 / 2^56 (docs/SPEC.md section 4: every stage is shift-invariant up
+    # to its grid residue): the scene's baseband sample 0 sits at `base`, with the power of two -- or the baseband sample the IQ
+    # index 2^32 makes -- anywhere inside the range or on its edges.  Drawn after everything else: earlier seeds keep their scenes.
+    two = int(rng.choice([31, 32, 32, 40, 56]))
+    edge = (1 << two) // 5 if (two == 32 and int(rng.integers(0, 2))) else 1 << two
+    base = edge - int(rng.integers(0, nb + 1))
+    set_drops(fe, shift=base)
+    dib, res, sp, sd = fe.slice_dev(bb[:, :nb].contiguous(), nb, abs_bb0=base, sync_cap=scap)
+    rr_small, rr = rr, parse_results(res)                          # (rr_small: the same call's record at position 0, above)
+    for c in range(Cn):
+        nd, ns = int(rr[c]["n_dibits"]), int(rr[c]["n_sync"])
+        check("slice_dev at a large base: counts", nd == len(res_ref[c][0]) and ns == len(res_ref[c][1]))
+        k = min(nd, dib.shape[1])
+        check("slice_dev at a large base: dibits", np.array_equal(dib[c, :k].cpu().numpy(), res_ref[c][0][:k]))
+        check("slice_dev at a large base: sync_pos", [int(x) for x in sp[c, :ns].cpu().numpy()] == [int(x) + base for x in res_ref[c][1]])
+        check("slice_dev at a large base: sync_dibit", np.array_equal(sd[c, :ns].cpu().numpy().astype(np.uint64), res_ref[c][2]))
+        # the record: counts, thresholds, clock and flags equal, every absolute index shifted by exactly `base`, -1 stays -1
+        big, small = rr[c], rr_small[c]
+        check("slice_dev at a large base: record counts", all(int(big[f]) == int(small[f]) for f in ("n_baseband", "n_dibits", "n_sync", "n_dibits_after_first", "flags", "reserved")))
+        check("slice_dev at a large base: record indices", all(int(big[f]) == (int(small[f]) + base if int(small[f]) >= 0 else -1) for f in ("first_event", "carry_end", "first_seg_end")
+                                                                 if int(small[f]) < 0 or int(small[f]) > 2))   # (at position 0 an index the tracking clock's lookahead puts in front of the stream reads 0)
+        a_big, a_small = big["anchor_out"], small["anchor_out"]
+        check("slice_dev at a large base: anchor", all(a_big[f].tobytes() == a_small[f].tobytes() for f in ("hi", "mid", "lo", "valid", "period_d", "period_n"))
+              and (not int(a_small["valid"]) or int(a_big["s"]) == int(a_small["s"]) + base))
+    # time shards there: the capture behind a lead-in of zeros (a shard away from position 0 needs its halo; zeros are what the start
+    # of a stream reads as, and only cf32 can say them), the lead-in a multiple of 5 samples long
+    if cuts is not None and s["fmt"] == "cf32":
+        fe1 = mk(1)
+        halo = fe1.shard_halo()
+        assert halo % 40 == 0
+        tp = torch.cat([torch.zeros((halo, 2), dtype=t.dtype, device=t.device), t[0]])
+        D = 5 * (base - halo // 5)                                   # padded index + D = absolute index; the capture's baseband 0 at `base`
+        d_rs = torch.tensor([q + base for q in drops[0]], dtype=torch.int64, device="cuda") if drops[0] else None
+        fes, summ, bb0, bbn = [], [], [], []
+        for i, (a, b) in enumerate(zip(cuts[:-1], cuts[1:])):
+            a, b = a + halo, b + halo
+            f = mk(1)
+            f.resync_at_dev(d_rs)
+            src = tp[a - halo:b]
+            if i % 2:
+                f.shard_pass1_main(src, offset=halo, n_hist=halo, abs0=a + D)
+                rs = f.shard_pass1_finish(src, offset=halo, n_hist=halo, abs0=a + D)
+            else:
+                rs = f.shard_pass1(src, offset=halo, n_hist=halo, abs0=a + D)
+            summ.append(parse_results(rs)[0])
+            bb0.append(n_baseband(0, a + D)); bbn.append(n_baseband(a + D, b - a)); fes.append(f)
+        check("large base: shard grid", bb0[0] == base and bbn == [n_baseband(a, b - a) for a, b in zip(cuts[:-1], cuts[1:])])
+        anc_h, off_h = fe1.shard_resolve(np.array(summ), bb0, bbn)
+        summ_t = torch.from_numpy(np.frombuffer(np.array(summ).tobytes(), dtype=np.uint8).copy()).view(len(fes), -1).cuda()
+        anc, off = fe1.shard_resolve_dev(summ_t, torch.tensor(bb0, dtype=torch.int64, device="cuda"),
+                                         torch.tensor(bbn, dtype=torch.int64, device="cuda"))
+        offs2 = off.cpu().numpy()
+        check("large base: shard resolve host == device", np.array_equal(offs2.astype(np.uint64), off_h) and anc.cpu().numpy().tobytes() == anc_h.tobytes())
+        check("large base: shard offsets", np.array_equal(offs2, offs))
+        got_rows = []
+        for i, f in enumerate(fes):
+            dd, rs2 = f.shard_pass2(anc[i:i + 1], bbn[i], t.device)
+            kk = int(parse_results(rs2)[0]["n_dibits"])
+            check("large base: shard %d count" % i, kk == int(offs2[i + 1] - offs2[i]))
+            got_rows.append(dd[0, :kk].cpu().numpy())
+        check("large base: time shards", np.array_equal(np.concatenate(got_rows) if got_rows else np.zeros(0, np.uint8), ref[0][0]))
     if verbose:
         print("seed %d ok: %r -> %d baseband, %s dibits, %s syncs, %d chunks" % (seed, s, nb, [len(r_[0]) for r_ in ref], [len(r_[1]) for r_ in ref], len(ch)))
     return len(what)

@@ -13,6 +13,13 @@ import numpy as np
 F = np.float32
 
 
+def grid_count(abs0, n, phase, step):
+    """SPEC 3.0 / 3.2: how many samples i of the range [abs0, abs0 + n) lie on a decimation grid, i % step == phase -- in Python
+    integers, for positions of any size (what p25fe_n_baseband / p25fe_n_predecim must return)"""
+    below = lambda x: (x + step - 1 - phase) // step                # ... of [0, x)
+    return below(abs0 + n) - below(abs0)
+
+
 def _shifted(b, k):
     """b[n - k] for every n, zero where n - k < 0"""
     if k == 0:

@@ -377,3 +377,142 @@ def test_cpp_host_driver_built_and_fails_loudly_without_gpu(lib, tmp_path):
     src.write_bytes(bytes(64))
     r = subprocess.run([exe, "u8", str(src), str(tmp_path / "o")], capture_output=True)
     assert r.returncode != 0 and b"no usable HIP device" in r.stderr
+
+
+# ---- stream positions past 2^31 and 2^32 (docs/SPEC.md section 4; the GPU side is tests/test_gpu_positions.py) ----------------------------
+
+def position_args():
+    """entry point -> index of its position argument (abs0 / abs_bb0), read off include/p25fe.h, where it must be a 64-bit type"""
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "p25fe.h")).read(), flags=re.S)
+    out = {}
+    for name, params in re.findall(r"\b(p25fe_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", hdr):
+        for k, p in enumerate(params.split(",")):
+            if re.search(r"\b(abs0|abs_bb0)\s*$", p.strip()):
+                assert re.search(r"\bu?int64_t\b", p), (name, p)
+                out[name] = k
+    return out
+
+
+def test_position_arguments_are_64_bit_in_ctypes_and_in_the_rust_binding(lib):
+    """A position is a sample count of a stream that runs for days: every abs0 / abs_bb0 of the header is (u)int64_t, the ctypes
+    layer passes it as a 64-bit integer and bindings/p25fe.rs declares it u64 or i64 -- at the same argument index."""
+    L = lib.load()
+    args = position_args()
+    assert set(args) == {"p25fe_demod_dev", "p25fe_predecim_dev", "p25fe_n_predecim", "p25fe_slice_dev", "p25fe_shard_pass1",
+                         "p25fe_shard_pass1_main", "p25fe_shard_pass1_finish", "p25fe_shard_pass1_head", "p25fe_shard_pass1_k1",
+                         "p25fe_channelise_dev", "p25fe_n_baseband", "p25fe_n_baseband_h"}, sorted(args)
+    rs = open(os.path.join(ROOT, "bindings", "p25fe.rs")).read()
+    for name, idx in args.items():
+        ty = getattr(L, name).argtypes[idx]
+        assert ty in (C.c_uint64, C.c_int64) and C.sizeof(ty) == 8, (name, idx, ty)
+        m = re.search(r"pub fn %s\(([^)]*)\)" % name, rs)
+        assert m, name
+        params = [p.strip() for p in m.group(1).split(",")]
+        assert re.fullmatch(r"(abs0|abs_bb0): (u64|i64)", params[idx]), (name, idx, params[idx])
+    # the records that carry positions back
+    for dt, f in ((lib.ANCHOR_DTYPE, "s"), (lib.NID_DTYPE, "sync_pos"), (lib.CHAN_STATS_DTYPE, "last_sync_pos"),
+                  (lib.RESULT_DTYPE, "first_event"), (lib.RESULT_DTYPE, "carry_end"), (lib.RESULT_DTYPE, "first_seg_end")):
+        assert dt[f].itemsize == 8
+    for struct, f in (("Anchor", "s"), ("Nid", "sync_pos"), ("ChanStats", "last_sync_pos"),
+                      ("ResultRec", "first_event"), ("ResultRec", "carry_end"), ("ResultRec", "first_seg_end")):
+        body = re.search(r"pub struct %s \{([^}]*)\}" % struct, rs)
+        assert body, struct
+        assert re.search(r"pub %s: (i64|u64)," % f, body.group(1)), (struct, f)
+
+
+def test_count_functions_against_python_integers_at_large_positions(lib):
+    """p25fe_n_baseband, p25fe_n_baseband_h (null handle: the default phase) and p25fe_n_predecim against Python integers around
+    2^31, 2^32, 2^40 and just below 2^63, every residue of the grid, lengths from 0 to a long range."""
+    L = lib.load()
+
+    from spec_model import grid_count as cnt                         # samples i of [abs0, abs0 + n) with i % step == phase
+    for two in (31, 32, 40, 63):
+        for d in list(range(-12, 13)) if two < 63 else list(range(-40, -15)):
+            abs0 = (1 << two) + d
+            for n in (0, 1, 4, 5, 6, 9, 10, 11, 16384, 240000, (1 << 31) + 7, (1 << 33) + 3):
+                if abs0 + n >= 1 << 63 and two == 63 and n > 11:
+                    continue                                        # (positions stay below 2^63: they are stored as int64)
+                assert L.p25fe_n_baseband(abs0, n) == cnt(abs0, n, 4, 5), (abs0, n)
+                assert L.p25fe_n_baseband_h(None, abs0, n) == cnt(abs0, n, 4, 5), (abs0, n)
+                assert L.p25fe_n_predecim(abs0, n) == cnt(abs0, n, 9, 10), (abs0, n)
+
+
+def test_shard_resolve_is_shift_invariant(lib):
+    """p25fe_shard_resolve on summaries shifted by a large baseband offset equals the unshifted resolve, shifted: the same dibit
+    offsets, the same anchors with s moved by the offset -- fixed stride, a lock drop inside a shard, and the tracking clock's
+    period hand-over (the scenes of test_shard_resolve_host_logic)."""
+    L = lib.load()
+    R, A = lib.RESULT_DTYPE, lib.ANCHOR_DTYPE
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+
+    def scene(kind):
+        summ = np.zeros(4, dtype=R)
+        summ[0]["first_event"], summ[0]["n_dibits_after_first"], summ[0]["carry_end"] = 307, 69, 308
+        summ[0]["anchor_out"] = (302, 0.2, 0.0, -0.2, 1, 10, 1)
+        summ[0]["first_seg_end"] = 1000
+        summ[1]["first_event"] = summ[1]["carry_end"] = -1
+        summ[2]["first_event"], summ[2]["n_dibits_after_first"], summ[2]["carry_end"] = 2508, 49, 2509
+        summ[2]["anchor_out"] = (2503, 0.3, 0.1, -0.1, 1, 10, 1)
+        summ[2]["first_seg_end"] = 3000
+        summ[3]["first_event"] = summ[3]["carry_end"] = -1
+        clock = 0
+        if kind == "drop":
+            summ[1]["carry_end"] = 1500
+        if kind == "tracking":
+            clock = 1
+            summ[0]["first_seg_end"], summ[2]["first_seg_end"] = 998, 2998
+            summ[2]["flags"] = 3
+            summ[0]["anchor_out"]["valid"] = 1 | (1 << 8)
+            summ[2]["anchor_out"]["valid"] = 1 | ((-2 & 7) << 8)
+            summ[2]["reserved"] = -2 & 7
+        return summ, clock
+
+    def resolve(summ, clock, shift):
+        s = summ.copy()
+        for r in range(len(s)):
+            for f in ("first_event", "carry_end", "first_seg_end"):
+                if int(s[r][f]) >= 0 and (f != "first_seg_end" or int(s[r]["first_event"]) >= 0):
+                    s[r][f] += shift
+            if int(s[r]["anchor_out"]["valid"]):
+                s[r]["anchor_out"]["s"] += shift
+        bb0 = np.array([shift + 1000 * r for r in range(4)], dtype=np.uint64)
+        bbn = np.full(4, 1000, dtype=np.uint64)
+        anc, off = np.zeros(4, dtype=A), np.zeros(5, dtype=np.uint64)
+        assert L.p25fe_shard_resolve(p(s), p(bb0), p(bbn), 4, clock, p(anc), p(off)) == 0
+        return anc, off
+    for kind in ("plain", "drop", "tracking"):
+        summ, clock = scene(kind)
+        anc0, off0 = resolve(summ, clock, 0)
+        assert off0[-1] > 200 and anc0["valid"].tolist()[1] & 1
+        for shift in ((1 << 31) - 1700, (1 << 32) - 1700, (1 << 32) // 5 - 2300, (1 << 40) - 1700, (1 << 56) - 2700, (1 << 62) - 4001):
+            anc, off = resolve(summ, clock, shift)
+            assert off.tolist() == off0.tolist(), (kind, shift)
+            assert [int(x) for x in anc["s"][anc0["valid"] != 0]] != [int(x) for x in anc0["s"][anc0["valid"] != 0]]
+            for f in ("hi", "mid", "lo", "valid", "period_d", "period_n"):
+                assert anc[f].tobytes() == anc0[f].tobytes(), (kind, shift, f)
+            ok = anc0["valid"] != 0                                  # (s of an anchor that is not valid means nothing)
+            assert [int(x) for x in anc["s"][ok]] == [int(x) + shift for x in anc0["s"][ok]], (kind, shift)
+
+
+def test_position_bound_is_documented_and_mirrored(lib):
+    """The one bound on positions is a documented P25FE_ERR_ARG: include/p25fe.h defines P25FE_MAX_POSITION = 2^62 and says what
+    happens there; the ctypes layer and bindings/p25fe.rs carry the same number.  The calls that need a device are tested on both
+    sides of the bound in tests/test_gpu_positions.py; p25fe_shard_resolve, pure host logic, here."""
+    hdr = open(os.path.join(ROOT, "include", "p25fe.h")).read()
+    assert re.search(r"#define P25FE_MAX_POSITION \(\(uint64_t\)1 << 62\)", hdr)
+    doc = hdr[:hdr.index("#define P25FE_MAX_POSITION")]
+    assert "P25FE_MAX_POSITION" in doc and "P25FE_ERR_ARG" in doc[doc.rindex("/*"):]
+    assert lib.MAX_POSITION == 1 << 62
+    assert "pub const MAX_POSITION: u64 = 1 << 62;" in open(os.path.join(ROOT, "bindings", "p25fe.rs")).read()
+    L = lib.load()
+    R, A = lib.RESULT_DTYPE, lib.ANCHOR_DTYPE
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    summ = np.zeros(2, dtype=R)
+    summ["first_event"] = summ["carry_end"] = -1
+    anc, off = np.zeros(2, dtype=A), np.zeros(3, dtype=np.uint64)
+    top = lib.MAX_POSITION
+    for bb0, bbn, want in (([top - 2000, top - 1000], [1000, 999], lib.OK), ([top - 2000, top - 1000], [1000, 1000], lib.ERR_ARG),
+                           ([top - 1000, top], [1000, 10], lib.ERR_ARG), ([0, 1000], [1000, top], lib.ERR_ARG),
+                           ([(1 << 64) - 1000, 0], [1000, 10], lib.ERR_ARG)):
+        rc = L.p25fe_shard_resolve(p(summ), p(np.array(bb0, dtype=np.uint64)), p(np.array(bbn, dtype=np.uint64)), 2, 0, p(anc), p(off))
+        assert rc == want, (bb0, bbn, rc)

@@ -614,3 +614,30 @@ def test_densest_detections_against_the_independent_batch_model(spec, mode):
         assert len(got[1]) > 600
         for k in range(3):
             assert len(got[k]) == len(ref[k]) and np.array_equal(got[k], np.asarray(ref[k]).astype(got[k].dtype)), (mode, drops, k)
+
+
+@pytest.mark.parametrize("two", [31, 32, 40, 56, 63])
+def test_channelise_is_shift_invariant_modulo_its_periods(spec, two):
+    """docs/SPEC.md section 4 for the channeliser: the stream depends on abs0 only through abs0 mod 10 (the decimation grid) and abs0 mod 192
+    (the mixer's phase), so oracle.channelise at a large abs0 equals, bit for bit, the one at P' = abs0 mod lcm(10, 192) = 960 --
+    every residue of the grid, ranges that straddle the power of two, without and with history.  This is what lets the GPU tests use
+    the small position as the reference for the large one."""
+    rng = np.random.default_rng(two)
+    n = 3000
+    x = ((rng.standard_normal(n) + 1j * rng.standard_normal(n)) * 0.3).astype(np.complex64)
+    outs = set()
+    for r in range(10):
+        P = (1 << two) - n // 2 - 7
+        P += (r - P) % 10
+        if two == 63:
+            P -= 1 << 12                                             # (positions stay below 2^63)
+        small = O.channelise(x, abs0=P % 960, spec=spec)
+        large = O.channelise(x, abs0=P, spec=spec)
+        assert small.shape == large.shape and small.shape[1] == (P % 10 + n) // 10
+        assert np.array_equal(small.view(np.uint32), large.view(np.uint32)), (two, r)
+        h = 100
+        small_h = O.channelise(x, n_hist=h, abs0=P % 960 + 960, spec=spec)
+        large_h = O.channelise(x, n_hist=h, abs0=P, spec=spec)
+        assert np.array_equal(small_h.view(np.uint32), large_h.view(np.uint32)), (two, r)
+        outs.add(small[7].tobytes())
+    assert len(outs) == 10                                           # the residues are different streams: the property is not vacuous
