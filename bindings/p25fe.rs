@@ -21,6 +21,9 @@ pub const MAX_POSITION: u64 = 1 << 62;
 pub const MAX_TAPS: usize = 64;
 pub const FMT_CF32: c_int = 0;
 pub const FMT_U8: c_int = 1;
+pub const FMT_S16: c_int = 2;
+/// P25FE_S16_SCALE: an int16 v of an FMT_S16 stream is the sample v as f32 * 2^-15, exactly
+pub const S16_SCALE: f32 = 1.0 / 32768.0;
 pub const CLOCK_FIXED: i32 = 0;
 pub const CLOCK_TRACKING: i32 = 1;
 /// CLOCK_TRACKING, and the calls that hold a whole range (run_dev, run_dev_pipelined, slice_dev) re-slice the first frame of a lock
@@ -156,6 +159,8 @@ extern "C" {
     pub fn p25fe_kernel_variant(h: *const Handle) -> c_int;
     pub fn p25fe_specialize(cfg: *const Config, dir: *const c_char, path_out: *mut c_char, path_cap: usize) -> c_int;
     pub fn p25fe_probe_variant(cfg: *const Config) -> c_int;
+    pub fn p25fe_format_variant(h: *const Handle, fmt: c_int) -> c_int;
+    pub fn p25fe_probe_format_variant(cfg: *const Config, fmt: c_int) -> c_int;
     pub fn p25fe_specialize_log(buf: *mut c_char, cap: usize) -> usize;
     // streaming, host buffers: the bodies of DemodTask::run (src/demod.rs:70-117) and RecvTask::run (src/recv.rs:148-150)
     pub fn p25fe_demod_u8(h: *mut Handle, iq: *const u8, n_bytes: usize, bb: *mut f32, bb_cap: usize, n_out: *mut usize,
@@ -166,6 +171,9 @@ extern "C" {
                        sync_pos: *mut i64, sync_dibit: *mut u64, sync_cap: usize, n_sync: *mut usize) -> c_int;
     pub fn p25fe_run_u8(h: *mut Handle, iq: *const u8, n_bytes: usize, dibits: *mut u8, cap: usize, n_dibits: *mut usize) -> c_int;
     pub fn p25fe_run_cf32(h: *mut Handle, iq: *const f32, n_samples: usize, dibits: *mut u8, cap: usize, n_dibits: *mut usize) -> c_int;
+    pub fn p25fe_run_s16(h: *mut Handle, iq: *const i16, n_samples: usize, dibits: *mut u8, cap: usize, n_dibits: *mut usize) -> c_int;
+    pub fn p25fe_demod_s16(h: *mut Handle, iq: *const i16, n_samples: usize, bb: *mut f32, bb_cap: usize, n_out: *mut usize,
+                           power_dbm: *mut f32) -> c_int;
     pub fn p25fe_run_host_windows(h: *mut Handle, iq: *const c_void, fmt: c_int, n: usize, window: usize, dibits: *mut u8,
                                   cap: usize, n_dibits: *mut usize, stats: *mut WindowsStats) -> c_int;
     pub fn p25fe_resync(h: *mut Handle) -> c_int;

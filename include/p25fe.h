@@ -73,7 +73,7 @@ typedef enum p25fe_status {
     P25FE_ERR_NO_DEVICE = -2,  /* no HIP device / wrong architecture */
     P25FE_ERR_HIP = -3,        /* a HIP runtime call failed (see p25fe_last_hip_error) */
     P25FE_ERR_CAPACITY = -4,   /* output buffer too small; nothing consumed */
-    P25FE_ERR_FORMAT = -5,     /* u8 / cf32 mixed within one stream */
+    P25FE_ERR_FORMAT = -5,     /* u8 / cf32 / s16 mixed within one stream */
     P25FE_ERR_NOMEM = -6,
     P25FE_ERR_JIT = -7,        /* specialising the kernels failed (p25fe_specialize_log has the compiler's words) */
     P25FE_ERR_TIMEOUT = -8     /* a device-side wait gave up (the head segment of a time shard never arrived: p25fe_shard_head_check) */
@@ -81,8 +81,14 @@ typedef enum p25fe_status {
 
 typedef enum p25fe_format {
     P25FE_FMT_CF32 = 0,        /* interleaved float32 I,Q (num::Complex32 layout) */
-    P25FE_FMT_U8 = 1           /* interleaved uint8 I,Q (RTL-SDR; src/demod.rs:74-76) */
+    P25FE_FMT_U8 = 1,          /* interleaved uint8 I,Q (RTL-SDR; src/demod.rs:74-76) */
+    P25FE_FMT_S16 = 2          /* interleaved int16_t I,Q, native little-endian, I first, 4 bytes per complex sample (Airspy, SDRplay,
+                                  USRP sc16, BladeRF, SigMF ci16_le; no reference item: the reference reads an RTL-SDR).  Value
+                                  (float)v * P25FE_S16_SCALE -- exact in fp32 for every int16_t, -32768 is -1.0 -- so an s16 stream IS the
+                                  cf32 stream of its converted samples, bit for bit, at every output (docs/SPEC.md 3.1).  The scale
+                                  is fixed: no configuration field. */
 } p25fe_format;
+#define P25FE_S16_SCALE 0x1p-15f
 
 /* Replaces the compile-time DSP parameters of DemodTask::new (src/demod.rs:49-54: every constructor argument of the four DSP
  * objects, ABI 5), the type-level tap tables of p25_filts (DecimFir / BandpassFir, src/demod.rs:27-29), the arguments of
@@ -205,6 +211,11 @@ int p25fe_device(const p25fe_t *h);              /* HIP device ordinal the handl
 #define P25FE_VARIANT_SPECIALIZED 1
 #define P25FE_VARIANT_GENERIC 2
 int p25fe_kernel_variant(const p25fe_t *h);      /* < 0: null handle */
+/* The same per input format.  P25FE_FMT_U8 / _CF32: p25fe_kernel_variant.  P25FE_FMT_S16 has no specialised kernels (a code object
+ * keeps exactly its six): BUILTIN with the build's numbers; with any others GENERIC -- said once per process on stderr unless
+ * specialize is _OFF or P25FE_QUIET=1 -- or, on a handle created with P25FE_SPECIALIZE_REQUIRE / _FORCE, P25FE_ERR_JIT, which is
+ * then also what every call given s16 input returns, before any state moves.  P25FE_ERR_ARG: null handle, unknown format. */
+int p25fe_format_variant(const p25fe_t *h, int fmt);
 /* Ahead-of-time form of what p25fe_create does for non-default numbers (the `make SPEC=` step; needs no GPU): compile the
  * front-end kernels for cfg's tables and constants and store the code object as <dir>/p25fe-<hash>.hsaco (dir NULL: the
  * cache directory -- $P25FE_CACHE_DIR, else $XDG_CACHE_HOME/p25fe, else $HOME/.cache/p25fe, else /tmp/p25fe-cache-<uid>;
@@ -220,6 +231,8 @@ int p25fe_specialize(const p25fe_config_t *cfg, const char *dir, char *path_out,
  * writable by their owner only; every file carries a trailer that ties its content to cfg's numbers and is verified
  * before it reaches the loader; files under $P25FE_SPEC_DIR are never deleted. */
 int p25fe_probe_variant(const p25fe_config_t *cfg);
+/* p25fe_format_variant without a device: p25fe_probe_variant for P25FE_FMT_U8 / _CF32, the rule above for P25FE_FMT_S16. */
+int p25fe_probe_format_variant(const p25fe_config_t *cfg, int fmt);
 /* compiler log of the calling thread's last p25fe_specialize / p25fe_create; returns the length copied (NUL-terminated) */
 size_t p25fe_specialize_log(char *buf, size_t cap);
 
@@ -248,10 +261,15 @@ int p25fe_demod_cf32(p25fe_t *h, const float *iq, size_t n_samples, float *bb, s
 int p25fe_slice(p25fe_t *h, const float *bb, size_t n, uint8_t *dibits, size_t cap, size_t *n_dibits,
                 int64_t *sync_pos, uint64_t *sync_dibit, size_t sync_cap, size_t *n_sync);
 
+/* Same for interleaved int16_t input (P25FE_FMT_S16): n_samples complex samples = 2 n_samples int16_t per channel. */
+int p25fe_demod_s16(p25fe_t *h, const int16_t *iq, size_t n_samples, float *bb, size_t bb_cap, size_t *n_out,
+                    float *power_dbm);
+
 /* Both halves with the baseband kept in HBM (DemodTask -> RecvTask without the channel hop).  Capacity as for
  * p25fe_slice with n = the chunk's baseband samples (p25fe_n_baseband): n_samples / 30 + 4 is always enough. */
 int p25fe_run_u8(p25fe_t *h, const uint8_t *iq, size_t n_bytes, uint8_t *dibits, size_t cap, size_t *n_dibits);
 int p25fe_run_cf32(p25fe_t *h, const float *iq, size_t n_samples, uint8_t *dibits, size_t cap, size_t *n_dibits);
+int p25fe_run_s16(p25fe_t *h, const int16_t *iq, size_t n_samples, uint8_t *dibits, size_t cap, size_t *n_dibits);
 
 /* A LONG capture in host memory through the same path at the speed of the bus: the capture is cut into windows of `window`
  * samples per channel (0: 64 MB worth; rounded down to a multiple of 8, at least 8 192); window k + 1 travels to the GPU
@@ -300,7 +318,8 @@ int p25fe_state_import(p25fe_t *h, const void *buf, size_t n);
 
 /* ---- device-resident ranges: the measured path -------------------------------------------------
  * d_iq points at the first OWNED sample of channel 0; channel c starts ch_stride elements
- * (complex samples for CF32, byte pairs for U8) later.  n_hist valid samples precede each
+ * (complex samples for CF32 and S16, byte pairs for U8) later; it is 16-byte aligned, and ch_stride a multiple of 2 (CF32),
+ * 4 (S16) or 8 (U8) samples, so that every channel's first owned sample is (P25FE_ERR_ARG otherwise).  n_hist valid samples precede each
  * channel's first owned sample in memory (0 at the start of a stream: history reads as zero,
  * exactly like the zero-initialised filters of DemodTask::new); abs0 is the absolute index of
  * the first owned sample in its stream (fixes the 5:1 grid, src/demod.rs:87-90).

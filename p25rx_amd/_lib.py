@@ -12,7 +12,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libp25fe.so")
 MAX_TAPS = 64
 ABI_VERSION = 6
-FMT_CF32, FMT_U8 = 0, 1
+FMT_CF32, FMT_U8, FMT_S16 = 0, 1, 2
+S16_SCALE = 2.0 ** -15                    # P25FE_S16_SCALE: an int16 v is the sample (float)v * 2^-15, exactly
 MAX_POSITION = 1 << 62                   # P25FE_MAX_POSITION: abs0 / abs_bb0 from here on are P25FE_ERR_ARG
 
 OK, ERR_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_CAPACITY, ERR_FORMAT, ERR_NOMEM, ERR_JIT, ERR_TIMEOUT = 0, -1, -2, -3, -4, -5, -6, -7, -8
@@ -73,6 +74,7 @@ SYMBOLS = [
     "p25fe_shard_pass1_main", "p25fe_shard_pass1_finish", "p25fe_shard_compact_dev", "p25fe_resync_at_dev",
     "p25fe_kernel_variant", "p25fe_specialize", "p25fe_specialize_log", "p25fe_run_host_windows",
     "p25fe_shard_pass1_head", "p25fe_shard_pipe_begin", "p25fe_shard_pipe_end", "p25fe_rx_stream", "p25fe_shard_head_check", "p25fe_shard_pass1_k1", "p25fe_streams_share_queue", "p25fe_shard_pass2_dev", "p25fe_shard_compact_from_dev", "p25fe_probe_variant", "p25fe_n_baseband_h",
+    "p25fe_demod_s16", "p25fe_run_s16", "p25fe_format_variant", "p25fe_probe_format_variant",
 ]
 
 
@@ -116,13 +118,17 @@ def load():
     L.p25fe_kernel_variant.argtypes = [vp]
     L.p25fe_specialize.argtypes = [C.POINTER(Config), C.c_char_p, C.c_char_p, sz]
     L.p25fe_probe_variant.argtypes = [C.POINTER(Config)]
+    L.p25fe_format_variant.argtypes = [vp, C.c_int]
+    L.p25fe_probe_format_variant.argtypes = [C.POINTER(Config), C.c_int]
     L.p25fe_specialize_log.argtypes = [C.c_char_p, sz]
     L.p25fe_specialize_log.restype = sz
     L.p25fe_demod_u8.argtypes = [vp, vp, sz, vp, sz, psz, vp]
     L.p25fe_demod_cf32.argtypes = [vp, vp, sz, vp, sz, psz, vp]
+    L.p25fe_demod_s16.argtypes = [vp, vp, sz, vp, sz, psz, vp]
     L.p25fe_slice.argtypes = [vp, vp, sz, vp, sz, vp, vp, vp, sz, vp]
     L.p25fe_run_u8.argtypes = [vp, vp, sz, vp, sz, vp]
     L.p25fe_run_cf32.argtypes = [vp, vp, sz, vp, sz, vp]
+    L.p25fe_run_s16.argtypes = [vp, vp, sz, vp, sz, vp]
     L.p25fe_run_host_windows.argtypes = [vp, vp, C.c_int, sz, sz, vp, sz, vp, C.POINTER(WindowsStats)]
     L.p25fe_resync.argtypes = [vp]
     L.p25fe_reset.argtypes = [vp]
@@ -239,6 +245,15 @@ def probe_variant(cfg):
     rc = L.p25fe_probe_variant(C.byref(cfg))
     if rc < 0:
         raise P25feError(rc, L.p25fe_strerror(rc).decode() + ": " + specialize_log()[-2000:])
+    return rc
+
+
+def probe_format_variant(cfg, fmt):
+    """p25fe_probe_format_variant: the kernels input format `fmt` would run on a handle made from cfg (VARIANT_*); no GPU needed"""
+    L = load()
+    rc = L.p25fe_probe_format_variant(C.byref(cfg), int(fmt))
+    if rc < 0:
+        raise P25feError(rc, L.p25fe_strerror(rc).decode())
     return rc
 
 

@@ -139,6 +139,15 @@ def to_u8(iq):
     return np.clip(np.rint((z + 1.0) * 127.5), 0, 255).astype(np.uint8)
 
 
+def to_s16(iq, full_scale=32767):
+    """cf32 -> interleaved int16 I/Q [2 n] (FMT_S16: I first; the library reads v as v * 2^-15).  A sample of 1.0 becomes
+    `full_scale`; round to nearest, clipped to int16."""
+    z = np.empty(2 * len(iq), dtype=np.float64)
+    z[0::2] = iq.real
+    z[1::2] = iq.imag
+    return np.clip(np.rint(z * float(full_scale)), -32768, 32767).astype(np.int16)
+
+
 def align_dibits(decoded, truth, max_skip=64):
     """Find k, j such that decoded[k:] matches truth[j:], return (k, j, n_matched, n_errors).
 

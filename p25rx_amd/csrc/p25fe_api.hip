@@ -106,7 +106,10 @@ inline void launch_ev(void (*kern)(Args...), dim3 grid, dim3 block, size_t lds, 
     if (e0 || e1) hipExtLaunchKernelGGL(kern, grid, block, (uint32_t)lds, st, e0, e1, 0u, Args(args)...);
     else hipLaunchKernelGGL(kern, grid, block, lds, st, Args(args)...);
 }
-inline size_t fmt_bytes(int fmt) { return fmt == P25FE_FMT_CF32 ? 8 : 2; }
+inline bool fmt_known(int fmt) { return fmt == P25FE_FMT_CF32 || fmt == P25FE_FMT_U8 || fmt == P25FE_FMT_S16; }
+inline size_t fmt_bytes(int fmt) { return (size_t)fmt_bps(fmt); }  // bytes per complex sample: 8 / 2 / 4 (p25fe_kernels.hip)
+// samples a channel stride must be a multiple of, so that every channel's owned sample 0 is 16-byte aligned
+inline size_t fmt_stride_unit(int fmt) { return 16 / fmt_bytes(fmt); }
 
 static_assert(BBPAD == (size_t)TAILN && BBPAD >= (size_t)HIST_BB + CLK_L, "baseband tail kept between calls");
 
@@ -239,7 +242,7 @@ struct StreamState {
         StateHeader hd;
         memcpy(&hd, p, sizeof hd); p += sizeof hd;
         if (hd.magic != STATE_MAGIC || hd.abi != P25FE_ABI_VERSION || hd.n_channels != (int32_t)anchor.size()) return false;
-        if (hd.fmt_locked != -1 && hd.fmt_locked != P25FE_FMT_U8 && hd.fmt_locked != P25FE_FMT_CF32) return false;
+        if (hd.fmt_locked != -1 && !fmt_known(hd.fmt_locked)) return false;
         if (hd.abs_iq >= P25FE_MAX_POSITION || hd.abs_bb >= P25FE_MAX_POSITION) return false;
         Sec s[4]; sections(s);
         // a blob is data from outside: every anchor's clock must be a usable period before anything is taken over
@@ -324,6 +327,7 @@ struct p25fe {
     Taps taps;                             // resolved numbers: padded tables, the u8 table, the discriminator's scale
     int k1_p = 5;                          // FIR outputs per thread
     int variant = P25FE_VARIANT_BUILTIN;   // which front-end kernels run (p25fe_kernel_variant)
+    bool dflt = true;                      // the numbers are the build's own (the built-in kernels carry them, whatever `variant` says)
     bool long_taps = false;                // more than P25FE_T1 / P25FE_T2 taps -> the 64 / 64 geometry (Geo<5, 1>)
     int phase = P25FE_DECIM_PHASE;         // p25fe_config_t.decim_phase: baseband sample m comes from input 5 m + phase
     int n_avg = BOX;                       // post-discriminator filter: taps in use (the table is taps.avg)
@@ -520,6 +524,31 @@ static int choose_variant(const p25fe_config_t* cfg, const Resolved& rs, std::ve
     return plain;
 }
 
+// s16 has no specialised kernels yet (a code object keeps exactly its six): a configuration whose numbers are
+// not the build's runs s16 through the generic kernels -- said once per process on stderr, like the notice above -- unless it
+// demands specialised ones, which cannot be had.
+static void s16_generic_notice()
+{
+    static bool said = false;
+    if (said) return;
+    said = true;
+    const char* q = getenv("P25FE_QUIET");
+    if (q && atoi(q) != 0) return;
+    fprintf(stderr, "p25fe: P25FE_FMT_S16 has no specialised kernels: with this configuration's numbers s16 input runs the GENERIC "
+                    "kernels (u8 and cf32 are not affected; p25fe_format_variant() reports it per format).\n");
+}
+// The kernels format `fmt` runs with: `variant` (what u8 and cf32 get) for those two; for s16 BUILTIN with the build's numbers, else
+// GENERIC, or P25FE_ERR_JIT where the configuration requires specialised kernels.
+static int format_variant_of(int variant, bool dflt, int specialize, int fmt)
+{
+    if (!fmt_known(fmt)) return P25FE_ERR_ARG;
+    if (fmt != P25FE_FMT_S16 || variant < 0) return variant;
+    if (dflt) return P25FE_VARIANT_BUILTIN;
+    if (specialize >= P25FE_SPECIALIZE_REQUIRE) return P25FE_ERR_JIT;
+    if (specialize != P25FE_SPECIALIZE_OFF) s16_generic_notice();
+    return P25FE_VARIANT_GENERIC;
+}
+
 #define HIPCHK(h, expr)                                                        \
     do {                                                                       \
         hipError_t e__ = (expr);                                               \
@@ -570,6 +599,10 @@ const char* p25fe_strerror(int status)
 int p25fe_last_hip_error(const p25fe_t* h) { return h ? h->last_hip : 0; }
 int p25fe_device(const p25fe_t* h) { return h ? h->cfg.device : -1; }
 int p25fe_kernel_variant(const p25fe_t* h) { return h ? h->variant : -1; }
+int p25fe_format_variant(const p25fe_t* h, int fmt)
+{
+    return h ? format_variant_of(h->variant, h->dflt, h->cfg.specialize, fmt) : P25FE_ERR_ARG;
+}
 
 size_t p25fe_specialize_log(char* buf, size_t cap)
 {
@@ -614,6 +647,16 @@ int p25fe_probe_variant(const p25fe_config_t* cfg)
     } catch (...) {
         return P25FE_ERR_NOMEM;
     }
+}
+
+int p25fe_probe_format_variant(const p25fe_config_t* cfg, int fmt)
+{
+    if (!cfg || !fmt_known(fmt)) return P25FE_ERR_ARG;
+    if (fmt != P25FE_FMT_S16) return p25fe_probe_variant(cfg);
+    Resolved r;
+    const int rc = resolve_config(cfg, &r);
+    if (rc) return rc;
+    return format_variant_of(P25FE_VARIANT_GENERIC, r.dflt, cfg->specialize, fmt);
 }
 
 static inline size_t n_baseband_ph(int phase, uint64_t abs0, size_t n)
@@ -667,6 +710,7 @@ int p25fe_create(const p25fe_config_t* cfg, p25fe_t** out)
     h->long_taps = rs.long_taps;
     h->u8_lut_mode = !rs.lut_affine;
     h->variant = rs.dflt ? P25FE_VARIANT_BUILTIN : P25FE_VARIANT_GENERIC;
+    h->dflt = rs.dflt;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { p25fe_destroy(h); return P25FE_ERR_HIP; }
     hipError_t e = hipSuccess;
     {
@@ -761,6 +805,13 @@ void p25fe_destroy(p25fe_t* h)
 // part: which segments of a time shard's range run -- every one; only those whose input window lies inside the owned samples
 // (the main launch, runs while the halo is still on the wire); the others (the head, after the halo has arrived)
 enum K1Part { K1_ALL = 0, K1_MAIN = 1, K1_HEAD = 2 };
+// An entry point's first question about its `fmt`, asked before anything moves: P25FE_ERR_ARG for a format that does not exist,
+// P25FE_ERR_JIT for s16 on a handle that may only run specialised kernels, else 0.
+static int format_unusable(const p25fe_t* h, int fmt)
+{
+    const int v = format_variant_of(h->variant, h->dflt, h->cfg.specialize, fmt);
+    return v < 0 ? v : P25FE_OK;
+}
 struct K1Launch {
     const void* src = nullptr;             // owned sample 0 of channel 0, n_hist valid samples in front of it
     int fmt = P25FE_FMT_CF32;
@@ -782,7 +833,7 @@ struct K1Launch {
 struct K1Plan {
     bool empty;                            // nothing to launch: no output, or no segment on this side of the part split
     K1Args a;                              // complete but for power_partial (the launch allocates it)
-    bool u8, ct; int pk;                   // which kernel: format, immediate coefficients, FIR outputs per lane
+    int fmt, variant; bool ct; int pk;     // which kernel: format, the variant that format runs (format_variant_of), immediate coefficients, FIR outputs per lane
     long n_seg;                            // segments of the whole range (a.seg_first, a.seg_count: this launch's)
     long head_end;                         // planar position up to which the head's segments write (part != K1_ALL)
     size_t lds;
@@ -790,11 +841,12 @@ struct K1Plan {
 static int k1_plan(const p25fe_t* h, const K1Launch& L, K1Plan* p)
 {
     const int fmt = L.fmt;
-    if (fmt != P25FE_FMT_CF32 && fmt != P25FE_FMT_U8) return P25FE_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(L.src) & 15u) != 0) return P25FE_ERR_ARG;   // 16-B vector loads
-    if (h->C > 1 && (L.ch_stride % (fmt == P25FE_FMT_CF32 ? 2 : 8)) != 0) return P25FE_ERR_ARG;
+    const int variant = format_variant_of(h->variant, h->dflt, h->cfg.specialize, fmt);
+    if (variant < 0) return variant;                               // unknown format; s16 where only specialised kernels will do
+    if ((reinterpret_cast<uintptr_t>(L.src) & 15u) != 0) return P25FE_ERR_ARG;   // owned sample 0 on a 16-byte boundary, every format
+    if (h->C > 1 && (L.ch_stride % fmt_stride_unit(fmt)) != 0) return P25FE_ERR_ARG;
     if (L.chunk && (!L.planar || L.part)) return P25FE_ERR_ARG;
-    const bool pro = seg_prologue(fmt);                            // p25fe_kernels.hip: segment prologue (u8) or recomputed halo (cf32)
+    const bool pro = seg_prologue(fmt);                            // p25fe_kernels.hip: segment prologue (u8, s16) or recomputed halo (cf32)
     const long m_begin = !L.planar ? 0 : (pro ? -(long)PLPAD - h->look : -(long)HIST_BB - h->look);
     const size_t n_out = p25fe_n_baseband_h(h, L.abs0, L.n);
     const long total = (long)n_out - m_begin;
@@ -807,19 +859,20 @@ static int k1_plan(const p25fe_t* h, const K1Launch& L, K1Plan* p)
     // 0.23-0.27 ms depending on the box -- neighbouring workgroups then stream neighbouring DRAM pages and the
     // dispatcher balances the CUs, which outweighs recomputing the 50-sample filter halo once per segment (5.5 % at
     // 3 sub-tiles; A/B on one box, three rounds: 2 -> 0.275, 3 -> 0.264, 4 -> 0.269 ms).  P25FE_SUBS overrides.
-    const int pk = (L.planar || h->long_taps || h->variant == P25FE_VARIANT_SPECIALIZED) ? 5 : h->k1_p;
+    const int pk = (L.planar || h->long_taps || variant == P25FE_VARIANT_SPECIALIZED) ? 5 : h->k1_p;
     const int t1 = h->long_taps ? TMAX : T1;
     const long sub = (long)WV * pk;
     static const long subs_env = [] { const char* e = getenv("P25FE_SUBS"); return e ? atol(e) : 0L; }();
     // (round 2: the instruction-bound u8 kernel prefers longer segments -- less halo recomputed: 3 -> 239, 6 -> 231 us on one
     // box; with the final build 4 -> 222 / 216, 6 -> 217 / 215, 9 -> 212 / 209, 12 -> 216 / 205 us under rocprofv3)
-    long subs = subs_env > 0 ? subs_env : (fmt == P25FE_FMT_U8 ? 9 : 3);
+    // (s16: u8's length until a box says otherwise -- docs/MEASUREMENTS.md)
+    long subs = subs_env > 0 ? subs_env : (fmt == P25FE_FMT_U8 ? 9 : (fmt == P25FE_FMT_S16 ? P25FE_K1_SUBS_S16 : 3));
     if (L.chunk) subs = 1;                                          // a chunk is latency: every sub-tile its own workgroup
     if (subs > 32768) subs = 32768;
     // the post-discriminator filter's length as far as the kernel's GEOMETRY goes (frontend_body's T3): the handle's own for the
     // immediate-coefficient kernels, the ABI's ceiling for the generic ones; the halo form's recomputed halo follows the
     // handle's real length either way (the generic kernels take it as an argument)
-    const bool ct = h->variant != P25FE_VARIANT_GENERIC;
+    const bool ct = variant != P25FE_VARIANT_GENERIC;
     const int t2e = h->long_taps ? TMAX : T2;
     const int t3geo = ct ? h->n_avg : TMAX;
     const long segh = seg_halo_for(h->n_avg, t2e);
@@ -854,7 +907,7 @@ static int k1_plan(const p25fe_t* h, const K1Launch& L, K1Plan* p)
         if (p->empty) return P25FE_OK;
     }
     if (seg_count * (long)h->C > 0x7fffffffL) return P25FE_ERR_ARG;
-    p->u8 = fmt == P25FE_FMT_U8; p->ct = ct; p->pk = pk; p->n_seg = n_seg;
+    p->fmt = fmt; p->variant = variant; p->ct = ct; p->pk = pk; p->n_seg = n_seg;
     a.x = L.src; a.ch_stride = (long)L.ch_stride; a.n_hist = (long)L.n_hist; a.n_new = (long)L.n; a.o0 = (int)o0; a.n_ch = h->C;
     a.bb = L.bb; a.bb_stride = (long)L.bb_stride; a.power_partial = nullptr;
     a.subs_per_seg = (int)subs; a.seg_first = (int)seg_first; a.seg_count = (int)seg_count; a.lead_segs = (int)lead; a.seg_halo = (int)segh;
@@ -868,7 +921,7 @@ static int k1_plan(const p25fe_t* h, const K1Launch& L, K1Plan* p)
     // LDS per workgroup: [d carry | window] (+ taps: generic kernels) (+ the u8 table: generic u8 kernels, and specialised ones
     // whose table is not affine).  Immediate-coefficient kernels never touch the taps area at the end of the layout: not
     // allocated.  (13 376 B per wave is 11 waves per CU; a 12th would need 13 312 -- trimming to that changed nothing.)
-    const bool lut = p->u8 && (!ct || h->u8_lut_mode);
+    const bool lut = fmt == P25FE_FMT_U8 && (!ct || h->u8_lut_mode);
     p->lds = h->long_taps ? k1_lds_bytes<Geo<5, 1>>(ct, lut, t3geo) : (pk == 3 ? k1_lds_bytes<Geo<3>>(ct, lut, t3geo) : k1_lds_bytes<Geo<5>>(ct, lut, t3geo));
     // (experiments: extra dynamic LDS per workgroup = fewer resident waves per CU; the occupancy sensitivity of docs/MEASUREMENTS.md)
     static const size_t lds_pad_env = [] { const char* e = getenv("P25FE_K1_LDS_PAD"); return e ? (size_t)atol(e) : (size_t)0; }();
@@ -891,6 +944,22 @@ template <int FMT> static ChunkKernel chunk_kernel_of(bool ct, bool long_taps)
 {
     if (long_taps) return k_chunk<FMT, false, 1>;
     return ct ? k_chunk<FMT, true, 0> : k_chunk<FMT, false, 0>;
+}
+static K1Kernel k1_kernel_of(int fmt, bool ct, int pk, bool planar, bool long_taps)
+{
+    switch (fmt) {
+    case P25FE_FMT_U8: return k1_kernel_of<P25FE_FMT_U8>(ct, pk, planar, long_taps);
+    case P25FE_FMT_S16: return k1_kernel_of<P25FE_FMT_S16>(ct, pk, planar, long_taps);
+    default: return k1_kernel_of<P25FE_FMT_CF32>(ct, pk, planar, long_taps);
+    }
+}
+static ChunkKernel chunk_kernel_of(int fmt, bool ct, bool long_taps)
+{
+    switch (fmt) {
+    case P25FE_FMT_U8: return chunk_kernel_of<P25FE_FMT_U8>(ct, long_taps);
+    case P25FE_FMT_S16: return chunk_kernel_of<P25FE_FMT_S16>(ct, long_taps);
+    default: return chunk_kernel_of<P25FE_FMT_CF32>(ct, long_taps);
+    }
 }
 
 static int launch_k1(p25fe_t* h, const K1Launch& L)
@@ -919,20 +988,19 @@ static int launch_k1(p25fe_t* h, const K1Launch& L)
     }
     const Taps* dt = h->d_taps.as<Taps>();
     const dim3 grid((unsigned)a.seg_count, (unsigned)h->C);          // one one-wave workgroup per (segment, channel)
-    if (h->variant == P25FE_VARIANT_SPECIALIZED) {
-        // kernels compiled for this handle's numbers (p25fe_jit.cpp): same source, same launch shape, C entry points
-        hipFunction_t f = h->jit_fn[p.u8 ? 1 : 0][L.chunk ? 2 : (L.planar ? 1 : 0)];
+    if (p.variant == P25FE_VARIANT_SPECIALIZED) {
+        // kernels compiled for this handle's numbers (p25fe_jit.cpp): same source, same launch shape, C entry points (u8 and cf32)
+        hipFunction_t f = h->jit_fn[p.fmt == P25FE_FMT_U8 ? 1 : 0][L.chunk ? 2 : (L.planar ? 1 : 0)];
         void* params[3] = {&a, &dt, &tail};
         if (L.ev0 || L.ev1)
             HIPCHK(h, hipExtModuleLaunchKernel(f, grid.x * WV, grid.y, 1, WV, 1, 1, p.lds, st, params, nullptr, L.ev0, L.ev1, 0));
         else
             HIPCHK(h, hipModuleLaunchKernel(f, grid.x, grid.y, 1, WV, 1, 1, (unsigned)p.lds, st, params, nullptr));
     } else if (L.chunk) {
-        const ChunkKernel k = p.u8 ? chunk_kernel_of<P25FE_FMT_U8>(p.ct, h->long_taps) : chunk_kernel_of<P25FE_FMT_CF32>(p.ct, h->long_taps);
+        const ChunkKernel k = chunk_kernel_of(p.fmt, p.ct, h->long_taps);
         hipLaunchKernelGGL(k, grid, dim3(WV), p.lds, st, a, dt, tail);
     } else {
-        const K1Kernel k = p.u8 ? k1_kernel_of<P25FE_FMT_U8>(p.ct, p.pk, L.planar, h->long_taps)
-                                : k1_kernel_of<P25FE_FMT_CF32>(p.ct, p.pk, L.planar, h->long_taps);
+        const K1Kernel k = k1_kernel_of(p.fmt, p.ct, p.pk, L.planar, h->long_taps);
         launch_ev(k, grid, dim3(WV), p.lds, st, L.ev0, L.ev1, a, dt);
     }
     HIPCHK(h, hipGetLastError());
@@ -1222,6 +1290,7 @@ int p25fe_demod_dev(p25fe_t* h, const void* d_iq, int fmt, size_t ch_stride, siz
                     float* d_bb, size_t bb_stride, float* d_power_dbm, void* stream)
 {
     if (!h || !d_iq || !d_bb || position_refused(abs0)) return P25FE_ERR_ARG;
+    if (int frc = format_unusable(h, fmt)) return frc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     K1Launch k;
     k.src = d_iq; k.fmt = fmt; k.ch_stride = ch_stride; k.n_hist = n_hist; k.n = n; k.abs0 = abs0;
@@ -1377,6 +1446,7 @@ static int pipe_open(p25fe_t* h, hipStream_t st, int depth = 2)
 static int run_dev(p25fe_t* h, const void* d_iq, int fmt, size_t ch_stride, size_t n, const RecvDest& dest, hipStream_t st, bool pipelined)
 {
     if (!h || !d_iq || !dest.dibits || !dest.result || p25fe_n_baseband_h(h, 0, n) > MAX_RANGE_BB) return P25FE_ERR_ARG;
+    if (int frc = format_unusable(h, fmt)) return frc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     h->sh.invalidate();
     if (int orc = pipelined ? pipe_open(h, st, h->run_depth) : pipe_join(h, st)) return orc;
@@ -1429,6 +1499,7 @@ static int shard_pass1_part(p25fe_t* h, const void* d_iq, int fmt, size_t ch_str
     const bool do_main = (what & SH_MAIN) != 0, do_finish = (what & SH_RECV) != 0;
     bool do_head = (what & SH_HEAD) != 0;
     if (!h || !d_iq || (do_finish && !d_result) || position_refused(abs0) || p25fe_n_baseband_h(h, abs0, n) > MAX_RANGE_BB || piecewise_refused(h)) return P25FE_ERR_ARG;
+    if (int frc = format_unusable(h, fmt)) return frc;
     if (do_main) h->sh.invalidate();
     if (n_hist < SHARD_HALO && n_hist != abs0) return P25FE_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -1748,6 +1819,7 @@ static int demod_host(p25fe_t* h, const void* iq, int fmt, size_t n, float* bb, 
                       float* power_dbm)
 {
     if (!h || (!iq && n) || !bb || !n_out) return P25FE_ERR_ARG;
+    if (int frc = format_unusable(h, fmt)) return frc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const size_t nb = p25fe_n_baseband_h(h, h->state.abs_iq, n);
     if (nb > bb_cap) return P25FE_ERR_CAPACITY;
@@ -1784,6 +1856,12 @@ int p25fe_demod_cf32(p25fe_t* h, const float* iq, size_t n_samples, float* bb, s
                      float* power_dbm)
 {
     return demod_host(h, iq, P25FE_FMT_CF32, n_samples, bb, bb_cap, n_out, power_dbm);
+}
+
+int p25fe_demod_s16(p25fe_t* h, const int16_t* iq, size_t n_samples, float* bb, size_t bb_cap, size_t* n_out,
+                    float* power_dbm)
+{
+    return demod_host(h, iq, P25FE_FMT_S16, n_samples, bb, bb_cap, n_out, power_dbm);
 }
 
 // Pinned outputs of one receiver call: per channel a result record, the carry-in anchor, a dibit row and (optionally) the
@@ -1944,6 +2022,7 @@ int p25fe_slice(p25fe_t* h, const float* bb, size_t n, uint8_t* dibits, size_t c
 static int run_host(p25fe_t* h, const void* iq, int fmt, size_t n, uint8_t* dibits, size_t cap, size_t* n_dibits)
 {
     if (!h || (!iq && n) || !dibits || !n_dibits || piecewise_refused(h)) return P25FE_ERR_ARG;
+    if (int frc = format_unusable(h, fmt)) return frc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const size_t C = (size_t)h->C;
     const size_t nb = p25fe_n_baseband_h(h, h->state.abs_iq, n);
@@ -2001,13 +2080,19 @@ int p25fe_run_cf32(p25fe_t* h, const float* iq, size_t n_samples, uint8_t* dibit
     return run_host(h, iq, P25FE_FMT_CF32, n_samples, dibits, cap, n_dibits);
 }
 
+int p25fe_run_s16(p25fe_t* h, const int16_t* iq, size_t n_samples, uint8_t* dibits, size_t cap, size_t* n_dibits)
+{
+    return run_host(h, iq, P25FE_FMT_S16, n_samples, dibits, cap, n_dibits);
+}
+
 // --------------------------------------------------------------------------------------------
 // a long host capture as a pipeline of windows: H2D copy | K1..K4 | dibits D2H, each on its own stream
 // --------------------------------------------------------------------------------------------
 int p25fe_run_host_windows(p25fe_t* h, const void* iq, int fmt, size_t n, size_t window, uint8_t* dibits, size_t cap,
                            size_t* n_dibits, p25fe_windows_stats_t* stats)
 {
-    if (!h || (!iq && n) || !dibits || !n_dibits || (fmt != P25FE_FMT_CF32 && fmt != P25FE_FMT_U8) || piecewise_refused(h)) return P25FE_ERR_ARG;
+    if (!h || (!iq && n) || !dibits || !n_dibits || piecewise_refused(h)) return P25FE_ERR_ARG;
+    if (int frc = format_unusable(h, fmt)) return frc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (h->state.format_refused(fmt)) return P25FE_ERR_FORMAT;
     const size_t C = (size_t)h->C, eb = fmt_bytes(fmt);

@@ -134,7 +134,15 @@ static_assert(SEG_HALO == seg_halo_for(BOX, TMAX) && seg_halo_for(TMAX, TMAX) >=
 #ifndef P25FE_K1_PRO_CF32
 #define P25FE_K1_PRO_CF32 0
 #endif
-__host__ __device__ constexpr bool seg_prologue(int fmt) { return fmt == P25FE_FMT_U8 || P25FE_K1_PRO_CF32 != 0; }
+#ifndef P25FE_K1_PRO_S16
+#define P25FE_K1_PRO_S16 1                   /* s16: u8's form (the kernel is expected to be issue-bound like u8's; docs/MEASUREMENTS.md) */
+#endif
+__host__ __device__ constexpr bool seg_prologue(int fmt)
+{
+    return fmt == P25FE_FMT_U8 ? true : (fmt == P25FE_FMT_S16 ? P25FE_K1_PRO_S16 != 0 : P25FE_K1_PRO_CF32 != 0);
+}
+// bytes per complex sample of an input format (docs/SPEC.md 3.1): cf32 8, s16 4, u8 2
+__host__ __device__ constexpr int fmt_bps(int fmt) { return fmt == P25FE_FMT_CF32 ? 8 : (fmt == P25FE_FMT_S16 ? 4 : 2); }
 
 // Polyphase ("planar") baseband layout of the fused path: with p = m + PLPAD (m = range-local baseband index, the
 // 240 history samples of the receiver at m = -240..-1), sample p belongs to plane r = p % 10 at symbol index i = p / 10.
@@ -443,6 +451,13 @@ __device__ __forceinline__ void phase_sync()
 // SPEC 3.1: rtlsdr_iq LUT value as arithmetic (src/demod.rs:82-84) -- the immediate-coefficient kernels; the generic
 // kernels (and a specialised build whose table is not affine) look the byte up in a 256-entry table in LDS
 __device__ __forceinline__ float u8_to_f32(unsigned b) { return __builtin_fmaf((float)b, K1_CT_U8_SCALE, K1_CT_U8_OFFSET); }
+// SPEC 3.1: one 32-bit word of an s16 stream = one complex sample, I in the low half.  (float)v * 2^-15 is exact for every
+// int16_t (16 significant bits, a power-of-two scale), so the result IS the cf32 sample a host conversion would have produced.
+__device__ __forceinline__ float2 s16_to_c32(unsigned w)
+{
+    const int i = (int)(short)(w & 0xffffu), q = (int)w >> 16;
+    return make_float2((float)i * P25FE_S16_SCALE, (float)q * P25FE_S16_SCALE);
+}
 
 // ------------------------------------------------------------------------------------------
 // window loader: global -> registers, one 16-B vector per lane per load.
@@ -459,13 +474,18 @@ __device__ __forceinline__ float u8_to_f32(unsigned b) { return __builtin_fmaf((
 #endif
 template <int FMT, int PK, int TX = 0, int NVX = 0> struct Loader {
     using G = Geo<PK, TX>;
-    // A lane's vector always holds TWO samples -- 16 B of cf32 or 4 B of u8 pairs -- which become one 16-B LDS store,
+    // A lane's vector always holds TWO samples -- 16 B of cf32, 8 B of s16 or 4 B of u8 pairs -- which become one 16-B LDS store,
     // lane-consecutive and therefore conflict-free.  (u8 used to load 16 B = 8 samples per lane: the 64-B lane stride of
     // the resulting ds_write_b128 is a 4-way bank conflict in every 8-lane group and cost 20 % of the kernel.)
     static constexpr int LOG_SPV = 1;
     static constexpr int SPV = 1 << LOG_SPV;
     static constexpr int NV = NVX ? NVX : (G::XWIN + SPV + SPV * WV - 1) / (SPV * WV);   // vectors per lane: 13 for PK = 5 (NVX: the segment prologue's short window)
-    using V = typename cond<FMT == P25FE_FMT_CF32, uint4, unsigned>::type;
+    // s16: two 32-bit words per lane (buffer_load_dwordx2: 26 VGPRs per window, between u8's 13 and cf32's 52).  Conversion
+    // per word, as the compiler emits it for gfx950: v_cvt_f32_i32_sdwa with a sign-extended WORD_0 / WORD_1 source select (the
+    // sign extension rides on the conversion: no v_bfe_i32 / v_ashrrev_i32), then ONE v_pk_mul_f32 by 2^-15 for the I / Q pair:
+    // 3 VALU instructions per sample (u8: 2 x v_cvt_f32_ubyteN + 2 x v_fma_f32 = 4).
+    static_assert(FMT == P25FE_FMT_CF32 || FMT == P25FE_FMT_S16 || FMT == P25FE_FMT_U8, "input format");
+    using V = typename cond<FMT == P25FE_FMT_CF32, uint4, typename cond<FMT == P25FE_FMT_S16, uint2, unsigned>::type>::type;
     V v[NV];
 
     // Window loads are BUFFER loads through one descriptor per segment: the hardware bounds check returns zeros for
@@ -479,8 +499,21 @@ template <int FMT, int PK, int TX = 0, int NVX = 0> struct Loader {
     // (An odd n_hist leaves one invalid sample inside the base vector: fixup() zeroes it, as it does every other sample
     // outside [-n_hist, n_new) that a straddling vector brought in.)
     typedef unsigned v4u_t __attribute__((ext_vector_type(4)));
-    static constexpr int BPS = FMT == P25FE_FMT_CF32 ? 8 : 2;       // bytes per sample
-    static constexpr int VB = BPS * SPV;                            // bytes per vector: 16 / 4
+    typedef unsigned v2u_t __attribute__((ext_vector_type(2)));
+    static constexpr int BPS = fmt_bps(FMT);                        // bytes per sample
+    static constexpr int VB = BPS * SPV;                            // bytes per vector: 16 / 8 / 4
+    __device__ __forceinline__ void load_vec(int j, int o)
+    {
+        if constexpr (FMT == P25FE_FMT_CF32) {
+            const v4u_t t = __builtin_amdgcn_raw_buffer_load_b128(rs, o, 0, P25FE_K1_LD_AUX);
+            v[j] = make_uint4(t.x, t.y, t.z, t.w);
+        } else if constexpr (FMT == P25FE_FMT_S16) {
+            const v2u_t t = __builtin_amdgcn_raw_buffer_load_b64(rs, o, 0, P25FE_K1_LD_AUX);
+            v[j] = make_uint2(t.x, t.y);
+        } else {
+            v[j] = __builtin_amdgcn_raw_buffer_load_b32(rs, o, 0, P25FE_K1_LD_AUX);
+        }
+    }
     __amdgpu_buffer_rsrc_t rs;
     long base_idx;                                                  // sample index of the descriptor base (uniform, vector aligned)
 
@@ -517,12 +550,7 @@ template <int FMT, int PK, int TX = 0, int NVX = 0> struct Loader {
         for (int j = 0; j < NV; ++j) {
             int o = voff + j * VB * WV;
             o = o < 0 ? 0x7ffffff0 : o;
-            if constexpr (FMT == P25FE_FMT_CF32) {
-                const v4u_t t = __builtin_amdgcn_raw_buffer_load_b128(rs, o, 0, P25FE_K1_LD_AUX);
-                v[j] = make_uint4(t.x, t.y, t.z, t.w);
-            } else {
-                v[j] = __builtin_amdgcn_raw_buffer_load_b32(rs, o, 0, P25FE_K1_LD_AUX);
-            }
+            load_vec(j, o);
         }
     }
     __device__ __forceinline__ void load(long first, int tid)        // first >= base_idx (every window but a segment's first)
@@ -534,12 +562,7 @@ template <int FMT, int PK, int TX = 0, int NVX = 0> struct Loader {
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             const int o = P25FE_M_LOAD_OFFSET(voff + j * VB * WV, VB * tid);
-            if constexpr (FMT == P25FE_FMT_CF32) {
-                const v4u_t t = __builtin_amdgcn_raw_buffer_load_b128(rs, o, 0, P25FE_K1_LD_AUX);
-                v[j] = make_uint4(t.x, t.y, t.z, t.w);
-            } else {
-                v[j] = __builtin_amdgcn_raw_buffer_load_b32(rs, o, 0, P25FE_K1_LD_AUX);
-            }
+            load_vec(j, o);
         }
     }
 
@@ -564,6 +587,8 @@ template <int FMT, int PK, int TX = 0, int NVX = 0> struct Loader {
                 if constexpr (FMT == P25FE_FMT_CF32) {
                     const unsigned w[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
                     s[e] = make_float2(__uint_as_float(w[2 * e]), __uint_as_float(w[2 * e + 1]));
+                } else if constexpr (FMT == P25FE_FMT_S16) {
+                    s[e] = s16_to_c32(e ? v[j].y : v[j].x);
                 } else {
                     const unsigned pair = (v[j] >> (16 * e)) & 0xffffu;
                     if constexpr (LUTM) s[e] = make_float2(lut[pair & 0xffu], lut[pair >> 8]);
@@ -653,6 +678,10 @@ struct K1Args {
 #ifndef P25FE_K1_PLANAR_WPS_U8
 #define P25FE_K1_PLANAR_WPS_U8 3
 #endif
+// s16 (prologue form): u8's bound, 148 VGPRs with one window in flight
+#ifndef P25FE_K1_PLANAR_WPS_S16
+#define P25FE_K1_PLANAR_WPS_S16 3
+#endif
 // Windows in flight per wave (register-staged loader).  Measured (tools/ab.sh, same box): a second register set costs
 // the cf32 kernel a wave per SIMD (181 VGPRs -> 8 waves per CU instead of 11) and makes it 25 % SLOWER (318 vs 254 us)
 // although 45 % more bytes are in flight -- the waves' arithmetic phases, not the bytes in flight, are what covers the
@@ -674,10 +703,18 @@ struct K1Args {
 #ifndef P25FE_K1_PF_U8
 #define P25FE_K1_PF_U8 2
 #endif
+#ifndef P25FE_K1_SUBS_S16
+#define P25FE_K1_SUBS_S16 9                  /* sub-tiles per segment (the host's choice, p25fe_api.hip: k1_plan) */
+#endif
+// s16: a window is 26 VGPRs.  Two in flight (u8's setting) come to 174 VGPRs = two waves per SIMD; bound to three waves the
+// allocator spills (168 VGPRs + 24 bytes of scratch), which no K1 kernel may.  One window: 148 VGPRs, three waves, no scratch.
+#ifndef P25FE_K1_PF_S16
+#define P25FE_K1_PF_S16 1
+#endif
 template <int FMT, bool CT, int PK, int OM = OUT_LINEAR, int TX = 0>
 __device__ __forceinline__ void frontend_body(const K1Args& a, const Taps* __restrict__ gtaps)
 {
-    constexpr int PF = (PK != 5 || TX != 0) ? 1 : (FMT == P25FE_FMT_U8 ? P25FE_K1_PF_U8 : P25FE_K1_PF_CF32);
+    constexpr int PF = (PK != 5 || TX != 0) ? 1 : (FMT == P25FE_FMT_U8 ? P25FE_K1_PF_U8 : (FMT == P25FE_FMT_S16 ? P25FE_K1_PF_S16 : P25FE_K1_PF_CF32));
 #ifndef P25FE_JIT
     static_assert(TX == 0 || !CT, "the 64-tap geometry is for caller-supplied taps");
 #endif
@@ -703,7 +740,7 @@ __device__ __forceinline__ void frontend_body(const K1Args& a, const Taps* __res
     float* const LUT = TAPS + (CT ? 0 : G::TAPS_N);                 // [256] u8 table, when LUTM
     float* const AVT = TAPS + (T1 + T2 + 3);                        // generic kernels: the post-discriminator taps
     // u8 -> float: arithmetic with immediate constants (CT, affine table) or a table in LDS (the generic kernels always:
-    // one code path for every table; a specialised build only when its table is not affine)
+    // one code path for every table; a specialised build only when its table is not affine).  cf32 and s16 have no table.
     constexpr bool LUTM = FMT == P25FE_FMT_U8 && (!CT || K1_CT_U8_LUT != 0);
     const int tid = threadIdx.x;
     if (!CT) {
@@ -713,7 +750,7 @@ __device__ __forceinline__ void frontend_body(const K1Args& a, const Taps* __res
     }
     if constexpr (LUTM)
         for (int k = tid; k < 256; k += WV) LUT[k] = gtaps->lut[k];
-    float* const FM = LUT + (FMT == P25FE_FMT_U8 && (!CT || K1_CT_U8_LUT != 0) ? 256 : 0);   // [T3 - 1 | SUB] fm window, when !AVG_DPP
+    float* const FM = LUT + (LUTM ? 256 : 0);   // [T3 - 1 | SUB] fm window, when !AVG_DPP
     float fm_gain = K1_CT_FM_GAIN;
     int n_avg = T3, avg_uniform = K1_CT_AVG_UNIFORM;               // run-time values of the generic kernels
     if constexpr (!CT) {
@@ -726,7 +763,7 @@ __device__ __forceinline__ void frontend_body(const K1Args& a, const Taps* __res
     auto tap_dec = [&](int k) -> float { return CT ? K1_CT_DECIM_TAPS[k] : TAPS[k]; };
     auto tap_ch = [&](int k) -> float { return CT ? K1_CT_CHAN_TAPS[k] : TAPS[T1 + k]; };
 
-    constexpr bool PRO = seg_prologue(FMT);                         // segment prologue (u8) or recomputed halo (cf32), see SEG_HALO
+    constexpr bool PRO = seg_prologue(FMT);                         // segment prologue (u8, s16) or recomputed halo (cf32), see SEG_HALO
     const long seg_len = PRO ? (long)a.subs_per_seg * SUB : (long)(SUB - SEGH) + (long)(a.subs_per_seg - 1) * SUB;
     // segment prologue: the ND decimator outputs in front of the segment, from a window of PWIN input samples
     constexpr int ND = HY + (T2 - 1);                               // 50 with the build's numbers
@@ -756,7 +793,7 @@ __device__ __forceinline__ void frontend_body(const K1Args& a, const Taps* __res
     const long m_seg0 = a.m_begin + (lead ? seg * LEAD_LEN : (long)a.lead_segs * LEAD_LEN + (seg - a.lead_segs) * seg_len);
     if (m_seg0 >= a.n_out) continue;
     const long m_seg1 = (m_seg0 + this_len < a.n_out) ? m_seg0 + this_len : a.n_out;
-    const char* xb = reinterpret_cast<const char*>(a.x) + (size_t)ch * a.ch_stride * (FMT == P25FE_FMT_CF32 ? 8 : 2);
+    const char* xb = reinterpret_cast<const char*>(a.x) + (size_t)ch * a.ch_stride * fmt_bps(FMT);
     float* bb = a.bb + (size_t)ch * a.bb_stride;
     phase_sync();                                                   // the previous item's LDS reads precede this item's writes
 
@@ -1224,8 +1261,9 @@ __device__ __forceinline__ void frontend_body(const K1Args& a, const Taps* __res
 // addresses and the table look-ups cost registers, and a spilled FIR loop costs far more than the occupancy)
 constexpr int k1_wps(int fmt, bool ct, int pk, int om)
 {
-    if (om == OUT_PLANAR) return fmt == P25FE_FMT_U8 ? (ct ? P25FE_K1_PLANAR_WPS_U8 : 2) : P25FE_K1_PLANAR_WPS;
-    return (fmt == P25FE_FMT_U8 && !ct && pk <= 3) ? 3 : (pk <= 3 ? 4 : 2);
+    if (om == OUT_PLANAR)
+        return fmt == P25FE_FMT_U8 ? (ct ? P25FE_K1_PLANAR_WPS_U8 : 2) : (fmt == P25FE_FMT_S16 ? (ct ? P25FE_K1_PLANAR_WPS_S16 : 2) : P25FE_K1_PLANAR_WPS);
+    return (fmt == P25FE_FMT_U8 && !ct && pk <= 3) ? 3 : (pk <= 3 ? 4 : 2);      // (s16 has no table to look up: cf32's bounds)
 }
 template <int FMT, bool CT, int PK, int OM = OUT_LINEAR, int TX = 0>
 __global__ __launch_bounds__(WV, k1_wps(FMT, CT, PK, OM)) void k_frontend(K1Args a, const Taps* __restrict__ gtaps)

@@ -362,7 +362,7 @@ static int exact_offsets_wait(p25fe_shard_t* s)
 struct StepStreams { hipStream_t st, rx, rx2; bool halo_on_st; };
 static bool step_args_ok(const void* d_buf, int fmt, const void* d_dibits, const void* d_result, int gather)
 {
-    return d_buf && d_dibits && d_result && (fmt == P25FE_FMT_CF32 || fmt == P25FE_FMT_U8) && gather >= P25FE_GATHER_NONE &&
+    return d_buf && d_dibits && d_result && (fmt == P25FE_FMT_CF32 || fmt == P25FE_FMT_U8 || fmt == P25FE_FMT_S16) && gather >= P25FE_GATHER_NONE &&
            gather <= P25FE_GATHER_ROOT_EXACT;
 }
 static int shard_step_impl(p25fe_shard_t* s, void* d_buf, int fmt, uint8_t* d_dibits, p25fe_result_t* d_result, int gather,
@@ -370,7 +370,7 @@ static int shard_step_impl(p25fe_shard_t* s, void* d_buf, int fmt, uint8_t* d_di
 {
     const hipStream_t st = ss.st, rx = ss.rx;
     if (!s || !step_args_ok(d_buf, fmt, d_dibits, d_result, gather)) return P25FE_ERR_ARG;
-    const size_t eb = fmt == P25FE_FMT_CF32 ? 8 : 2;
+    const size_t eb = fmt == P25FE_FMT_CF32 ? 8 : (fmt == P25FE_FMT_S16 ? 4 : 2);   // bytes per sample: the halo is s->halo of them
     char* buf = static_cast<char*>(d_buf);
     char* owned = buf + s->halo * eb;
     const size_t n_hist = s->rank > 0 ? s->halo : 0;

@@ -1,10 +1,12 @@
 """Python mirror of demod::DemodTask (src/demod.rs:25-120) over the C ABI.
 
-Same wiring as the reference: a reader channel of u8 I/Q chunks in, baseband chunks out on the
+Same wiring as the reference: a reader channel of u8 I/Q chunks in (or, from a 16-bit tuner, NumPy int16 arrays: FMT_S16), baseband chunks out on the
 receiver channel, signal power to the hub every 4th chunk.  Channels are anything with get()/put()
 (queue.Queue); `None` on the reader channel ends run() (the reference loops until the process dies).
 All arithmetic happens in libp25fe.so on the GPU.
 """
+import numpy as np
+
 from .consts import BUF_BYTES
 from .frontend import FrontEnd
 
@@ -67,10 +69,12 @@ class DemodTask:
             if data is None:
                 return
             assert len(data) % 2 == 0 and len(data) <= BUF_BYTES * 64
+            # the chunk's type names its format: bytes / uint8 -> u8 (the reference's reader), an int16 array -> s16
+            demod = self.fe.demod_s16 if getattr(data, "dtype", None) == np.int16 else self.fe.demod_u8
             want = notifier.throttle()                            # :95
             if want:
-                bb, power = self.fe.demod_u8(data, want_power=True)     # :74-93, 97, 109-114
+                bb, power = demod(data, want_power=True)          # :74-93, 97, 109-114
                 self.hub.put(HubEvent.UpdateSignalPower(power))   # :99
             else:
-                bb = self.fe.demod_u8(data)
+                bb = demod(data)
             self.chan.put(RecvEvent.Baseband(bb))                 # :116

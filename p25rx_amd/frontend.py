@@ -10,12 +10,25 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import FMT_CF32, FMT_U8, RESULT_DTYPE, ANCHOR_DTYPE
+from ._lib import FMT_CF32, FMT_U8, FMT_S16, RESULT_DTYPE, ANCHOR_DTYPE
 CHZ_CHANNELS = 192                  # P25FE_CHZ_CHANNELS (include/p25fe_spec.h)
 
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def fmt_bytes(fmt):
+    """bytes per complex sample of an input format: what a sample offset into an IQ buffer is multiplied by"""
+    return {FMT_CF32: 8, FMT_S16: 4, FMT_U8: 2}[fmt]
+
+
+def _torch_fmt(dtype):
+    import torch
+    try:
+        return {torch.float32: FMT_CF32, torch.uint8: FMT_U8, torch.int16: FMT_S16}[dtype]
+    except KeyError:
+        raise TypeError("IQ tensor must be float32, int16 or uint8") from None
 
 
 class FrontEnd:
@@ -41,6 +54,14 @@ class FrontEnd:
     def kernel_variant(self):
         """0: the library's own immediate-coefficient kernels, 1: kernels specialised for this handle's numbers, 2: generic"""
         return int(self.L.p25fe_kernel_variant(self.h))
+
+    def format_variant(self, fmt):
+        """the same for one input format (p25fe_format_variant): s16 has no specialised kernels and runs the generic ones on
+        a handle whose numbers are not the build's; raises P25feError(ERR_JIT) where the handle requires specialised ones"""
+        rc = int(self.L.p25fe_format_variant(self.h, int(fmt)))
+        if rc < 0:
+            self._chk(rc)
+        return rc
 
     def close(self):
         if getattr(self, "h", None):
@@ -74,6 +95,11 @@ class FrontEnd:
         iq = np.ascontiguousarray(iq, dtype=np.complex64).reshape(self.C, -1)
         return self._demod(self.L.p25fe_demod_cf32, iq, iq.shape[1], iq.shape[1], want_power)
 
+    def demod_s16(self, iq, want_power=False):
+        """the same on interleaved int16 I/Q (FMT_S16); iq shape [2 n] / [n, 2] or [C, ...]"""
+        iq = np.ascontiguousarray(iq, dtype=np.int16).reshape(self.C, -1)
+        return self._demod(self.L.p25fe_demod_s16, iq, iq.shape[1] // 2, iq.shape[1] // 2, want_power)
+
     def slice(self, bb, sync_cap=None):
         """RecvTask sample loop on baseband; returns (dibits, sync_pos, sync_dibit) (lists per channel if C > 1)."""
         bb = np.ascontiguousarray(bb, dtype=np.float32).reshape(self.C, -1)
@@ -106,23 +132,27 @@ class FrontEnd:
         iq = np.ascontiguousarray(iq, dtype=np.complex64).reshape(self.C, -1)
         return self._run(self.L.p25fe_run_cf32, iq, iq.shape[1], iq.shape[1])
 
+    def run_s16(self, iq):
+        iq = np.ascontiguousarray(iq, dtype=np.int16).reshape(self.C, -1)
+        return self._run(self.L.p25fe_run_s16, iq, iq.shape[1] // 2, iq.shape[1] // 2)
+
     def run_host_windows(self, iq, window=0, fmt=None):
         """p25fe_run_host_windows: a LONG host capture through the path as a pipeline of windows (H2D copy | kernels | dibits
         back).  iq: numpy array (pageable: staged by the library) or a CPU torch tensor (pinned: copied from directly) --
-        complex64 / float32 pairs (cf32) or uint8 pairs (u8), [n] or [C, n].  Returns (dibits per channel, stats dict)."""
+        complex64 / float32 pairs (cf32), int16 pairs (s16) or uint8 pairs (u8), [n] or [C, n].  Returns (dibits per channel, stats dict)."""
         if hasattr(iq, "data_ptr"):                                  # torch CPU tensor (possibly pinned)
             import torch
             assert not iq.is_cuda and iq.is_contiguous()
-            is_u8 = iq.dtype == torch.uint8
+            by_type = FMT_U8 if iq.dtype == torch.uint8 else (FMT_S16 if iq.dtype == torch.int16 else FMT_CF32)
             n_el = iq.numel() // self.C
             n = n_el // 2
             ptr = C.c_void_p(iq.data_ptr())
         else:
-            is_u8 = iq.dtype == np.uint8
-            iq = np.ascontiguousarray(iq if is_u8 else iq.view(np.float32) if iq.dtype == np.complex64 else iq.astype(np.float32))
+            by_type = FMT_U8 if iq.dtype == np.uint8 else (FMT_S16 if iq.dtype == np.int16 else FMT_CF32)
+            iq = np.ascontiguousarray(iq if by_type != FMT_CF32 else iq.view(np.float32) if iq.dtype == np.complex64 else iq.astype(np.float32))
             n = iq.size // self.C // 2
             ptr = _p(iq)
-        fmt = (FMT_U8 if is_u8 else FMT_CF32) if fmt is None else fmt
+        fmt = by_type if fmt is None else fmt
         cap = n // 30 + 4
         dib = np.empty((self.C, cap), dtype=np.uint8)
         nd = (C.c_size_t * self.C)()
@@ -174,11 +204,7 @@ class FrontEnd:
     @staticmethod
     def _fmt_of(t):
         import torch
-        if t.dtype == torch.float32:
-            return FMT_CF32, t.shape[-2] if t.dim() == 3 else t.shape[0]
-        if t.dtype == torch.uint8:
-            return FMT_U8, t.shape[-2] if t.dim() == 3 else t.shape[0]
-        raise TypeError("IQ tensor must be float32 [C, n, 2] or uint8 [C, n, 2]")
+        return _torch_fmt(t.dtype), t.shape[-2] if t.dim() == 3 else t.shape[0]
 
     def _iq_view(self, iq):
         """iq: [n, 2] or [C, n, 2] contiguous per channel; returns (fmt, n, ch_stride)."""
@@ -187,9 +213,7 @@ class FrontEnd:
         if iq.dim() == 2:
             iq = iq.unsqueeze(0)
         assert iq.shape[0] == self.C and iq.stride(2) == 1 and iq.stride(1) == 2
-        fmt = FMT_CF32 if iq.dtype == torch.float32 else FMT_U8
-        if iq.dtype not in (torch.float32, torch.uint8):
-            raise TypeError("IQ tensor must be float32 or uint8")
+        fmt = _torch_fmt(iq.dtype)
         return fmt, iq.shape[1], (iq.stride(0) // 2 if self.C > 1 else iq.shape[1])
 
     @staticmethod
@@ -244,7 +268,7 @@ class FrontEnd:
         if bb is None:
             bb = torch.empty((self.C, (nb + 7) // 4 * 4), dtype=torch.float32, device=iq.device)
         pw = torch.empty(self.C, dtype=torch.float32, device=iq.device) if want_power else None
-        ptr = iq.data_ptr() + offset * (8 if fmt == FMT_CF32 else 2)
+        ptr = iq.data_ptr() + offset * fmt_bytes(fmt)
         self._chk(self.L.p25fe_demod_dev(self.h, C.c_void_p(ptr), fmt, stride, n_hist, n, abs0,
                                          C.c_void_p(bb.data_ptr()), bb.stride(0),
                                          C.c_void_p(pw.data_ptr()) if want_power else None, self._stream()))
@@ -356,7 +380,7 @@ class FrontEnd:
         n = n_total - offset
         if result is None:
             result = torch.empty((self.C, RESULT_DTYPE.itemsize), dtype=torch.uint8, device=iq.device)
-        ptr = iq.data_ptr() + offset * (8 if fmt == FMT_CF32 else 2)
+        ptr = iq.data_ptr() + offset * fmt_bytes(fmt)
         self._chk(self.L.p25fe_shard_pass1(self.h, C.c_void_p(ptr), fmt, stride, n_hist, n, abs0,
                                            C.c_void_p(result.data_ptr()), self._stream()))
         return result
@@ -364,7 +388,7 @@ class FrontEnd:
     def shard_pass1_main(self, iq, offset, n_hist, abs0):
         """K1 over everything that does not need the left halo (may run while the halo is still on the wire)."""
         fmt, n_total, stride = self._iq_view(iq)
-        ptr = iq.data_ptr() + offset * (8 if fmt == FMT_CF32 else 2)
+        ptr = iq.data_ptr() + offset * fmt_bytes(fmt)
         self._chk(self.L.p25fe_shard_pass1_main(self.h, C.c_void_p(ptr), fmt, stride, n_hist, n_total - offset, abs0,
                                                 self._stream()))
 
@@ -374,7 +398,7 @@ class FrontEnd:
         fmt, n_total, stride = self._iq_view(iq)
         if result is None:
             result = torch.empty((self.C, RESULT_DTYPE.itemsize), dtype=torch.uint8, device=iq.device)
-        ptr = iq.data_ptr() + offset * (8 if fmt == FMT_CF32 else 2)
+        ptr = iq.data_ptr() + offset * fmt_bytes(fmt)
         self._chk(self.L.p25fe_shard_pass1_finish(self.h, C.c_void_p(ptr), fmt, stride, n_hist, n_total - offset, abs0,
                                                   C.c_void_p(result.data_ptr()), self._stream()))
         return result
@@ -382,7 +406,7 @@ class FrontEnd:
     def shard_pass1_head(self, iq, offset, n_hist, abs0):
         """The shard's head segment alone (needs the halo); may run on another stream beside shard_pass1_main's launch."""
         fmt, n_total, stride = self._iq_view(iq)
-        ptr = iq.data_ptr() + offset * (8 if fmt == FMT_CF32 else 2)
+        ptr = iq.data_ptr() + offset * fmt_bytes(fmt)
         self._chk(self.L.p25fe_shard_pass1_head(self.h, C.c_void_p(ptr), fmt, stride, n_hist, n_total - offset, abs0,
                                                 self._stream()))
 
@@ -405,7 +429,7 @@ class FrontEnd:
     def shard_pass1_k1(self, iq, offset, n_hist, abs0):
         """The whole front end of pass 1 (main + head) in one launch; shard_pass1_finish then runs detection + scan only."""
         fmt, n_total, stride = self._iq_view(iq)
-        ptr = iq.data_ptr() + offset * (8 if fmt == FMT_CF32 else 2)
+        ptr = iq.data_ptr() + offset * fmt_bytes(fmt)
         self._chk(self.L.p25fe_shard_pass1_k1(self.h, C.c_void_p(ptr), fmt, stride, n_hist, n_total - offset, abs0, self._stream()))
 
     def streams_share_queue(self, a, b):

@@ -49,27 +49,36 @@ private:
     p25fe_t* h_ = nullptr;
 };
 
+// one chunk through stages 1-5, by the chunk's sample type: uint8_t pairs (the reference's reader) or int16_t pairs (P25FE_FMT_S16)
+inline int demod_chunk(p25fe_t* h, const std::vector<uint8_t>& iq, float* bb, size_t cap, size_t* n_out, float* power)
+{
+    return p25fe_demod_u8(h, iq.data(), iq.size(), bb, cap, n_out, power);
+}
+inline int demod_chunk(p25fe_t* h, const std::vector<int16_t>& iq, float* bb, size_t cap, size_t* n_out, float* power)
+{
+    return p25fe_demod_s16(h, iq.data(), iq.size() / 2, bb, cap, n_out, power);
+}
+
 struct HubEvent { float signal_power_dbm; };                         // HubEvent::UpdateSignalPower, src/hub.rs:455
 struct StatsEvent { uint64_t dibits, syncs; };                       // HubEvent::UpdateStats (src/recv.rs:162-165): what exists of Stats here
 struct Baseband { std::vector<float> samples; };                     // RecvEvent::Baseband, src/recv.rs:25
 
-// demod::DemodTask (src/demod.rs:25-120)
-template <class Reader, class Hub, class Chan> class DemodTask {
+// demod::DemodTask (src/demod.rs:25-120).  Sample: what the reader's chunks hold -- uint8_t (the reference) or int16_t.
+template <class Reader, class Hub, class Chan, class Sample = uint8_t> class DemodTask {
 public:
     DemodTask(Handle& h, Reader& reader, Hub& hub, Chan& chan) : h_(h), reader_(reader), hub_(hub), chan_(chan) {}
 
     // DemodTask::run (src/demod.rs:62-119); returns when the reader channel closes.
     void run()
     {
-        std::vector<uint8_t> bytes;
+        std::vector<Sample> bytes;
         while (reader_.recv(bytes)) {                                 // :70
             Baseband bb;
             bb.samples.resize(bytes.size() / 2 / 5 + 2);
             size_t n_out = 0;
             float power = 0.f;
             const bool want = (++notifier_ % 4) == 0;                 // :95
-            expect(p25fe_demod_u8(h_.get(), bytes.data(), bytes.size(), bb.samples.data(), bb.samples.size(), &n_out,
-                                  want ? &power : nullptr),
+            expect(demod_chunk(h_.get(), bytes, bb.samples.data(), bb.samples.size(), &n_out, want ? &power : nullptr),
                    "unable to demodulate");                           // :74-93, 97, 109-114
             bb.samples.resize(n_out);
             if (want) hub_.send(HubEvent{power});                     // :99

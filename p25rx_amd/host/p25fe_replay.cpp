@@ -1,10 +1,11 @@
 // p25fe_replay -- file-in / file-out driver in the role of the reference's command line for this path
 // (src/main.rs:95-102, 162-175, 278-283 and src/replay.rs:26-57): a deterministic harness for the hot path.
 //
-//   p25fe_replay [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] u8|cf32|bb <in> <dibits.out>
-//   p25fe_replay -W WINDOW_BYTES u8|cf32 <in> <dibits.out>
+//   p25fe_replay [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] u8|s16|cf32|bb <in> <dibits.out>
+//   p25fe_replay -W WINDOW_BYTES u8|s16|cf32 <in> <dibits.out>
 //
 //     u8    RTL-SDR style interleaved u8 I/Q, the reference's live input (src/consts.rs:6: 32768-byte chunks)
+//     s16   interleaved little-endian int16 I/Q at 240 ksps (Airspy, SDRplay, USRP sc16, SigMF ci16_le), 16384 samples per chunk
 //     cf32  Complex32 I/Q at 240 ksps
 //     bb    48 kHz f32le baseband: what `p25rx -w FILE` records and `p25rx -r FILE` replays (src/main.rs:95-102)
 //
@@ -94,16 +95,16 @@ struct Sink {
 
 static int usage(const char* argv0)
 {
-    std::fprintf(stderr, "usage: %s [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] u8|cf32|bb <in> <dibits.out>\n"
-                         "       %s -W WINDOW_BYTES u8|cf32 <in> <dibits.out>\n", argv0, argv0);
+    std::fprintf(stderr, "usage: %s [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] u8|s16|cf32|bb <in> <dibits.out>\n"
+                         "       %s -W WINDOW_BYTES u8|s16|cf32 <in> <dibits.out>\n", argv0, argv0);
     return 2;
 }
 
 // bulk mode: reader thread -> two pinned blocks -> p25fe_run_host_windows
 static int bulk(Handle& h, const std::string& mode, std::ifstream& in, const char* out_path, size_t window_bytes)
 {
-    const int fmt = mode == "u8" ? P25FE_FMT_U8 : P25FE_FMT_CF32;
-    const size_t eb = fmt == P25FE_FMT_U8 ? 2 : 8;
+    const int fmt = mode == "u8" ? P25FE_FMT_U8 : (mode == "s16" ? P25FE_FMT_S16 : P25FE_FMT_CF32);
+    const size_t eb = fmt == P25FE_FMT_U8 ? 2 : (fmt == P25FE_FMT_S16 ? 4 : 8);
     const size_t window = window_bytes / eb / 8 * 8;
     if (window < 8192) { std::fprintf(stderr, "window too small\n"); return 2; }
     const size_t block = 8 * window;                                  // samples per pinned block: the reader fills one while the library pipelines the other
@@ -195,7 +196,7 @@ int main(int argc, char** argv)
     if (!in) { std::fprintf(stderr, "unable to open %s\n", argv[a + 1]); return 1; }
     Handle h(0, 1);
     if (window_bytes) {
-        if (wpath || jpath || (mode != "u8" && mode != "cf32")) return usage(argv[0]);
+        if (wpath || jpath || (mode != "u8" && mode != "s16" && mode != "cf32")) return usage(argv[0]);
         return bulk(h, mode, in, argv[a + 2], window_bytes);
     }
     Chan<std::vector<uint8_t>> reader;
@@ -221,6 +222,16 @@ int main(int argc, char** argv)
         while (in.read(reinterpret_cast<char*>(buf.data()), (std::streamsize)buf.size()) || in.gcount() > 0) {
             std::vector<uint8_t> chunk(buf.begin(), buf.begin() + (in.gcount() & ~std::streamsize(1)));
             reader.send(std::move(chunk));
+            demod.run();
+            recv.run(dump, hub);
+        }
+    } else if (mode == "s16") {
+        Chan<std::vector<int16_t>> reader16;
+        std::vector<int16_t> buf(2 * BUF_SAMPLES * batch);
+        DemodTask<Chan<std::vector<int16_t>>, Hub, Chan<Baseband>, int16_t> demod(h, reader16, hub, chan);
+        while (in.read(reinterpret_cast<char*>(buf.data()), (std::streamsize)(buf.size() * 2)) || in.gcount() > 0) {
+            std::vector<int16_t> chunk(buf.begin(), buf.begin() + (in.gcount() / 4) * 2);      // whole complex samples
+            reader16.send(std::move(chunk));
             demod.run();
             recv.run(dump, hub);
         }
