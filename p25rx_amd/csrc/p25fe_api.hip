@@ -861,7 +861,6 @@ static int k1_plan(const p25fe_t* h, const K1Launch& L, K1Plan* p)
     // 3 sub-tiles; A/B on one box, three rounds: 2 -> 0.275, 3 -> 0.264, 4 -> 0.269 ms).  P25FE_SUBS overrides.
     const int pk = (L.planar || h->long_taps || variant == P25FE_VARIANT_SPECIALIZED) ? 5 : h->k1_p;
     const int t1 = h->long_taps ? TMAX : T1;
-    const long sub = (long)WV * pk;
     static const long subs_env = [] { const char* e = getenv("P25FE_SUBS"); return e ? atol(e) : 0L; }();
     // (round 2: the instruction-bound u8 kernel prefers longer segments -- less halo recomputed: 3 -> 239, 6 -> 231 us on one
     // box; with the final build 4 -> 222 / 216, 6 -> 217 / 215, 9 -> 212 / 209, 12 -> 216 / 205 us under rocprofv3)
@@ -875,34 +874,23 @@ static int k1_plan(const p25fe_t* h, const K1Launch& L, K1Plan* p)
     const bool ct = variant != P25FE_VARIANT_GENERIC;
     const int t2e = h->long_taps ? TMAX : T2;
     const int t3geo = ct ? h->n_avg : TMAX;
-    const long segh = seg_halo_for(h->n_avg, t2e);
-    const long seg_len = pro ? subs * sub : (sub - segh) + (subs - 1) * sub;
-    // what a segment needs in front of its first output: the prologue's decimator outputs, or the recomputed halo
-    const long nd = pro ? t3geo + t2e - 1 : segh;
-    // a time shard's launches (part != K1_ALL): the segments in front of the first one whose input lies inside the owned samples
-    // are ONE sub-tile long (K1Args.lead_segs) -- the head is then a few one-sub-tile workgroups side by side
-    const long lead_len = pro ? sub : sub - segh;
+    SegGeo g{pro, WV * pk, (int)subs, seg_halo_for(h->n_avg, t2e), 0, m_begin, (long)n_out};      // p25fe_kernels.hip: the kernel's own geometry
+    const int nd = g.front(t3geo, t2e);
     const long o0 = (long)(((uint64_t)h->phase + 5 - L.abs0 % 5) % 5);
-    long lead = 0;
-    if (L.part && subs > 1 && !L.chunk)
-        while (lead < 64 && o0 + DEC * (m_begin + lead * lead_len - nd) - (t1 - 1) < 0 && lead * lead_len < total) ++lead;
-    auto seg_start = [&](long k) { return k < lead ? m_begin + k * lead_len : m_begin + lead * lead_len + (k - lead) * seg_len; };
-    const long n_seg = lead * lead_len >= total ? (total + lead_len - 1) / lead_len : lead + (total - lead * lead_len + seg_len - 1) / seg_len;
+    if (L.part && subs > 1 && !L.chunk) g.set_lead(nd, o0, t1);    // a time shard's launches (part != K1_ALL)
+    const long n_seg = g.count(total);
     const long pl_shift = PLPAD + h->look;       // the general receiver sees the range h->look samples late (p25fe_recv.hip)
-    if (L.planar && pro && (m_begin + pl_shift < 0 || (m_begin + pl_shift) % PL_BLK != 0 || seg_len % PL_BLK != 0)) return P25FE_ERR_ARG;
     // (halo form: the outputs a segment recomputes and drops may lie in front of planar position 0 -- with a 160-output halo the
     // range's first segment starts 80 positions in front of it; they are never stored, only whole bytes of the planes are)
-    if (L.planar && !pro && (m_begin + pl_shift < 0 || (m_begin + pl_shift) % 80 != 0 || seg_len % 80 != 0)) return P25FE_ERR_ARG;
+    if (L.planar && !g.planar_ok(pl_shift)) return P25FE_ERR_ARG;
     if (L.planar && n_out > MAX_RANGE_BB) return P25FE_ERR_ARG;
     long seg_first = 0, seg_count = n_seg;
     if (L.part) {
         if (L.power_dbm) return P25FE_ERR_ARG;
-        // segment k reads input from o0 + 5 (its first output - nd) - (T1 - 1) on
-        long k_min = 0;
-        while (k_min < n_seg && o0 + DEC * (seg_start(k_min) - nd) - (t1 - 1) < 0) ++k_min;
+        const long k_min = g.head_count(n_seg, nd, o0, t1);
         if (L.part == K1_MAIN) { seg_first = k_min; seg_count = n_seg - k_min; }
         else seg_count = k_min;
-        p->head_end = seg_start(k_min) - m_begin;
+        p->head_end = g.start(k_min) - m_begin;
         p->empty = seg_count <= 0;
         if (p->empty) return P25FE_OK;
     }
@@ -910,7 +898,7 @@ static int k1_plan(const p25fe_t* h, const K1Launch& L, K1Plan* p)
     p->fmt = fmt; p->variant = variant; p->ct = ct; p->pk = pk; p->n_seg = n_seg;
     a.x = L.src; a.ch_stride = (long)L.ch_stride; a.n_hist = (long)L.n_hist; a.n_new = (long)L.n; a.o0 = (int)o0; a.n_ch = h->C;
     a.bb = L.bb; a.bb_stride = (long)L.bb_stride; a.power_partial = nullptr;
-    a.subs_per_seg = (int)subs; a.seg_first = (int)seg_first; a.seg_count = (int)seg_count; a.lead_segs = (int)lead; a.seg_halo = (int)segh;
+    a.subs_per_seg = g.subs_per_seg; a.seg_first = (int)seg_first; a.seg_count = (int)seg_count; a.lead_segs = g.lead_segs; a.seg_halo = g.segh;
     a.bbp = nullptr; a.bbp_ch_stride = 0; a.bits = nullptr; a.bits_ch_stride = 0; a.pl_shift = (int)pl_shift;
     a.done_flag = L.planar ? L.done_flag : nullptr; a.done_seq = L.done_seq;
     if (L.planar) {

@@ -157,6 +157,58 @@ static_assert(PLPAD % 320 == 0 && PLPAD >= 240 + 2, "planar pad holds the receiv
 constexpr int OUT_LINEAR = 0, OUT_PLANAR = 1;
 constexpr int PL_BLK = 32 * P25FE_SPS;       // floats per block
 __host__ __device__ inline long planar_index(long i, int r) { return (i >> 5) * PL_BLK + r * 32 + (i & 31); }
+
+// The segments of one K1 range [m_begin, n_out), ONCE: the host's planner (p25fe_api.hip: k1_plan) writes these numbers into
+// K1Args, frontend_body reads them back, and both ask the same members (walked on the CPU: tests/native/k1_geometry_driver.cpp).
+// Segment k is an absolute index into the range; the first lead_segs of them are ONE sub-tile long: a time shard's head -- the
+// outputs that depend on the halo, launched on their own after it has arrived -- is then two or three one-sub-tile workgroups
+// side by side (~6 us) instead of one workgroup walking a whole segment alone (15 - 45 us).
+#define K1_GEO_FN __host__ __device__ __forceinline__ constexpr
+// first input sample of a window whose first decimator output is m (o0: K1Args.o0, t1: the decimator's taps).  frontend_body
+// uses the macro itself: its instruction stream depends on the simplifier meeting this sum before any inlining.
+#define K1_FIRST_INPUT(m, o0, t1) ((long)(o0) + DEC * (m) - ((t1) - 1))
+struct SegGeo {
+    bool pro;               // prologue form (seg_prologue) or halo form
+    int sub, subs_per_seg;  // outputs a sub-tile computes (64 x PK); sub-tiles of a segment
+    int segh;               // halo form: the outputs a segment's first sub-tile recomputes and drops (seg_halo_for)
+    int lead_segs;
+    long m_begin, n_out;
+    // (not to be given: the lengths of a whole segment and of a lead one, worked out once, where the struct is built)
+    long seg_len_ = pro ? (long)subs_per_seg * sub : (long)(sub - segh) + (long)(subs_per_seg - 1) * sub;
+    long lead_len_ = pro ? (long)sub : (long)(sub - segh);
+    K1_GEO_FN long seg_len() const { return seg_len_; }
+    K1_GEO_FN long lead_len() const { return lead_len_; }
+    // the same segments over a range of its own
+    K1_GEO_FN SegGeo range(int lead, long mb, long no) const { SegGeo g = *this; g.lead_segs = lead; g.m_begin = mb; g.n_out = no; return g; }
+    K1_GEO_FN bool is_lead(long k) const { return k < (long)lead_segs; }
+    K1_GEO_FN long len(long k) const { return is_lead(k) ? lead_len_ : seg_len_; }
+    K1_GEO_FN int subs(long k) const { return is_lead(k) ? 1 : subs_per_seg; }
+    K1_GEO_FN long start(long k) const { return m_begin + (is_lead(k) ? k * lead_len_ : (long)lead_segs * lead_len_ + (k - lead_segs) * seg_len_); }
+    K1_GEO_FN long end_of(long m0, long len_) const { return (m0 + len_ < n_out) ? m0 + len_ : n_out; }   // clipped to the range
+    K1_GEO_FN long end(long k) const { return end_of(start(k), len(k)); }
+    K1_GEO_FN long count(long total) const                          // segments of a range of `total` outputs
+    {
+        return lead_segs * lead_len_ >= total ? (total + lead_len_ - 1) / lead_len_ : lead_segs + (total - lead_segs * lead_len_ + seg_len_ - 1) / seg_len_;
+    }
+    // what a segment needs in front of its first output: the prologue's decimator outputs (t3geo = the post-discriminator filter's
+    // length as far as the kernel's geometry goes, t2 = the channel filter's), or the recomputed halo's outputs
+    K1_GEO_FN int front(int t3geo, int t2) const { return pro ? t3geo + t2 - 1 : segh; }
+    K1_GEO_FN static long first_input(long m, long o0, int t1) { return K1_FIRST_INPUT(m, o0, t1); }
+    // segment k reads input in front of the owned samples: a time shard launches it once the halo has arrived (HEAD); they are
+    // the first head_count() of the range's n_seg segments, MAIN is the rest
+    K1_GEO_FN bool in_head(long k, int front_, long o0, int t1) const { return first_input(start(k) - front_, o0, t1) < 0; }
+    K1_GEO_FN long head_count(long n_seg, int front_, long o0, int t1) const { long k = 0; while (k < n_seg && in_head(k, front_, o0, t1)) ++k; return k; }
+    // a time shard's lead_segs: the segments in front of the first one whose input lies inside the owned samples
+    K1_GEO_FN void set_lead(int front_, long o0, int t1) { for (lead_segs = 0; lead_segs < 64 && start(lead_segs) < n_out && in_head(lead_segs, front_, o0, t1);) ++lead_segs; }
+    // the planar epilogue's stores (K1Args.bbp): with m_begin + pl_shift >= 0 and a multiple of 320 every sub-tile of the prologue
+    // form is one block of the layout; the halo form needs a multiple of 80 and a segment length that is one: whole sign bytes
+    K1_GEO_FN bool planar_ok(long pl_shift) const
+    {
+        const long g = pro ? PL_BLK : 80;
+        return m_begin + pl_shift >= 0 && (m_begin + pl_shift) % g == 0 && seg_len_ % g == 0;
+    }
+};
+#undef K1_GEO_FN
 // history (input samples before the first owned one) needed for exact results
 constexpr int HIST_IQ = DEC * HALO_D + (T1 - 1) + (DEC - 1);   // 284
 constexpr int HIST_IQ_MAX = DEC * (TMAX + TMAX - 1) + (TMAX - 1) + (DEC - 1);   // 702 with 64 + 64 + 64 taps
@@ -644,9 +696,7 @@ struct K1Args {
     int seg_first;          // first segment of this launch (a shard's head segment is launched after its halo has arrived)
     long m_begin;           // first output to produce (<= 0: also outputs that lie in the history)
     float* power_partial;   // nullable: [n_channels][seg_count] partial sums of |y|^2
-    // OUT_PLANAR only (bb unused): polyphase baseband + sign planes, see PLPAD.  Prologue form: m_begin + pl_shift >= 0 and a
-    // multiple of 320 (every sub-tile is one block of the layout); halo form: m_begin + pl_shift >= 0, a multiple
-    // of 80, and a segment length that is a multiple of 80.
+    // OUT_PLANAR only (bb unused): polyphase baseband + sign planes, see PLPAD; the range is aligned as SegGeo::planar_ok says
     float* bbp;             // channel 0
     long bbp_ch_stride;     // floats per channel (a whole number of blocks)
     uint8_t* bits;          // channel 0, addressed by byte
@@ -658,10 +708,7 @@ struct K1Args {
     // the sync detection that reads its planes: the detection's first tile polls this word (p25fe_recv.hip, k_detect).
     unsigned* done_flag;
     unsigned done_seq;
-    // The first lead_segs segments of the range are ONE sub-tile long (the rest subs_per_seg): a time shard's head -- the
-    // outputs that depend on the halo, launched on their own after it has arrived -- is then two or three one-sub-tile
-    // workgroups side by side (~6 us) instead of one workgroup walking a whole segment alone (15 - 45 us).
-    int lead_segs;
+    int lead_segs;          // the first lead_segs segments of the range are ONE sub-tile long (the rest subs_per_seg): SegGeo
     int seg_halo;           // generic kernels, halo form: outputs a segment recomputes in front of its first one (seg_halo_for; the
                             // immediate-coefficient kernels know theirs at compile time)
 };
@@ -764,9 +811,9 @@ __device__ __forceinline__ void frontend_body(const K1Args& a, const Taps* __res
     auto tap_ch = [&](int k) -> float { return CT ? K1_CT_CHAN_TAPS[k] : TAPS[T1 + k]; };
 
     constexpr bool PRO = seg_prologue(FMT);                         // segment prologue (u8, s16) or recomputed halo (cf32), see SEG_HALO
-    const long seg_len = PRO ? (long)a.subs_per_seg * SUB : (long)(SUB - SEGH) + (long)(a.subs_per_seg - 1) * SUB;
+    const SegGeo shape{PRO, SUB, a.subs_per_seg, SEGH};             // the segments' lengths; their range: per item, below
     // segment prologue: the ND decimator outputs in front of the segment, from a window of PWIN input samples
-    constexpr int ND = HY + (T2 - 1);                               // 50 with the build's numbers
+    constexpr int ND = SegGeo{true}.front(HY, T2);                  // 50 with the build's numbers
     constexpr int PWIN = DEC * (ND - 1) + T1;                       // 276 (424)
     constexpr int NVP = (PWIN + 2 + 2 * WV - 1) / (2 * WV);         // 16-B vectors per lane: 3 (4)
     constexpr int PBASE = 2 * WV * NVP;                             // the d's are parked behind the staged prologue window
@@ -786,13 +833,12 @@ __device__ __forceinline__ void frontend_body(const K1Args& a, const Taps* __res
     const int ch = grid2d ? (int)blockIdx.y : (int)((unsigned)item / (unsigned)a.seg_count);
     const long seg_rel = grid2d ? (long)blockIdx.x : item - (long)ch * a.seg_count;
     const long seg = seg_rel + a.seg_first;
-    const bool lead = seg < (long)a.lead_segs;                      // uniform
-    const long LEAD_LEN = PRO ? (long)SUB : (long)(SUB - SEGH);
-    const long this_len = lead ? LEAD_LEN : seg_len;
-    const int subs_this = lead ? 1 : a.subs_per_seg;
-    const long m_seg0 = a.m_begin + (lead ? seg * LEAD_LEN : (long)a.lead_segs * LEAD_LEN + (seg - a.lead_segs) * seg_len);
+    const SegGeo sg = shape.range(a.lead_segs, a.m_begin, a.n_out);
+    const long this_len = sg.len(seg);                              // uniform
+    const int subs_this = sg.subs(seg);
+    const long m_seg0 = sg.start(seg);
     if (m_seg0 >= a.n_out) continue;
-    const long m_seg1 = (m_seg0 + this_len < a.n_out) ? m_seg0 + this_len : a.n_out;
+    const long m_seg1 = sg.end_of(m_seg0, this_len);
     const char* xb = reinterpret_cast<const char*>(a.x) + (size_t)ch * a.ch_stride * fmt_bps(FMT);
     float* bb = a.bb + (size_t)ch * a.bb_stride;
     phase_sync();                                                   // the previous item's LDS reads precede this item's writes
@@ -800,7 +846,7 @@ __device__ __forceinline__ void frontend_body(const K1Args& a, const Taps* __res
     using LoaderT = Loader<FMT, PK, TX>;
     using LoaderP = Loader<FMT, PK, TX, NVP>;
     LoaderT ld0, ld1;
-    long dlo = PRO ? m_seg0 : m_seg0 - SEGH;                       // first d index of this sub-tile
+    long dlo = PRO ? m_seg0 : m_seg0 - sg.front(HY, T2);           // first d index of this sub-tile
     const long i_last = (long)a.o0 + DEC * (m_seg1 - 1);          // newest input sample this segment needs
     float pw = 0.f;
     // context carried across sub-tiles in wave-uniform registers: the last channel output and the
@@ -812,11 +858,11 @@ __device__ __forceinline__ void frontend_body(const K1Args& a, const Taps* __res
         for (int k = tid; k < D_CARRY; k += WV) D[k] = make_float2(0.f, 0.f);
         if constexpr (!AVG_DPP)
             for (int k = tid; k < T3 - 1; k += WV) FM[k] = 0.f;
-        ld0.init(xb, (long)a.o0 + DEC * dlo - (T1 - 1), a.n_hist, a.n_new, i_last);
-        ld0.load_first((long)a.o0 + DEC * dlo - (T1 - 1), tid);
+        ld0.init(xb, K1_FIRST_INPUT(dlo, a.o0, T1), a.n_hist, a.n_new, i_last);
+        ld0.load_first(K1_FIRST_INPUT(dlo, a.o0, T1), tid);
         if constexpr (PF == 2) {
             ld1.rs = ld0.rs; ld1.base_idx = ld0.base_idx;
-            ld1.load((long)a.o0 + DEC * (dlo + SUB) - (T1 - 1), tid);
+            ld1.load(K1_FIRST_INPUT(dlo + SUB, a.o0, T1), tid);
         }
 #pragma unroll
         for (int b = 0; b < NBACK; ++b)
@@ -824,7 +870,7 @@ __device__ __forceinline__ void frontend_body(const K1Args& a, const Taps* __res
             for (int p = 0; p < P; ++p) f_carry[b][p] = 0.f;
     } else {
     LoaderP lp;
-    const long pfirst = (long)a.o0 + DEC * (m_seg0 - ND) - (T1 - 1);     // first input sample of the prologue window
+    const long pfirst = K1_FIRST_INPUT(m_seg0 - ND, a.o0, T1);           // first input sample of the prologue window
     ld0.init(xb, pfirst, a.n_hist, a.n_new, i_last);
     lp.rs = ld0.rs; lp.base_idx = ld0.base_idx;
     // one HBM round trip for the prologue window and the first sub-tile's window (both may start before the descriptor's base
@@ -835,10 +881,10 @@ __device__ __forceinline__ void frontend_body(const K1Args& a, const Taps* __res
     // (174: two waves per SIMD); the prologue's arithmetic runs under the second request instead of under both.
     constexpr bool LATE_LD0 = FMT == P25FE_FMT_CF32;
     if constexpr (!LATE_LD0) {
-        ld0.load_first((long)a.o0 + DEC * dlo - (T1 - 1), tid);
+        ld0.load_first(K1_FIRST_INPUT(dlo, a.o0, T1), tid);
         if constexpr (PF == 2) {
             ld1.rs = ld0.rs; ld1.base_idx = ld0.base_idx;
-            ld1.load_first((long)a.o0 + DEC * (dlo + SUB) - (T1 - 1), tid);
+            ld1.load_first(K1_FIRST_INPUT(dlo + SUB, a.o0, T1), tid);
         }
     }
     {
@@ -849,10 +895,10 @@ __device__ __forceinline__ void frontend_body(const K1Args& a, const Taps* __res
         lp.template store<LUTM>(XIN, pfirst, a.n_hist, a.n_new, tid, LUT);
         lp.fixup(XIN, pfirst, a.n_hist, a.n_new, tid);
         if constexpr (LATE_LD0) {
-            ld0.load_first((long)a.o0 + DEC * dlo - (T1 - 1), tid);
+            ld0.load_first(K1_FIRST_INPUT(dlo, a.o0, T1), tid);
             if constexpr (PF == 2) {
                 ld1.rs = ld0.rs; ld1.base_idx = ld0.base_idx;
-                ld1.load_first((long)a.o0 + DEC * (dlo + SUB) - (T1 - 1), tid);
+                ld1.load_first(K1_FIRST_INPUT(dlo + SUB, a.o0, T1), tid);
             }
         }
         phase_sync();
@@ -978,7 +1024,7 @@ __device__ __forceinline__ void frontend_body(const K1Args& a, const Taps* __res
     auto sub_tile = [&](auto& ld) -> bool {
         if (dlo >= m_seg1) return false;                           // uniform
         P25FE_M_SUBTILE;
-        const long first = (long)a.o0 + DEC * dlo - (T1 - 1);      // XIN[xsh + k] = x[first + k]
+        const long first = K1_FIRST_INPUT(dlo, a.o0, T1);           // XIN[xsh + k] = x[first + k]
         const int xsh = (int)(first & 1);                           // window start relative to the aligned staging origin
 #if P25FE_K1_TURNAROUND_PRIO
         __builtin_amdgcn_s_setprio(P25FE_K1_TURNAROUND_PRIO);       // see below

@@ -1132,14 +1132,19 @@ def test_run_dev_lengths_around_layout_boundaries(O, FE):
     from p25rx_amd.frontend import parse_results
     iq_all, _, _ = c4fm.synth(1.2, seed=41, snr_db=20.0, frame_dibits=230, timing_offset=7)
     u8_all = c4fm.to_u8(iq_all)
+    s16_all = c4fm.to_s16(iq_all)
+    cf16_all = (s16_all.astype(np.float32) * np.float32(2.0 ** -15)).view(np.complex64)     # what an s16 sample means (docs/SPEC.md 3.1)
     rng = np.random.default_rng(9)
-    lens = set()
-    for base_bb in (880, 320 * 3, 7680, 7680 * 2, 320 * 24, 880 * 11, 10 * 32 * 7):
+    lens, pro_lens = set(), set()                               # pro_lens: around the u8 / s16 segment, 9 x 320 = 2880 outputs
+    for base_bb in (880, 320 * 3, 7680, 7680 * 2, 320 * 24, 880 * 11, 10 * 32 * 7, 2880, 2 * 2880):
         for d in (-6, -5, -1, 0, 1, 4, 5, 11):
             lens.add(5 * base_bb + d)
+            if base_bb % 2880 == 0:
+                pro_lens.add(5 * base_bb + d)
     lens |= set(int(x) for x in rng.integers(2000, len(iq_all) - 8, size=12))
-    fe, fe8 = FE(), FE()
+    fe, fe8, fe16 = FE(), FE(), FE()
     for n in sorted(lens):
+        pro = n in pro_lens
         n = max(8, min(n, len(iq_all)))
         iq = iq_all[:n]
         ref = O.run_cf32(iq)
@@ -1148,12 +1153,18 @@ def test_run_dev_lengths_around_layout_boundaries(O, FE):
         r = parse_results(res)[0]
         assert int(r["n_dibits"]) == len(ref), n
         assert np.array_equal(dib[0, :len(ref)].cpu().numpy(), ref), n
-        if n % 97 < 40:                                          # a subset through the u8 kernel as well
+        if n % 97 < 40 or pro:                                   # a subset through the u8 kernel as well
             ref8 = O.Recv().feed(O.Demod().feed_u8(u8_all[:2 * n]))[0]
             t8 = torch.from_numpy(u8_all[:2 * n].reshape(-1, 2)).cuda()
             d8, r8 = fe8.run_dev(t8)
             assert int(parse_results(r8)[0]["n_dibits"]) == len(ref8), n
             assert np.array_equal(d8[0, :len(ref8)].cpu().numpy(), ref8), n
+        if pro:                                                  # ... and, around its segment, the s16 kernel
+            ref16 = O.run_cf32(cf16_all[:n])
+            t16 = torch.from_numpy(s16_all[:2 * n].reshape(-1, 2)).cuda()
+            d16, r16 = fe16.run_dev(t16)
+            assert int(parse_results(r16)[0]["n_dibits"]) == len(ref16), n
+            assert np.array_equal(d16[0, :len(ref16)].cpu().numpy(), ref16), n
 
 
 @pytest.mark.gpu

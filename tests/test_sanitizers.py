@@ -31,6 +31,19 @@ def test_library_host_side_under_asan_ubsan():
     assert "abi host driver ok" in out
 
 
+def test_k1_segment_geometry_under_asan_ubsan():
+    """K1's segment geometry (SegGeo, p25fe_kernels.hip: what the launch planner and the kernel both call) walked on the CPU:
+    segments tile a range exactly, HEAD and MAIN partition it, MAIN never reads the halo, the planar alignment rules
+    (tests/native/k1_geometry_driver.cpp).  Host code only: no HIP runtime call, no GPU."""
+    exe = os.path.join(ROOT, "build", "k1_geometry")
+    os.makedirs(os.path.dirname(exe), exist_ok=True)
+    subprocess.check_call([os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-x", "hip", "--offload-arch=gfx950", "-O2", "-g", "-std=c++17",
+                           "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
+                           "-fno-omit-frame-pointer", "-I" + os.path.join(ROOT, "include"), "-o", exe,
+                           os.path.join(ROOT, "tests", "native", "k1_geometry_driver.cpp")])
+    assert "k1 geometry driver ok" in run_clean(exe)
+
+
 @pytest.mark.gpu
 def test_library_streaming_entry_points_under_host_asan():
     """On the GPU box (the same host-side sanitizer build as above, made here when a CPU run has not left it in build/): the
