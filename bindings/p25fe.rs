@@ -187,6 +187,8 @@ extern "C" {
                            d_bb: *mut f32, bb_stride: usize, d_power_dbm: *mut f32, stream: *mut c_void) -> c_int;
     pub fn p25fe_predecim_dev(h: *mut Handle, d_iq: *const f32, ch_stride: usize, n_hist: usize, n: usize, abs0: u64,
                               d_out: *mut f32, out_stride: usize, stream: *mut c_void) -> c_int;
+    pub fn p25fe_predecim_fmt_dev(h: *mut Handle, d_iq: *const c_void, fmt: c_int, ch_stride: usize, n_hist: usize, n: usize, abs_first: u64,
+                                  d_out: *mut f32, out_stride: usize, stream: *mut c_void) -> c_int;
     pub fn p25fe_n_predecim(abs0: u64, n: usize) -> usize;
     pub fn p25fe_n_baseband(abs0: u64, n: usize) -> usize;
     pub fn p25fe_slice_dev(h: *mut Handle, d_bb: *const f32, bb_stride: usize, n_hist_bb: usize, n_bb: usize, abs_bb0: u64,
@@ -238,6 +240,8 @@ extern "C" {
                                 d_power_dbm: *const f32, d_stats: *mut ChanStats, stream: *mut c_void) -> c_int;
     pub fn p25fe_channelise_dev(h: *mut Handle, d_iq: *const f32, n_hist: usize, n: usize, abs0: u64, d_out: *mut f32,
                                 out_stride: usize, stream: *mut c_void) -> c_int;
+    pub fn p25fe_channelise_fmt_dev(h: *mut Handle, d_iq: *const c_void, fmt: c_int, n_hist: usize, n: usize, abs_first: u64,
+                                    d_out: *mut f32, out_stride: usize, stream: *mut c_void) -> c_int;
     pub fn p25fe_n_baseband_h(h: *const Handle, abs0: u64, n: usize) -> usize;
     pub fn p25fe_profile_enable(h: *mut Handle, on: c_int) -> c_int;
     pub fn p25fe_profile_read(h: *mut Handle, ms: *mut f64, n_calls: *mut u64) -> c_int;

@@ -331,7 +331,7 @@ int p25fe_state_import(p25fe_t *h, const void *buf, size_t n);
  * comes back shifted by the difference (docs/SPEC.md section 4).
  * The one bound is P25FE_MAX_POSITION = 2^62: the kernels keep signed 64-bit indices and add a
  * range's length on top.  What the host can see is checked and answers P25FE_ERR_ARG at 2^62 or
- * more: abs0 (p25fe_demod_dev, p25fe_predecim_dev, p25fe_channelise_dev, the p25fe_shard_pass1
+ * more: abs0 (p25fe_demod_dev, p25fe_predecim_dev, p25fe_channelise_dev -- abs_first in their _fmt_ forms --, the p25fe_shard_pass1
  * forms), abs_bb0 (p25fe_slice_dev), shard_bb0[r] and shard_bb0[r] + shard_bb_n[r] of
  * p25fe_shard_resolve, and in a blob given to p25fe_state_import the two counters and the `s` of
  * every valid anchor.  Positions the library only ever sees in DEVICE memory are the caller's to
@@ -351,6 +351,13 @@ int p25fe_demod_dev(p25fe_t *h, const void *d_iq, int fmt, size_t ch_stride, siz
 int p25fe_predecim_dev(p25fe_t *h, const float *d_iq, size_t ch_stride, size_t n_hist, size_t n, uint64_t abs0,
                        float *d_out, size_t out_stride, void *stream);
 size_t p25fe_n_predecim(uint64_t abs0, size_t n);
+/* The same stage on the capture as the tuner delivers it (docs/SPEC.md 3.0): fmt = P25FE_FMT_U8 (byte pairs, I first; the
+ * handle's u8_scale / u8_offset or u8_lut) or P25FE_FMT_S16 (little-endian int16 pairs, I first; value * 2^-15).  The output is,
+ * bit for bit, p25fe_predecim_dev's on the converted samples.  d_iq is 16-byte aligned, ch_stride a multiple of 8 (u8) or 4
+ * (s16) samples, as for p25fe_demod_dev; only the aligned 16-byte vectors that hold samples [-n_hist, n) of a channel are read.
+ * fmt = P25FE_FMT_CF32 is p25fe_predecim_dev itself.  P25FE_ERR_ARG: unknown format, misaligned or null pointer, abs_first >= 2^62. */
+int p25fe_predecim_fmt_dev(p25fe_t *h, const void *d_iq, int fmt, size_t ch_stride, size_t n_hist, size_t n,
+                           uint64_t abs_first /* = p25fe_predecim_dev's abs0 */, float *d_out, size_t out_stride, void *stream);
 
 /* stages 6-7 on device baseband.  d_bb points at the first owned sample; n_hist_bb valid
  * samples precede it; abs_bb0 is its absolute index; d_anchor_in (nullable = no lock) is the
@@ -527,6 +534,11 @@ int p25fe_nid_batch_dev(p25fe_t *h, const uint8_t *d_dibits, size_t dibit_stride
 #define P25FE_CHZ_CHANNELS_ABI 192
 int p25fe_channelise_dev(p25fe_t *h, const float *d_iq, size_t n_hist, size_t n, uint64_t abs0, float *d_out,
                          size_t out_stride, void *stream);
+/* ... on a u8 or s16 capture (docs/SPEC.md 3.11; formats, conversion, alignment and errors as p25fe_predecim_fmt_dev): bit for
+ * bit p25fe_channelise_dev's output on the converted samples; here the handle also supplies the u8 conversion.
+ * fmt = P25FE_FMT_CF32 is p25fe_channelise_dev itself. */
+int p25fe_channelise_fmt_dev(p25fe_t *h, const void *d_iq, int fmt, size_t n_hist, size_t n,
+                             uint64_t abs_first /* = p25fe_channelise_dev's abs0 */, float *d_out, size_t out_stride, void *stream);
 
 /* Per-channel observability record: what the reference pushes to its hub as
  * HubEvent::UpdateSignalPower (src/demod.rs:95-101, "sigPower" src/hub.rs:344) and HubEvent::UpdateStats

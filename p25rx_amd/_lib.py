@@ -75,6 +75,7 @@ SYMBOLS = [
     "p25fe_kernel_variant", "p25fe_specialize", "p25fe_specialize_log", "p25fe_run_host_windows",
     "p25fe_shard_pass1_head", "p25fe_shard_pipe_begin", "p25fe_shard_pipe_end", "p25fe_rx_stream", "p25fe_shard_head_check", "p25fe_shard_pass1_k1", "p25fe_streams_share_queue", "p25fe_shard_pass2_dev", "p25fe_shard_compact_from_dev", "p25fe_probe_variant", "p25fe_n_baseband_h",
     "p25fe_demod_s16", "p25fe_run_s16", "p25fe_format_variant", "p25fe_probe_format_variant",
+    "p25fe_predecim_fmt_dev", "p25fe_channelise_fmt_dev",
 ]
 
 
@@ -167,6 +168,8 @@ def load():
     L.p25fe_profile_enable.argtypes = [vp, C.c_int]
     L.p25fe_profile_read.argtypes = [vp, C.POINTER(C.c_double * 4), C.POINTER(u64)]
     L.p25fe_predecim_dev.argtypes = [vp, vp, sz, sz, sz, u64, vp, sz, vp]
+    L.p25fe_predecim_fmt_dev.argtypes = [vp, vp, C.c_int, sz, sz, sz, u64, vp, sz, vp]
+    L.p25fe_channelise_fmt_dev.argtypes = [vp, vp, C.c_int, sz, sz, u64, vp, sz, vp]
     L.p25fe_n_predecim.argtypes = [u64, sz]
     L.p25fe_n_predecim.restype = sz
     L.p25fe_n_baseband.argtypes = [u64, sz]

@@ -332,6 +332,7 @@ struct p25fe {
     int phase = P25FE_DECIM_PHASE;         // p25fe_config_t.decim_phase: baseband sample m comes from input 5 m + phase
     int n_avg = BOX;                       // post-discriminator filter: taps in use (the table is taps.avg)
     bool u8_lut_mode = false;              // the u8 table is not affine: the specialised kernels look it up in LDS (the generic ones always do)
+    float u8_scale = 0.0f, u8_offset = 0.0f;   // the affine u8 table as arithmetic (unused when u8_lut_mode): K0 / K6 on u8 input
     int track = 0;                         // p25fe_config_t.symbol_clock without its flag bits (docs/SPEC.md 3.8b)
     bool causal_ok = false;                // P25FE_CLOCK_CAUSAL_OK: mode 2 may run as mode 1 in the calls that see the stream in pieces
     long look = 0;                         // samples the receiver runs behind the baseband (2 with the tracking clock)
@@ -709,6 +710,7 @@ int p25fe_create(const p25fe_config_t* cfg, p25fe_t** out)
     h->n_avg = rs.taps.n_avg;
     h->long_taps = rs.long_taps;
     h->u8_lut_mode = !rs.lut_affine;
+    h->u8_scale = rs.u8_scale; h->u8_offset = rs.u8_offset;
     h->variant = rs.dflt ? P25FE_VARIANT_BUILTIN : P25FE_VARIANT_GENERIC;
     h->dflt = rs.dflt;
     if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { p25fe_destroy(h); return P25FE_ERR_HIP; }
@@ -1326,6 +1328,68 @@ int p25fe_channelise_dev(p25fe_t* h, const float* d_iq, size_t n_hist, size_t n,
     a.o0 = (int)((PD - 1 + PD - abs0 % PD) % PD);
     a.y = d_out; a.y_stride = (long)out_stride; a.n_out = (long)n_out;
     hipLaunchKernelGGL(k_channelise, dim3((unsigned)((n_out + WV - 1) / WV)), dim3(WV), 0, (hipStream_t)stream, a);
+    HIPCHK(h, hipGetLastError());
+    return P25FE_OK;
+}
+
+// Wideband input as the tuner delivers it (SPEC 3.0 / 3.11): the same stages on s16 or u8 pairs.  The conversion's numbers are
+// kernel arguments; a u8 table the handle could not recognise as affine is read from its device copy.
+static WideConv wide_conv_of(const p25fe_t* h)
+{
+    WideConv cv;
+    cv.scale = h->u8_scale; cv.offset = h->u8_offset;
+    cv.lut = h->u8_lut_mode ? h->d_taps.as<Taps>()->lut : nullptr;
+    return cv;
+}
+static inline bool wide_fmt_known(int fmt) { return fmt == P25FE_FMT_CF32 || fmt == P25FE_FMT_S16 || fmt == P25FE_FMT_U8; }
+
+int p25fe_predecim_fmt_dev(p25fe_t* h, const void* d_iq, int fmt, size_t ch_stride, size_t n_hist, size_t n, uint64_t abs_first,
+                           float* d_out, size_t out_stride, void* stream)
+{
+    if (!h || !wide_fmt_known(fmt)) return P25FE_ERR_ARG;
+    if (fmt == P25FE_FMT_CF32) return p25fe_predecim_dev(h, static_cast<const float*>(d_iq), ch_stride, n_hist, n, abs_first, d_out, out_stride, stream);
+    if (!d_iq || !d_out || position_refused(abs_first)) return P25FE_ERR_ARG;
+    const size_t spv = 16 / fmt_bytes(fmt);                               // samples per 16-B vector: 4 (s16), 8 (u8)
+    if ((reinterpret_cast<uintptr_t>(d_iq) & 15u) != 0 || (h->C > 1 && ch_stride % spv != 0)) return P25FE_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const size_t n_out = p25fe_n_predecim(abs_first, n);
+    if (n_out == 0) return P25FE_OK;
+    K0Args a;
+    a.x = static_cast<const float*>(d_iq); a.ch_stride = (long)ch_stride; a.n_hist = (long)n_hist; a.n_new = (long)n;   // (x: addressed by the format's bytes)
+    a.o0 = (int)((PD - 1 + PD - abs_first % PD) % PD);
+    a.y = d_out; a.y_stride = (long)out_stride; a.n_out = (long)n_out;
+    const size_t per_wg = (size_t)K0_SUB * K0_SUBS;
+    dim3 grid((unsigned)((n_out + per_wg - 1) / per_wg), (unsigned)h->C);
+    const WideConv cv = wide_conv_of(h);
+    hipStream_t st = (hipStream_t)stream;
+    if (fmt == P25FE_FMT_S16) hipLaunchKernelGGL((k_predecim_fmt<P25FE_FMT_S16, false>), grid, dim3(WV), 0, st, a, cv);
+    else if (cv.lut) hipLaunchKernelGGL((k_predecim_fmt<P25FE_FMT_U8, true>), grid, dim3(WV), 0, st, a, cv);
+    else hipLaunchKernelGGL((k_predecim_fmt<P25FE_FMT_U8, false>), grid, dim3(WV), 0, st, a, cv);
+    HIPCHK(h, hipGetLastError());
+    return P25FE_OK;
+}
+
+int p25fe_channelise_fmt_dev(p25fe_t* h, const void* d_iq, int fmt, size_t n_hist, size_t n, uint64_t abs_first, float* d_out,
+                             size_t out_stride, void* stream)
+{
+    if (!h || !wide_fmt_known(fmt)) return P25FE_ERR_ARG;
+    if (fmt == P25FE_FMT_CF32) return p25fe_channelise_dev(h, static_cast<const float*>(d_iq), n_hist, n, abs_first, d_out, out_stride, stream);
+    if (!d_iq || !d_out || position_refused(abs_first)) return P25FE_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_iq) & 15u) != 0 || (reinterpret_cast<uintptr_t>(d_out) & 7u) != 0) return P25FE_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const size_t n_out = p25fe_n_predecim(abs_first, n);
+    if (n_out == 0) return P25FE_OK;
+    if (out_stride < round_up(n_out, (size_t)WV)) return P25FE_ERR_ARG;      // rows are written in whole 64-instant tiles
+    ChzArgs a;
+    a.x = static_cast<const float*>(d_iq); a.n_hist = (long)n_hist; a.n_new = (long)n; a.abs0 = (long)abs_first;
+    a.o0 = (int)((PD - 1 + PD - abs_first % PD) % PD);
+    a.y = d_out; a.y_stride = (long)out_stride; a.n_out = (long)n_out;
+    const dim3 grid((unsigned)((n_out + WV - 1) / WV));
+    const WideConv cv = wide_conv_of(h);
+    hipStream_t st = (hipStream_t)stream;
+    if (fmt == P25FE_FMT_S16) hipLaunchKernelGGL((k_channelise_fmt<P25FE_FMT_S16, false>), grid, dim3(WV), 0, st, a, cv);
+    else if (cv.lut) hipLaunchKernelGGL((k_channelise_fmt<P25FE_FMT_U8, true>), grid, dim3(WV), 0, st, a, cv);
+    else hipLaunchKernelGGL((k_channelise_fmt<P25FE_FMT_U8, false>), grid, dim3(WV), 0, st, a, cv);
     HIPCHK(h, hipGetLastError());
     return P25FE_OK;
 }

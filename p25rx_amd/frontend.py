@@ -275,26 +275,35 @@ class FrontEnd:
         return (bb, nb, pw) if want_power else (bb, nb)
 
     def predecim_dev(self, iq, n_hist=0, abs0=0, offset=0, out=None):
-        """Stage 0 (config 3): cf32 @ 2.4 Msps [n, 2] or [C, n, 2] -> cf32 @ 240 ksps [C, n_out, 2] on device."""
+        """Stage 0 (config 3): cf32, int16 or uint8 @ 2.4 Msps [n, 2] or [C, n, 2] -> cf32 @ 240 ksps [C, n_out, 2] on device."""
         import torch
         fmt, n_total, stride = self._iq_view(iq)
-        assert fmt == FMT_CF32
         n = n_total - offset
         no = self.L.p25fe_n_predecim(abs0, n)
         if out is None:
             out = torch.empty((self.C, (no + 3) // 2 * 2, 2), dtype=torch.float32, device=iq.device)
+        if fmt != FMT_CF32:
+            self._chk(self.L.p25fe_predecim_fmt_dev(self.h, C.c_void_p(iq.data_ptr() + fmt_bytes(fmt) * offset), fmt, stride, n_hist,
+                                                    n, abs0, C.c_void_p(out.data_ptr()), out.stride(0) // 2, self._stream()))
+            return out, no
         self._chk(self.L.p25fe_predecim_dev(self.h, C.c_void_p(iq.data_ptr() + 8 * offset), stride, n_hist, n, abs0,
                                             C.c_void_p(out.data_ptr()), out.stride(0) // 2, self._stream()))
         return out, no
 
     def channelise_dev(self, iq, n_hist=0, abs0=0, offset=0, out=None):
-        """SPEC 3.11: wideband cf32 @ 2.4 Msps [n, 2] (device) -> [192, n_out (padded), 2] cf32 @ 240 ksps."""
+        """SPEC 3.11: wideband cf32, int16 or uint8 @ 2.4 Msps [n, 2] (device) -> [192, n_out (padded), 2] cf32 @ 240 ksps."""
         import torch
-        assert iq.dtype == torch.float32 and iq.dim() == 2 and iq.shape[1] == 2
+        assert iq.dim() == 2 and iq.shape[1] == 2
+        fmt = _torch_fmt(iq.dtype)
+        assert fmt == FMT_CF32 or (iq.is_cuda and iq.is_contiguous())
         n = iq.shape[0] - offset
         no = self.L.p25fe_n_predecim(abs0, n)
         if out is None:
             out = torch.empty((CHZ_CHANNELS, max(64, (no + 63) // 64 * 64), 2), dtype=torch.float32, device=iq.device)
+        if fmt != FMT_CF32:
+            self._chk(self.L.p25fe_channelise_fmt_dev(self.h, C.c_void_p(iq.data_ptr() + fmt_bytes(fmt) * offset), fmt, n_hist, n,
+                                                      abs0, C.c_void_p(out.data_ptr()), out.stride(0) // 2, self._stream()))
+            return out, no
         self._chk(self.L.p25fe_channelise_dev(self.h, C.c_void_p(iq.data_ptr() + 8 * offset), n_hist, n, abs0,
                                               C.c_void_p(out.data_ptr()), out.stride(0) // 2, self._stream()))
         return out, no
