@@ -1271,6 +1271,68 @@ static int launch_planar_recv(p25fe_t* h, K1Launch& k, const RecvCall& rc, hipEv
 // (P25FE_CLOCK_CAUSAL_OK) -- otherwise the call is refused instead of quietly returning another receiver's dibits.
 static inline bool piecewise_refused(const p25fe_t* h) { return h->track == P25FE_CLOCK_TRACKING_RESLICE && !h->causal_ok; }
 
+// --------------------------------------------------------------------------------------------
+// K0 and K6 launches: one function per stage for every wideband format (h and fmt are checked by the caller).  The conversion's
+// numbers are kernel arguments; a u8 table the handle could not recognise as affine is read from its device copy.
+// --------------------------------------------------------------------------------------------
+static WideConv wide_conv_of(const p25fe_t* h)
+{
+    WideConv cv;
+    cv.scale = h->u8_scale; cv.offset = h->u8_offset;
+    cv.lut = h->u8_lut_mode ? h->d_taps.as<Taps>()->lut : nullptr;
+    return cv;
+}
+static inline bool wide_fmt_known(int fmt) { return fmt == P25FE_FMT_CF32 || fmt == P25FE_FMT_S16 || fmt == P25FE_FMT_U8; }
+static inline int wide_o0(uint64_t abs0) { return (int)((PD - 1 + PD - abs0 % PD) % PD); }   // first decimation instant of the range
+
+static int launch_k0(p25fe_t* h, const void* d_iq, int fmt, size_t ch_stride, size_t n_hist, size_t n, uint64_t abs0,
+                     float* d_out, size_t out_stride, hipStream_t st)
+{
+    if (!d_iq || !d_out || position_refused(abs0)) return P25FE_ERR_ARG;
+    // the kernels fetch aligned 16-byte vectors: channel rows are whole vectors (2 cf32, 4 s16, 8 u8 samples)
+    if ((reinterpret_cast<uintptr_t>(d_iq) & 15u) != 0 || (h->C > 1 && ch_stride % fmt_stride_unit(fmt) != 0)) return P25FE_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const size_t n_out = p25fe_n_predecim(abs0, n);
+    if (n_out == 0) return P25FE_OK;
+    K0Args a;
+    a.x = static_cast<const float*>(d_iq); a.ch_stride = (long)ch_stride; a.n_hist = (long)n_hist; a.n_new = (long)n;   // (x: addressed by the format's bytes)
+    a.o0 = wide_o0(abs0);
+    a.y = d_out; a.y_stride = (long)out_stride; a.n_out = (long)n_out;
+    const size_t per_wg = (size_t)K0_SUB * K0_SUBS;
+    const dim3 grid((unsigned)((n_out + per_wg - 1) / per_wg), (unsigned)h->C);
+    const WideConv cv = wide_conv_of(h);
+    if (fmt == P25FE_FMT_CF32) hipLaunchKernelGGL(k_predecim, grid, dim3(WV), 0, st, a);
+    else if (fmt == P25FE_FMT_S16) hipLaunchKernelGGL((k_predecim_fmt<P25FE_FMT_S16, false>), grid, dim3(WV), 0, st, a, cv);
+    else if (cv.lut) hipLaunchKernelGGL((k_predecim_fmt<P25FE_FMT_U8, true>), grid, dim3(WV), 0, st, a, cv);
+    else hipLaunchKernelGGL((k_predecim_fmt<P25FE_FMT_U8, false>), grid, dim3(WV), 0, st, a, cv);
+    HIPCHK(h, hipGetLastError());
+    return P25FE_OK;
+}
+
+static int launch_k6(p25fe_t* h, const void* d_iq, int fmt, size_t n_hist, size_t n, uint64_t abs0, float* d_out,
+                     size_t out_stride, hipStream_t st)
+{
+    static_assert(P25FE_CHZ_CHANNELS_ABI == CZ_M, "header and spec disagree");
+    if (!d_iq || !d_out || position_refused(abs0)) return P25FE_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_iq) & 15u) != 0 || (reinterpret_cast<uintptr_t>(d_out) & 7u) != 0) return P25FE_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const size_t n_out = p25fe_n_predecim(abs0, n);
+    if (n_out == 0) return P25FE_OK;
+    if (out_stride < round_up(n_out, (size_t)WV)) return P25FE_ERR_ARG;      // rows are written in whole 64-instant tiles
+    ChzArgs a;
+    a.x = static_cast<const float*>(d_iq); a.n_hist = (long)n_hist; a.n_new = (long)n; a.abs0 = (long)abs0;
+    a.o0 = wide_o0(abs0);
+    a.y = d_out; a.y_stride = (long)out_stride; a.n_out = (long)n_out;
+    const dim3 grid((unsigned)((n_out + WV - 1) / WV));
+    const WideConv cv = wide_conv_of(h);
+    if (fmt == P25FE_FMT_CF32) hipLaunchKernelGGL(k_channelise, grid, dim3(WV), 0, st, a);
+    else if (fmt == P25FE_FMT_S16) hipLaunchKernelGGL((k_channelise_fmt<P25FE_FMT_S16, false>), grid, dim3(WV), 0, st, a, cv);
+    else if (cv.lut) hipLaunchKernelGGL((k_channelise_fmt<P25FE_FMT_U8, true>), grid, dim3(WV), 0, st, a, cv);
+    else hipLaunchKernelGGL((k_channelise_fmt<P25FE_FMT_U8, false>), grid, dim3(WV), 0, st, a, cv);
+    HIPCHK(h, hipGetLastError());
+    return P25FE_OK;
+}
+
 extern "C" {
 
 // --------------------------------------------------------------------------------------------
@@ -1290,108 +1352,37 @@ int p25fe_demod_dev(p25fe_t* h, const void* d_iq, int fmt, size_t ch_stride, siz
 
 size_t p25fe_n_predecim(uint64_t abs0, size_t n)
 {
-    const size_t o0 = (size_t)((PD - 1 + PD - abs0 % PD) % PD);
+    const size_t o0 = (size_t)wide_o0(abs0);
     return n > o0 ? (n - o0 - 1) / PD + 1 : 0;
 }
 
 int p25fe_predecim_dev(p25fe_t* h, const float* d_iq, size_t ch_stride, size_t n_hist, size_t n, uint64_t abs0,
                        float* d_out, size_t out_stride, void* stream)
 {
-    if (!h || !d_iq || !d_out || position_refused(abs0)) return P25FE_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(d_iq) & 15u) != 0 || (h->C > 1 && (ch_stride & 1))) return P25FE_ERR_ARG;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const size_t n_out = p25fe_n_predecim(abs0, n);
-    if (n_out == 0) return P25FE_OK;
-    K0Args a;
-    a.x = d_iq; a.ch_stride = (long)ch_stride; a.n_hist = (long)n_hist; a.n_new = (long)n;
-    a.o0 = (int)((PD - 1 + PD - abs0 % PD) % PD);
-    a.y = d_out; a.y_stride = (long)out_stride; a.n_out = (long)n_out;
-    const size_t per_wg = (size_t)K0_SUB * K0_SUBS;
-    dim3 grid((unsigned)((n_out + per_wg - 1) / per_wg), (unsigned)h->C);
-    hipLaunchKernelGGL(k_predecim, grid, dim3(WV), 0, (hipStream_t)stream, a);
-    HIPCHK(h, hipGetLastError());
-    return P25FE_OK;
+    if (!h) return P25FE_ERR_ARG;
+    return launch_k0(h, d_iq, P25FE_FMT_CF32, ch_stride, n_hist, n, abs0, d_out, out_stride, (hipStream_t)stream);
 }
 
 int p25fe_channelise_dev(p25fe_t* h, const float* d_iq, size_t n_hist, size_t n, uint64_t abs0, float* d_out,
                          size_t out_stride, void* stream)
 {
-    static_assert(P25FE_CHZ_CHANNELS_ABI == CZ_M, "header and spec disagree");
-    if (!h || !d_iq || !d_out || position_refused(abs0)) return P25FE_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(d_iq) & 15u) != 0 || (reinterpret_cast<uintptr_t>(d_out) & 7u) != 0) return P25FE_ERR_ARG;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const size_t n_out = p25fe_n_predecim(abs0, n);
-    if (n_out == 0) return P25FE_OK;
-    if (out_stride < round_up(n_out, (size_t)WV)) return P25FE_ERR_ARG;      // rows are written in whole 64-instant tiles
-    ChzArgs a;
-    a.x = d_iq; a.n_hist = (long)n_hist; a.n_new = (long)n; a.abs0 = (long)abs0;
-    a.o0 = (int)((PD - 1 + PD - abs0 % PD) % PD);
-    a.y = d_out; a.y_stride = (long)out_stride; a.n_out = (long)n_out;
-    hipLaunchKernelGGL(k_channelise, dim3((unsigned)((n_out + WV - 1) / WV)), dim3(WV), 0, (hipStream_t)stream, a);
-    HIPCHK(h, hipGetLastError());
-    return P25FE_OK;
+    if (!h) return P25FE_ERR_ARG;
+    return launch_k6(h, d_iq, P25FE_FMT_CF32, n_hist, n, abs0, d_out, out_stride, (hipStream_t)stream);
 }
 
-// Wideband input as the tuner delivers it (SPEC 3.0 / 3.11): the same stages on s16 or u8 pairs.  The conversion's numbers are
-// kernel arguments; a u8 table the handle could not recognise as affine is read from its device copy.
-static WideConv wide_conv_of(const p25fe_t* h)
-{
-    WideConv cv;
-    cv.scale = h->u8_scale; cv.offset = h->u8_offset;
-    cv.lut = h->u8_lut_mode ? h->d_taps.as<Taps>()->lut : nullptr;
-    return cv;
-}
-static inline bool wide_fmt_known(int fmt) { return fmt == P25FE_FMT_CF32 || fmt == P25FE_FMT_S16 || fmt == P25FE_FMT_U8; }
-
+// Wideband input as the tuner delivers it (SPEC 3.0 / 3.11): the same stages on s16 or u8 pairs, or on cf32.
 int p25fe_predecim_fmt_dev(p25fe_t* h, const void* d_iq, int fmt, size_t ch_stride, size_t n_hist, size_t n, uint64_t abs_first,
                            float* d_out, size_t out_stride, void* stream)
 {
     if (!h || !wide_fmt_known(fmt)) return P25FE_ERR_ARG;
-    if (fmt == P25FE_FMT_CF32) return p25fe_predecim_dev(h, static_cast<const float*>(d_iq), ch_stride, n_hist, n, abs_first, d_out, out_stride, stream);
-    if (!d_iq || !d_out || position_refused(abs_first)) return P25FE_ERR_ARG;
-    const size_t spv = 16 / fmt_bytes(fmt);                               // samples per 16-B vector: 4 (s16), 8 (u8)
-    if ((reinterpret_cast<uintptr_t>(d_iq) & 15u) != 0 || (h->C > 1 && ch_stride % spv != 0)) return P25FE_ERR_ARG;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const size_t n_out = p25fe_n_predecim(abs_first, n);
-    if (n_out == 0) return P25FE_OK;
-    K0Args a;
-    a.x = static_cast<const float*>(d_iq); a.ch_stride = (long)ch_stride; a.n_hist = (long)n_hist; a.n_new = (long)n;   // (x: addressed by the format's bytes)
-    a.o0 = (int)((PD - 1 + PD - abs_first % PD) % PD);
-    a.y = d_out; a.y_stride = (long)out_stride; a.n_out = (long)n_out;
-    const size_t per_wg = (size_t)K0_SUB * K0_SUBS;
-    dim3 grid((unsigned)((n_out + per_wg - 1) / per_wg), (unsigned)h->C);
-    const WideConv cv = wide_conv_of(h);
-    hipStream_t st = (hipStream_t)stream;
-    if (fmt == P25FE_FMT_S16) hipLaunchKernelGGL((k_predecim_fmt<P25FE_FMT_S16, false>), grid, dim3(WV), 0, st, a, cv);
-    else if (cv.lut) hipLaunchKernelGGL((k_predecim_fmt<P25FE_FMT_U8, true>), grid, dim3(WV), 0, st, a, cv);
-    else hipLaunchKernelGGL((k_predecim_fmt<P25FE_FMT_U8, false>), grid, dim3(WV), 0, st, a, cv);
-    HIPCHK(h, hipGetLastError());
-    return P25FE_OK;
+    return launch_k0(h, d_iq, fmt, ch_stride, n_hist, n, abs_first, d_out, out_stride, (hipStream_t)stream);
 }
 
 int p25fe_channelise_fmt_dev(p25fe_t* h, const void* d_iq, int fmt, size_t n_hist, size_t n, uint64_t abs_first, float* d_out,
                              size_t out_stride, void* stream)
 {
     if (!h || !wide_fmt_known(fmt)) return P25FE_ERR_ARG;
-    if (fmt == P25FE_FMT_CF32) return p25fe_channelise_dev(h, static_cast<const float*>(d_iq), n_hist, n, abs_first, d_out, out_stride, stream);
-    if (!d_iq || !d_out || position_refused(abs_first)) return P25FE_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(d_iq) & 15u) != 0 || (reinterpret_cast<uintptr_t>(d_out) & 7u) != 0) return P25FE_ERR_ARG;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const size_t n_out = p25fe_n_predecim(abs_first, n);
-    if (n_out == 0) return P25FE_OK;
-    if (out_stride < round_up(n_out, (size_t)WV)) return P25FE_ERR_ARG;      // rows are written in whole 64-instant tiles
-    ChzArgs a;
-    a.x = static_cast<const float*>(d_iq); a.n_hist = (long)n_hist; a.n_new = (long)n; a.abs0 = (long)abs_first;
-    a.o0 = (int)((PD - 1 + PD - abs_first % PD) % PD);
-    a.y = d_out; a.y_stride = (long)out_stride; a.n_out = (long)n_out;
-    const dim3 grid((unsigned)((n_out + WV - 1) / WV));
-    const WideConv cv = wide_conv_of(h);
-    hipStream_t st = (hipStream_t)stream;
-    if (fmt == P25FE_FMT_S16) hipLaunchKernelGGL((k_channelise_fmt<P25FE_FMT_S16, false>), grid, dim3(WV), 0, st, a, cv);
-    else if (cv.lut) hipLaunchKernelGGL((k_channelise_fmt<P25FE_FMT_U8, true>), grid, dim3(WV), 0, st, a, cv);
-    else hipLaunchKernelGGL((k_channelise_fmt<P25FE_FMT_U8, false>), grid, dim3(WV), 0, st, a, cv);
-    HIPCHK(h, hipGetLastError());
-    return P25FE_OK;
+    return launch_k6(h, d_iq, fmt, n_hist, n, abs_first, d_out, out_stride, (hipStream_t)stream);
 }
 
 // Every entry point that uses the receiver's scratch first makes its stream wait for receive kernels that

@@ -1318,7 +1318,7 @@ __global__ __launch_bounds__(WV, k1_wps(FMT, CT, PK, OM)) void k_frontend(K1Args
 }
 
 // ------------------------------------------------------------------------------------------
-// K0: stage 0 of BASELINE.json config 3 -- 10:1 decimating FIR, 2.4 Msps cf32 -> 240 ksps cf32, T0 = 80 taps
+// K0: stage 0 of BASELINE.json config 3 -- 10:1 decimating FIR, 2.4 Msps (cf32, s16 or u8) -> 240 ksps cf32, T0 = 80 taps
 // (SPEC 3.0; no reference counterpart: src/consts.rs:11 fixes 240 ksps).  Same construction as K1: one wave per
 // workgroup, next window prefetched into registers, outputs stored one iteration late.  The 1990-sample window of
 // a 192-output sub-tile is staged in LDS in POLYPHASE layout X[r][j] = x[base + 10 j + r]; a lane computes 3
@@ -1348,7 +1348,6 @@ constexpr int k0_row_pitch(int need) { return need + ((13 - need % 16) + 16) % 1
 constexpr int K0_JP = k0_row_pitch(K0_NIN / PD + 2);   // entries per phase row (205 for 192 outputs); = 13 mod 16: staging position t lands on
                                              // bank pair 13 t + c (mod 16) whether or not the phase wraps -> conflict-free ds_write_b64
 static_assert(K0_JP >= K0_NIN / PD + 2 && K0_JP % 16 == 13, "polyphase row pitch");
-constexpr int K0_NV = (K0_NIN + 2 + 2 * WV - 1) / (2 * WV);   // 16-B vectors per lane: 16
 constexpr int HIST_PRE = K0_HALO + PD - 1;   // 79: history needed for exact results
 
 struct K0Args {
@@ -1362,122 +1361,13 @@ struct K0Args {
 };
 
 #ifndef P25FE_JIT
-// (predecim_body below is this kernel with another window loader, for s16 / u8 input: a change to the FIR loop or the stores
-// here is made there too -- tests/test_gpu_wide_fmt.py compares the two bit for bit)
-__global__ __launch_bounds__(WV, P25FE_K0_WPS) void k_predecim(K0Args a)
-{
-    __shared__ float2 X[PD * K0_JP];
-    __shared__ float2 OUT[K0_SUB];
-    const int tid = threadIdx.x, ch = blockIdx.y;
-    const long m_wg0 = (long)blockIdx.x * (K0_SUB * K0_SUBS);
-    const uint4* xb = reinterpret_cast<const uint4*>(a.x + 2 * (size_t)ch * a.ch_stride);
-    float2* yb = reinterpret_cast<float2*>(a.y) + (size_t)ch * a.y_stride;
-
-    const long wg_last = (long)a.o0 + PD * (m_wg0 + (long)(K0_SUBS - 1) * K0_SUB) - (T0 - 1);   // base of the last window
-    uint4 v[K0_NV];
-    // window of the sub-tile whose first output is m0: positions k = 0 .. K0_NIN-1 are inputs base + k
-    auto load = [&](long m0) {
-        const long base = (long)a.o0 + PD * m0 - (T0 - 1);
-        const long v0 = base >> 1;
-        long lo = ((-a.n_hist) >> 1) - v0, hi = ((a.n_new - 1) >> 1) - v0;
-        const long seg_hi = ((wg_last + K0_NIN) >> 1) - v0;         // prefetch past the segment re-reads its last vector
-        hi = hi < seg_hi ? hi : seg_hi;
-        lo = lo < -(1L << 30) ? -(1L << 30) : (lo > (1L << 30) ? (1L << 30) : lo);
-        hi = hi < -(1L << 30) ? -(1L << 30) : (hi > (1L << 30) ? (1L << 30) : hi);
-        const int lo32 = (int)lo, hi32 = (int)hi;
-        const uint4* q = xb + v0;
-#pragma unroll
-        for (int j = 0; j < K0_NV; ++j) {
-            int r = tid + j * WV;
-            r = r < lo32 ? lo32 : r;
-            r = r > hi32 ? hi32 : r;
-            v[j] = q[r];
-        }
-    };
-    auto stage = [&](long m0) {
-        const long base = (long)a.o0 + PD * m0 - (T0 - 1);
-        const long v0 = base >> 1;
-        const int sh = (int)(base - (v0 << 1));                     // 0 or 1
-        const bool interior = (v0 << 1) >= -a.n_hist && (v0 << 1) + 2L * K0_NV * WV <= a.n_new;   // uniform
-#pragma unroll
-        for (int j = 0; j < K0_NV; ++j) {
-            const unsigned w[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const int k = 2 * (tid + j * WV) + e - sh;          // window position
-                float2 s2 = make_float2(__uint_as_float(w[2 * e]), __uint_as_float(w[2 * e + 1]));
-                if (!interior) {
-                    const long i = ((v0 + tid + (long)j * WV) << 1) + e;
-                    if (i < -a.n_hist || i >= a.n_new) s2 = make_float2(0.f, 0.f);
-                }
-                if (k >= 0 && k < K0_NIN) X[((unsigned)k % PD) * K0_JP + (unsigned)k / PD] = s2;
-            }
-        }
-    };
-
-    float2 outv[K0_P];
-#pragma unroll
-    for (int q = 0; q < K0_P; ++q) outv[q] = make_float2(0.f, 0.f);
-    long out_m0 = -1;                                               // sub-tile whose outputs sit in outv (-1: none)
-    auto flush = [&]() {
-        if (out_m0 >= 0) {
-#pragma unroll
-            for (int q = 0; q < K0_P; ++q) {
-                const long m = out_m0 + tid + q * WV;
-                if (m < a.n_out) yb[m] = outv[q];
-            }
-        }
-    };
-
-    load(m_wg0);
-#pragma unroll 1
-    for (int it = 0; it < K0_SUBS; ++it) {
-        const long m0 = m_wg0 + (long)it * K0_SUB;
-        if (m0 >= a.n_out) break;                                   // uniform
-        stage(m0);
-        phase_sync();
-        flush();                                                    // stores before the prefetch (single in-order vmcnt queue)
-        load(m0 + K0_SUB);                                          // unconditional; clamped past the stream
-        float2 acc[K0_P];
-#pragma unroll
-        for (int p = 0; p < K0_P; ++p) acc[p] = make_float2(0.f, 0.f);
-        const float2* col = X + K0_P * tid;
-#pragma unroll
-        for (int u = K0_P - 1 + T0 / PD - 1; u >= 0; --u) {        // u = 9 .. 0
-            float2 ph[PD];
-#pragma unroll
-            for (int r = 0; r < PD; ++r) ph[r] = lds_read_c(col + r * K0_JP + u);
-#pragma unroll
-            for (int p = 0; p < K0_P; ++p) {
-                const int q = p + (T0 / PD - 1) - u;                // tap block 10 q .. 10 q + 9
-                if (q >= 0 && q < T0 / PD) {
-#pragma unroll
-                    for (int rr = 0; rr < PD; ++rr) {
-                        const float h = P25FE_DEFAULT_PRE_TAPS[PD * q + rr];
-                        acc[p].x = __builtin_fmaf(h, ph[PD - 1 - rr].x, acc[p].x);
-                        acc[p].y = __builtin_fmaf(h, ph[PD - 1 - rr].y, acc[p].y);
-                    }
-                }
-            }
-        }
-#pragma unroll
-        for (int p = 0; p < K0_P; ++p) OUT[K0_P * tid + p] = acc[p];
-        phase_sync();
-#pragma unroll
-        for (int q = 0; q < K0_P; ++q) outv[q] = OUT[tid + q * WV];
-        out_m0 = m0;
-        phase_sync();
-    }
-    flush();
-}
-
 // ------------------------------------------------------------------------------------------
-// K0 and K6 on s16 and u8 input (SPEC 3.0 / 3.11: a u8 or s16 stream IS the cf32 stream of its converted samples).  The cf32
-// kernels above stay as they are, instruction for instruction; these forms repeat their construction with another window
-// loader: a lane still fetches aligned 16-byte vectors, which now hold 4 s16 or 8 u8 samples instead of 2 cf32 -- a window is
-// 8 / 4 vectors per lane in K0 (cf32: 16) and 3 / 2 in K6 (cf32: 6) --, converts them in registers and stores cf32 into the same
-// polyphase LDS rows.  From the rows on the text is the cf32 kernel's, operation for operation (tap order, one accumulator,
-// the DFT's factoring): that is what makes the outputs bit-identical to the cf32 kernel's on the converted samples.
+// K0 and K6 take cf32, s16 or u8 input (SPEC 3.0 / 3.11: a u8 or s16 stream IS the cf32 stream of its converted samples).  Each
+// stage has ONE body, predecim_body / channelise_body<FMT, LUTM>; the formats differ in the window loader alone: a lane fetches
+// aligned 16-byte vectors, which hold 2 cf32, 4 s16 or 8 u8 samples -- a window is 16 / 8 / 4 vectors per lane in K0 and
+// 6 / 3 / 2 in K6 --, wide_sample() turns an element into cf32 in registers, and cf32 goes into the polyphase LDS rows.  From the
+// rows on nothing depends on the format (tap order, one accumulator, the DFT's factoring): the outputs on u8 / s16 are
+// bit-identical to those on the converted cf32 samples.
 // Staging stores and the row pitch (= 13 mod 16; a ds_write_b64 is served in groups of 16 consecutive lanes over 16 bank pairs):
 // lane t of a group writes window position k = S t + c (S = samples per vector) to bank pair 13 (k % 10) + k / 10 (mod 16).
 // Counted over every group, vector, element and shift of a window, no format is ever worse than 2-way; the LDS-array cycles
@@ -1486,20 +1376,21 @@ __global__ __launch_bounds__(WV, P25FE_K0_WPS) void k_predecim(K0Args a)
 // staging stores than cf32 does (no pitch makes a stride of 4 or 8 samples conflict-free: the step from one lane to the next
 // is 8 P or 1 - 2 P bank pairs for pitch P, never the same odd number): the pitch stays.
 // ------------------------------------------------------------------------------------------
-struct WideConv {           // u8 only; run-time numbers of the handle (these kernels are never specialised)
+struct WideConv {           // u8 only (the cf32 entries pass none); run-time numbers of the handle (these kernels are never specialised)
     float scale, offset;    // affine table: byte b -> fma((float)b, scale, offset)
     const float* lut;       // any other table: the handle's 256 floats (device), looked up in LDS
 };
 constexpr int wide_log_spv(int fmt) { return fmt == P25FE_FMT_CF32 ? 1 : (fmt == P25FE_FMT_S16 ? 2 : 3); }   // log2(samples per 16-B vector)
 constexpr int wide_nv(int fmt, int nin) { return (nin + (1 << wide_log_spv(fmt)) + (WV << wide_log_spv(fmt)) - 1) / (WV << wide_log_spv(fmt)); }
-static_assert(wide_nv(P25FE_FMT_CF32, K0_NIN) == K0_NV, "vectors per lane");
 // sample e of a vector as cf32 (e is a constant after unrolling); lut: the table in LDS (LUTM)
 template <int FMT, bool LUTM>
 __device__ __forceinline__ float2 wide_sample(const uint4& v, int e, const WideConv& cv, const float* lut)
 {
-    static_assert(FMT == P25FE_FMT_S16 || FMT == P25FE_FMT_U8, "narrow formats");
+    static_assert(FMT == P25FE_FMT_CF32 || FMT == P25FE_FMT_S16 || FMT == P25FE_FMT_U8, "wideband formats");
     const unsigned w[4] = {v.x, v.y, v.z, v.w};
-    if constexpr (FMT == P25FE_FMT_S16) {
+    if constexpr (FMT == P25FE_FMT_CF32) {
+        return make_float2(__uint_as_float(w[2 * e]), __uint_as_float(w[2 * e + 1]));
+    } else if constexpr (FMT == P25FE_FMT_S16) {
         return s16_to_c32(w[e]);
     } else {
         const unsigned pair = w[e >> 1] >> (16 * (e & 1));          // low byte = I (SPEC 3.1); v_cvt_f32_ubyteN picks the byte
@@ -1623,6 +1514,7 @@ __device__ __forceinline__ void predecim_body(K0Args a, WideConv cv)
     }
     flush();
 }
+__global__ __launch_bounds__(WV, P25FE_K0_WPS) void k_predecim(K0Args a) { predecim_body<P25FE_FMT_CF32, false>(a, WideConv{}); }
 // s16 (LUTM false) and u8 with the table as arithmetic (false) or looked up (true)
 template <int FMT, bool LUTM>
 __global__ __launch_bounds__(WV, P25FE_K0_WPS) void k_predecim_fmt(K0Args a, WideConv cv)
@@ -1665,7 +1557,6 @@ constexpr int CZ_G = P25FE_CZ_G;                                         // c1 v
 constexpr int CZ_NIN = PD * WV + (T0 - PD);                     // 710 window positions for 64 instants
 constexpr int CZ_JP = 77;                                       // entries per phase row (>= 73), = 13 mod 16 as in K0
 static_assert(CZ_JP >= CZ_NIN / PD + 2 && CZ_JP % 16 == 13, "polyphase row pitch");
-constexpr int CZ_NV = (CZ_NIN + 2 + 2 * WV - 1) / (2 * WV);     // 16-B vectors per lane: 6
 
 struct ChzArgs {
     const float* x;         // owned sample 0 (cf32 @ 2.4 Msps), 16-B aligned
@@ -1727,143 +1618,6 @@ __device__ __forceinline__ void cz_bf4(float2& x0, float2& x1, float2& x2, float
 }
 
 #ifndef P25FE_JIT
-// (channelise_body below is this kernel with another window loader, for s16 / u8 input: a change to the DFT, the rotation or
-// the stores here is made there too -- tests/test_gpu_wide_fmt.py compares the two bit for bit)
-__global__ __launch_bounds__(WV, P25FE_CZ_WPS) void k_channelise(ChzArgs a)
-{
-    __shared__ float2 X[PD * CZ_JP];
-    __shared__ float2 ROT[CZ_M];
-    const int lane = threadIdx.x;
-    for (int k = lane; k < CZ_M; k += WV) ROT[k] = make_float2(P25FE_CHZ_W[2 * k], -P25FE_CHZ_W[2 * k + 1]);
-    const long m0 = (long)blockIdx.x * WV;
-    {   // stage the window: positions k = 0 .. CZ_NIN-1 are inputs base + k
-        const uint4* xb = reinterpret_cast<const uint4*>(a.x);
-        const long base = (long)a.o0 + PD * m0 - (T0 - 1);
-        const long v0 = base >> 1;
-        const int sh = (int)(base - (v0 << 1));
-        long lo = ((-a.n_hist) >> 1) - v0, hi = ((a.n_new - 1) >> 1) - v0;
-        lo = lo < -(1L << 30) ? -(1L << 30) : (lo > (1L << 30) ? (1L << 30) : lo);
-        hi = hi < -(1L << 30) ? -(1L << 30) : (hi > (1L << 30) ? (1L << 30) : hi);
-        const int lo32 = (int)lo, hi32 = (int)hi;
-        const uint4* q = xb + v0;
-        uint4 v[CZ_NV];
-#pragma unroll
-        for (int j = 0; j < CZ_NV; ++j) {
-            int r = lane + j * WV;
-            r = r < lo32 ? lo32 : r;
-            r = r > hi32 ? hi32 : r;
-            v[j] = q[r];
-        }
-        const bool interior = (v0 << 1) >= -a.n_hist && (v0 << 1) + 2L * CZ_NV * WV <= a.n_new;   // uniform
-#pragma unroll
-        for (int j = 0; j < CZ_NV; ++j) {
-            const unsigned w[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const int k = 2 * (lane + j * WV) + e - sh;
-                float2 s2 = make_float2(__uint_as_float(w[2 * e]), __uint_as_float(w[2 * e + 1]));
-                if (!interior) {
-                    const long i = ((v0 + lane + (long)j * WV) << 1) + e;
-                    if (i < -a.n_hist || i >= a.n_new) s2 = make_float2(0.f, 0.f);
-                }
-                if (k >= 0 && k < CZ_NIN) X[((unsigned)k % PD) * CZ_JP + (unsigned)k / PD] = s2;
-            }
-        }
-    }
-    phase_sync();
-
-    const long m = m0 + lane;
-    const unsigned nm = (unsigned)((unsigned long long)(a.abs0 + a.o0 + PD * m) % (unsigned long long)CZ_M);
-    const unsigned step2 = (CZ_C1 * nm) % (unsigned)CZ_M;       // index step of the rotation from c to c + 12
-    unsigned idx1 = 0;                                          // (c1 * nm) mod 192
-    float2* yb = reinterpret_cast<float2*>(a.y) + m;
-    const bool odd = (lane & 1) != 0;
-
-    // c1 in groups of CZ_G (a rolled loop: the c1-dependent twiddles come from CZ_TW by scalar loads): the 80 products
-    // a[p] = h[p] x[n - p] are re-formed from LDS once per group (window position 79 + 10 lane - p -> phase
-    // 9 - p % 10, column lane + 7 - p / 10) instead of living in 160 registers
-    P25FE_M_K6_STORES_ONLY;                                         // (measurement builds: the store stream alone)
-#pragma unroll 1
-    for (int c1g = 0; c1g < CZ_C1; c1g += CZ_G) {
-        float2 BB[CZ_G][CZ_C2];
-#pragma unroll
-        for (int p2 = 0; p2 < CZ_C2; ++p2) {
-            float2 a5[CZ_P1];
-#pragma unroll
-            for (int p1 = 0; p1 < CZ_P1; ++p1) {
-                const int p = CZ_C2 * p1 + p2;
-                const float2 xv = lds_read_c(X + (PD - 1 - p % PD) * CZ_JP + lane + (T0 / PD - 1) - p / PD);
-                a5[p1] = make_float2(P25FE_DEFAULT_PRE_TAPS[p] * xv.x, P25FE_DEFAULT_PRE_TAPS[p] * xv.y);
-            }
-#pragma unroll
-            for (int q = 0; q < CZ_G; ++q) {
-                const CzC* tw = CZ_TW.v[c1g + q];
-                float2 acc = a5[0];                             // p1 = 0: V12^0 = 1
-#pragma unroll
-                for (int p1 = 1; p1 < CZ_P1; ++p1) acc = cz_mac(acc, a5[p1], tw[p1 - 1]);
-                float2 bv = p2 ? cz_mul(acc, tw[4 + p2]) : acc;
-                // pin the value here: otherwise the arithmetic is sunk below ALL the (ordered, volatile) window reads of the
-                // group and their 160 result registers stay live -- spills at any useful occupancy
-                asm volatile("" : "+v"(bv.x), "+v"(bv.y));
-                BB[q][p2] = bv;
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < CZ_G; ++q) {
-        const int c1 = c1g + q;
-        // 16-point DFT, kernel V16^{c2 p2} = e^{+j 2 pi c2 p2 / 16}: p2 = 4 a + b, c2 = e + 4 f
-#pragma unroll
-        for (int b = 0; b < 4; ++b) cz_bf4(BB[q][b], BB[q][4 + b], BB[q][8 + b], BB[q][12 + b]);        // slot 4 e + b <- Z[b][e]
-#pragma unroll
-        for (int e = 1; e < 4; ++e)
-#pragma unroll
-            for (int b = 1; b < 4; ++b) {
-                const int k = 12 * (e * b);                     // V16^{e b} = W[12 e b]
-                BB[q][4 * e + b] = cz_mul_const(BB[q][4 * e + b], P25FE_CHZ_W[2 * k], P25FE_CHZ_W[2 * k + 1]);
-            }
-        unsigned idx[4];                                        // rotation index of c = c1 + 12 (e + 4 f), by e
-        idx[0] = idx1;
-#pragma unroll
-        for (int e = 1; e < 4; ++e) { idx[e] = idx[e - 1] + step2; idx[e] = idx[e] >= (unsigned)CZ_M ? idx[e] - CZ_M : idx[e]; }
-        const unsigned step8 = (4u * step2) % (unsigned)CZ_M;   // from f to f + 1: c grows by 48
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            cz_bf4(BB[q][4 * e], BB[q][4 * e + 1], BB[q][4 * e + 2], BB[q][4 * e + 3]);                 // slot 4 e + f <- Y[e + 4 f]
-            unsigned ix = idx[e];
-            float2 o4[4];
-#pragma unroll
-            for (int f = 0; f < 4; ++f) {
-                const float2 rot = ROT[ix];
-                const float2 yv = BB[q][4 * e + f];
-                o4[f] = make_float2(__builtin_fmaf(-yv.y, rot.y, yv.x * rot.x), __builtin_fmaf(yv.y, rot.x, yv.x * rot.y));
-                ix += step8; ix = ix >= (unsigned)CZ_M ? ix - CZ_M : ix;
-            }
-            // Streaming stores (nt: 22 GB of output per minute of capture never fit a cache; measured +4.5 %), 16 bytes per
-            // lane: the lanes of a pair swap one value each (DPP quad_perm [1,0,3,2]) so that the even lane writes instants
-            // (m, m + 1) of channel row f and the odd lane instants (m - 1, m) of row f + 1 -- half as many store
-            // instructions for the same 512 contiguous bytes per row (the store-only build: 0.416 against 0.458 ms per
-            // 1.44e7 input samples).  Rows are padded to whole tiles: no predicate.
-#pragma unroll
-            for (int f = 0; f < 4; f += 2) {
-                const float2 mine = odd ? o4[f + 1] : o4[f];        // what this lane keeps (its own instant)
-                const float2 give = odd ? o4[f] : o4[f + 1];        // what its partner needs
-                float2 got;
-                got.x = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(give.x), 0xB1, 0xf, 0xf, true));
-                got.y = __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(give.y), 0xB1, 0xf, 0xf, true));
-                typedef float __attribute__((ext_vector_type(4))) f32x4;
-                f32x4 ov;
-                ov.x = odd ? got.x : mine.x; ov.y = odd ? got.y : mine.y;      // instant m - 1 (odd lane) / m (even lane)
-                ov.z = odd ? mine.x : got.x; ov.w = odd ? mine.y : got.y;      // instant m (odd lane) / m + 1 (even lane)
-                const int c = c1 + CZ_C1 * (e + 4 * (f + (odd ? 1 : 0)));
-                __builtin_nontemporal_store(ov, reinterpret_cast<f32x4*>(yb - (odd ? 1 : 0) + (size_t)c * a.y_stride));
-            }
-        }
-        idx1 += nm; idx1 = idx1 >= (unsigned)CZ_M ? idx1 - CZ_M : idx1;
-        }
-    }
-}
-
-static_assert(wide_nv(P25FE_FMT_CF32, CZ_NIN) == CZ_NV, "vectors per lane");
 template <int FMT, bool LUTM>
 __device__ __forceinline__ void channelise_body(ChzArgs a, WideConv cv)
 {
@@ -2005,6 +1759,7 @@ __device__ __forceinline__ void channelise_body(ChzArgs a, WideConv cv)
         }
     }
 }
+__global__ __launch_bounds__(WV, P25FE_CZ_WPS) void k_channelise(ChzArgs a) { channelise_body<P25FE_FMT_CF32, false>(a, WideConv{}); }
 template <int FMT, bool LUTM>
 __global__ __launch_bounds__(WV, P25FE_CZ_WPS) void k_channelise_fmt(ChzArgs a, WideConv cv)
 {

@@ -4,7 +4,8 @@ A wideband u8 or s16 stream IS the cf32 stream of its converted samples, so ever
 (A) the narrow call's output equals, as uint32, the cf32 call's output on the converted samples with the same n_hist / abs0 /
     offset;
 (B) where abs0 == offset, it equals the oracle on the converted samples: O.PreDecim bit for bit, O.channelise within SPEC 3.11's
-    own 2e-6 * sum|h| * max|x|.
+    own 2e-6 * sum|h| * max|x|.  Tests 1, 2 and 5 hold the cf32 call's output to (B) as well: cf32 is one more instantiation of the
+    same kernel body, checked on its own and not only through (A).
 The conversions are computed here in float64 and rounded once, which is fma((float)b, scale, offset) exactly (8 x 24 bits and one
 addition fit a double), and (float)v * 2^-15, which is exact.
 """
@@ -108,6 +109,7 @@ def test_predecim_whole_stream(O, FE, fmt):
     assert same_bits(y[:, :no], yc[:, :no])                          # (A)
     ref = O.PreDecim().feed(cf)
     assert len(ref) == no and np.array_equal(bits(y[0, :no].cpu().numpy()).ravel(), bits(ref).ravel())     # (B)
+    assert np.array_equal(bits(yc[0, :no].cpu().numpy()).ravel(), bits(ref).ravel())                       # (B), cf32
 
 
 # ---- 2: grid and history sweep -----------------------------------------------------------------------------------------------
@@ -136,6 +138,7 @@ def test_predecim_grid_and_history_sweep(O, FE, fmt):
                     if r == 0:                                                                        # (B)
                         assert no == len(ref), (offset, n_hist, n)
                         assert np.array_equal(bits(y[0, :no].cpu().numpy()).ravel(), bits(ref).ravel()), (offset, n_hist, n)
+                        assert np.array_equal(bits(yc[0, :no].cpu().numpy()).ravel(), bits(ref).ravel()), (offset, n_hist, n)
     assert seen_empty and seen_one
 
 
@@ -232,7 +235,9 @@ def test_channeliser(O, FE, fmt):
     y, no = fe.channelise_dev(tx[:n])
     yc, _ = fe.channelise_dev(tc[:n])
     assert no == 200 and same_bits(y[:, :no], yc[:, :no])
-    assert np.abs(host(y, no) - O.channelise(cf[:n])).max() <= tol
+    ref = O.channelise(cf[:n])
+    assert np.abs(host(y, no) - ref).max() <= tol
+    assert np.abs(host(yc, no) - ref).max() <= tol                                                    # cf32
     for offset, n_hist in ((1000, 80), (1048, 96), (1504, 1504)):
         kw = dict(n_hist=n_hist, abs0=offset, offset=offset)
         y, no = fe.channelise_dev(tx[:offset + n], **kw)
@@ -240,6 +245,7 @@ def test_channeliser(O, FE, fmt):
         assert no == noc and no >= 200 and same_bits(y[:, :no], yc[:, :no]), offset                   # (A)
         ref = O.channelise(cf[offset - n_hist:offset + n], n_hist=n_hist, abs0=offset)
         assert ref.shape[1] == no and np.abs(host(y, no) - ref).max() <= tol, offset                  # (B)
+        assert np.abs(host(yc, no) - ref).max() <= tol, offset                                        # (B), cf32
         for k, r in ((1, 0), (1, 1), (3, 7), (5, 9), (1 << 20, 101), (7, 191)):                       # the mixer phase moves
             kw = dict(n_hist=n_hist, abs0=offset + 192 * k + r, offset=offset)
             y, no = fe.channelise_dev(tx[:offset + n], **kw)
