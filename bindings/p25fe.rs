@@ -146,6 +146,13 @@ pub struct WindowsStats {
 }
 
 pub enum Handle {}
+/// p25fe_resampler_t: the rational resampler of docs/SPEC.md 3.0b (made from a Handle, which must outlive it)
+pub enum Resampler {}
+/// P25FE_RS_MAX_L / _M / _T / _TABLE: L <= 32, L < M <= 1024, T <= 1024, L * T <= 4096, gcd(L, M) = 1
+pub const RS_MAX_L: i32 = 32;
+pub const RS_MAX_M: i32 = 1024;
+pub const RS_MAX_T: i32 = 1024;
+pub const RS_MAX_TABLE: i32 = 4096;
 pub enum Shard {}
 
 #[link(name = "p25fe")]
@@ -190,6 +197,15 @@ extern "C" {
     pub fn p25fe_predecim_fmt_dev(h: *mut Handle, d_iq: *const c_void, fmt: c_int, ch_stride: usize, n_hist: usize, n: usize, abs_first: u64,
                                   d_out: *mut f32, out_stride: usize, stream: *mut c_void) -> c_int;
     pub fn p25fe_n_predecim(abs0: u64, n: usize) -> usize;
+    // rational resampler: any tuner rate -> 240 ksps (taps[j * L + p] = tap j of phase p)
+    pub fn p25fe_resampler_design(fs_in_hz: u32, l: *mut i32, m: *mut i32, t: *mut i32, taps: *mut f32, cap: usize) -> c_int;
+    pub fn p25fe_resampler_create(h: *mut Handle, l: i32, m: i32, t: i32, taps: *const f32, out: *mut *mut Resampler) -> c_int;
+    pub fn p25fe_resampler_destroy(rs: *mut Resampler);
+    pub fn p25fe_resampler_reset(rs: *mut Resampler) -> c_int;
+    pub fn p25fe_n_resample(l: i32, m: i32, abs_first: u64, n: usize) -> usize;
+    pub fn p25fe_resample_dev(rs: *mut Resampler, d_iq: *const c_void, fmt: c_int, ch_stride: usize, n_hist: usize, n: usize, abs_first: u64,
+                              d_out: *mut f32, out_stride: usize, stream: *mut c_void) -> c_int;
+    pub fn p25fe_resample(rs: *mut Resampler, iq: *const c_void, fmt: c_int, n: usize, out: *mut f32, cap: usize, n_out: *mut usize) -> c_int;
     pub fn p25fe_n_baseband(abs0: u64, n: usize) -> usize;
     pub fn p25fe_slice_dev(h: *mut Handle, d_bb: *const f32, bb_stride: usize, n_hist_bb: usize, n_bb: usize, abs_bb0: u64,
                            d_anchor_in: *const Anchor, d_dibits: *mut u8, dibit_stride: usize, d_sync_pos: *mut i64,

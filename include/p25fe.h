@@ -359,6 +359,55 @@ size_t p25fe_n_predecim(uint64_t abs0, size_t n);
 int p25fe_predecim_fmt_dev(p25fe_t *h, const void *d_iq, int fmt, size_t ch_stride, size_t n_hist, size_t n,
                            uint64_t abs_first /* = p25fe_predecim_dev's abs0 */, float *d_out, size_t out_stride, void *stream);
 
+/* ---- rational resampler: any tuner sample rate -> 240 ksps (docs/SPEC.md 3.0b) -------------------
+ * A polyphase FIR resampler by L / M (= 240000 / fs_in in lowest terms) with a caller-supplied table taps[0 .. L*T): T taps per
+ * phase, index j*L + p is tap j of phase p.  With x[n] = 0 for n < 0:
+ *     u = m*M + (M-1);  n_m = u div L;  p_m = u mod L;  y[m] = sum_{j<T} taps[j*L + p_m] x[n_m - j]   (fp32 fma chain, j ascending)
+ * L = 1, M = 10, T = 80 with p25fe_spec.h's pre-decimator taps IS p25fe_predecim_dev, bit for bit.  A range [abs_first,
+ * abs_first + n) owns the outputs whose n_m lies in it; n_hist >= T - 1 gives exact continuation; the position grid is M.
+ * Limits (P25FE_ERR_ARG otherwise): gcd(L, M) = 1, 1 <= L <= P25FE_RS_MAX_L, L < M <= P25FE_RS_MAX_M, 1 <= T <= P25FE_RS_MAX_T,
+ * L*T <= P25FE_RS_MAX_TABLE, finite taps. */
+#define P25FE_RS_MAX_L 32
+#define P25FE_RS_MAX_M 1024
+#define P25FE_RS_MAX_T 1024
+#define P25FE_RS_MAX_TABLE 4096
+#define P25FE_RS_RATE_OUT_HZ 240000u
+typedef struct p25fe_resampler p25fe_resampler_t;
+
+/* The table for a tuner rate, no device needed: L / M = 240000 / fs_in_hz reduced, T = ceil(fs_in_hz / 30000) taps per phase, a
+ * Kaiser(beta = 7.0)-windowed sinc of L*T points with its cutoff at 60 kHz (at the rate L * fs_in_hz), scaled to sum L, evaluated in
+ * double and rounded once (at 2.4 Msps: the design rule of the pre-decimator's own table).  *L, *M, *T are always filled when the
+ * ratio is within the limits; taps (cap floats) is filled when cap >= L*T, P25FE_ERR_CAPACITY otherwise (taps may then be null).
+ * P25FE_ERR_ARG: a null L / M / T, fs_in_hz = 0, or a reduced ratio outside the limits (fs_in_hz = 240000 among them). */
+int p25fe_resampler_design(uint32_t fs_in_hz, int32_t *L, int32_t *M, int32_t *T, float *taps, size_t cap);
+
+/* A resampler on h's device, for h's n_channels and u8 conversion; h must outlive every USE of it (p25fe_resampler_destroy alone
+ * is safe after p25fe_destroy(h): it does not read the handle).  The arguments are checked before any
+ * device is touched.  The object holds the table's device copy and the state of the host streaming form. */
+int p25fe_resampler_create(p25fe_t *h, int32_t L, int32_t M, int32_t T, const float *taps, p25fe_resampler_t **out);
+void p25fe_resampler_destroy(p25fe_resampler_t *rs);
+int p25fe_resampler_reset(p25fe_resampler_t *rs);      /* the host streaming form restarts at position 0 with zero history */
+
+/* outputs a range owns: floor((abs_first + n) L / M) - floor(abs_first L / M); exact for every uint64_t abs_first (0 for a ratio
+ * outside the limits) */
+size_t p25fe_n_resample(int32_t L, int32_t M, uint64_t abs_first, size_t n);
+
+/* A device-resident range, conventions as p25fe_predecim_fmt_dev: d_iq points at owned sample 0 of channel 0 and is 16-byte
+ * aligned, ch_stride is a multiple of 2 / 4 / 8 samples (cf32 / s16 / u8), only the aligned 16-byte vectors that hold samples
+ * [-n_hist, n) of a channel are read.  Writes exactly p25fe_n_resample(L, M, abs_first, n) cf32 samples per channel to d_out +
+ * c * out_stride (complex samples) and nothing beyond them; enqueues on `stream`, synchronises nothing.  u8 / s16 input gives,
+ * bit for bit, the cf32 call's output on the converted samples.  P25FE_ERR_ARG: null or misaligned pointer, unknown format,
+ * out_stride < the count, abs_first >= 2^62. */
+int p25fe_resample_dev(p25fe_resampler_t *rs, const void *d_iq, int fmt, size_t ch_stride, size_t n_hist, size_t n,
+                       uint64_t abs_first, float *d_out, size_t out_stride, void *stream);
+
+/* Host streaming form: iq holds n new samples per channel, channel-major ([n_channels][n] in the format's units), out is
+ * [n_channels][cap] cf32; *n_out = samples written per channel.  The object keeps the last T - 1 samples and the stream position:
+ * any chunking gives the same concatenated output.  P25FE_ERR_CAPACITY (cap too small; *n_out = the count needed) leaves the
+ * state untouched; P25FE_ERR_FORMAT when the format differs from the stream's first call (p25fe_resampler_reset starts a new
+ * stream).  Synchronous. */
+int p25fe_resample(p25fe_resampler_t *rs, const void *iq, int fmt, size_t n, float *out, size_t cap, size_t *n_out);
+
 /* stages 6-7 on device baseband.  d_bb points at the first owned sample; n_hist_bb valid
  * samples precede it; abs_bb0 is its absolute index; d_anchor_in (nullable = no lock) is the
  * carry-in per channel.  d_result[c] is filled per channel.

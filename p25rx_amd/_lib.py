@@ -15,6 +15,7 @@ ABI_VERSION = 6
 FMT_CF32, FMT_U8, FMT_S16 = 0, 1, 2
 S16_SCALE = 2.0 ** -15                    # P25FE_S16_SCALE: an int16 v is the sample (float)v * 2^-15, exactly
 MAX_POSITION = 1 << 62                   # P25FE_MAX_POSITION: abs0 / abs_bb0 from here on are P25FE_ERR_ARG
+RS_MAX_L, RS_MAX_M, RS_MAX_T, RS_MAX_TABLE = 32, 1024, 1024, 4096   # P25FE_RS_MAX_*: limits of the rational resampler
 
 OK, ERR_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_CAPACITY, ERR_FORMAT, ERR_NOMEM, ERR_JIT, ERR_TIMEOUT = 0, -1, -2, -3, -4, -5, -6, -7, -8
 CLOCK_FIXED, CLOCK_TRACKING, CLOCK_TRACKING_RESLICE, CLOCK_CAUSAL_OK = 0, 1, 2, 0x100
@@ -76,6 +77,8 @@ SYMBOLS = [
     "p25fe_shard_pass1_head", "p25fe_shard_pipe_begin", "p25fe_shard_pipe_end", "p25fe_rx_stream", "p25fe_shard_head_check", "p25fe_shard_pass1_k1", "p25fe_streams_share_queue", "p25fe_shard_pass2_dev", "p25fe_shard_compact_from_dev", "p25fe_probe_variant", "p25fe_n_baseband_h",
     "p25fe_demod_s16", "p25fe_run_s16", "p25fe_format_variant", "p25fe_probe_format_variant",
     "p25fe_predecim_fmt_dev", "p25fe_channelise_fmt_dev",
+    "p25fe_resampler_design", "p25fe_resampler_create", "p25fe_resampler_destroy", "p25fe_resampler_reset", "p25fe_n_resample",
+    "p25fe_resample_dev", "p25fe_resample",
 ]
 
 
@@ -170,6 +173,16 @@ def load():
     L.p25fe_predecim_dev.argtypes = [vp, vp, sz, sz, sz, u64, vp, sz, vp]
     L.p25fe_predecim_fmt_dev.argtypes = [vp, vp, C.c_int, sz, sz, sz, u64, vp, sz, vp]
     L.p25fe_channelise_fmt_dev.argtypes = [vp, vp, C.c_int, sz, sz, u64, vp, sz, vp]
+    pi32 = C.POINTER(C.c_int32)
+    L.p25fe_resampler_design.argtypes = [C.c_uint32, pi32, pi32, pi32, vp, sz]
+    L.p25fe_resampler_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, C.POINTER(vp)]
+    L.p25fe_resampler_destroy.argtypes = [vp]
+    L.p25fe_resampler_destroy.restype = None
+    L.p25fe_resampler_reset.argtypes = [vp]
+    L.p25fe_n_resample.argtypes = [C.c_int32, C.c_int32, u64, sz]
+    L.p25fe_n_resample.restype = sz
+    L.p25fe_resample_dev.argtypes = [vp, vp, C.c_int, sz, sz, sz, u64, vp, sz, vp]
+    L.p25fe_resample.argtypes = [vp, vp, C.c_int, sz, vp, sz, psz]
     L.p25fe_n_predecim.argtypes = [u64, sz]
     L.p25fe_n_predecim.restype = sz
     L.p25fe_n_baseband.argtypes = [u64, sz]

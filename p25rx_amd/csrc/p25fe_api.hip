@@ -11,6 +11,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <chrono>
 #include <new>
 #include <utility>
@@ -1333,7 +1334,209 @@ static int launch_k6(p25fe_t* h, const void* d_iq, int fmt, size_t n_hist, size_
     return P25FE_OK;
 }
 
+// --------------------------------------------------------------------------------------------
+// Rational resampler (SPEC 3.0b; kernel: k_resample).  The object: the ratio, the table's device copy in the kernel's layout, and the
+// state of the host streaming form (position, format, the last T - 1 samples per channel as they came in).
+// --------------------------------------------------------------------------------------------
+struct p25fe_resampler {
+    p25fe_t* h = nullptr;
+    int device = 0;                        // h's, kept here: destroying the object must not read the handle
+    int L = 0, M = 0, T = 0, TP = 0;
+    DevBuf d_taps, d_in, d_out;
+    uint64_t pos = 0;                      // samples consumed per channel
+    int fmt = -1;                          // format of the stream (-1: none yet)
+    std::vector<unsigned char> stage;      // host image of the device rows of one p25fe_resample call
+    std::vector<unsigned char> hist;       // [C][T - 1] samples in the stream's format, oldest first (the valid ones are the last min(pos, T - 1))
+};
+
+static bool rs_ratio_ok(int64_t L, int64_t M)
+{
+    if (L < 1 || L > P25FE_RS_MAX_L || M <= L || M > P25FE_RS_MAX_M) return false;
+    int64_t a = M, b = L;
+    while (b) { const int64_t t = a % b; a = b; b = t; }
+    return a == 1;
+}
+static bool rs_shape_ok(int64_t L, int64_t M, int64_t T)
+{
+    return rs_ratio_ok(L, M) && T >= 1 && T <= P25FE_RS_MAX_T && L * T <= P25FE_RS_MAX_TABLE;
+}
+// floor(a L / M) without a 64-bit product that overflows (M <= 1024, L <= 32)
+static inline uint64_t rs_floor(uint64_t a, uint64_t L, uint64_t M) { return (a / M) * L + ((a % M) * L) / M; }
+// modified Bessel function I0 from its power series (terms fall below 1e-17 of the sum well inside 64 of them at beta = 7)
+static double rs_i0(double x)
+{
+    double s = 1.0, t = 1.0;
+    for (int k = 1; k < 64; ++k) { t *= (x / (2.0 * k)) * (x / (2.0 * k)); s += t; if (t < 1e-18 * s) break; }
+    return s;
+}
+
+static int launch_resample(p25fe_resampler* rs, const void* d_iq, int fmt, size_t ch_stride, size_t n_hist, size_t n, uint64_t abs_first,
+                           float* d_out, size_t out_stride, hipStream_t st)
+{
+    p25fe_t* h = rs->h;
+    if (!d_iq || !d_out || position_refused(abs_first)) return P25FE_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_iq) & 15u) != 0 || (reinterpret_cast<uintptr_t>(d_out) & 7u) != 0 ||
+        (h->C > 1 && ch_stride % fmt_stride_unit(fmt) != 0))
+        return P25FE_ERR_ARG;
+    const size_t n_out = p25fe_n_resample(rs->L, rs->M, abs_first, n);
+    if (out_stride < n_out) return P25FE_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (n_out == 0) return P25FE_OK;
+    const int L = rs->L, M = rs->M, T = rs->T;
+    RsArgs a;
+    a.x = d_iq; a.ch_stride = (long)ch_stride; a.n_hist = (long)n_hist; a.n_new = (long)n;
+    a.y = d_out; a.y_stride = (long)out_stride; a.n_out = (long)n_out;
+    a.taps = rs->d_taps.as<float>(); a.L = L; a.M = M; a.T = T; a.TP = rs->TP;
+    // owned output 0 is output floor(abs_first L / M) of the stream; with abs_first = qa M + ra it is output qa L + mr, whose
+    // u = (qa L + mr) M + M - 1: its input index is qa M + (mr M + M - 1) div L -- only ra matters (the position grid is M)
+    const int ra = (int)(abs_first % (uint64_t)M), mr = ra * L / M, ur = mr * M + M - 1;
+    a.p0 = ur % L; a.d0 = ur / L - ra;
+    // the sub-tile fits the window: its last output's newest sample sits at position <= (L - 1 + (tile - 1) M) / L + T - 1 < RS_NIN
+    const int fit = 1 + (RS_NIN - T) * L / M;
+    a.gl = WV - WV % L;
+    if (fit >= a.gl) { a.R = fit / a.gl < RS_R ? fit / a.gl : RS_R; a.tile = a.gl * a.R; }
+    else { a.R = 1; a.tile = fit; }
+    const size_t per_wg = (size_t)a.tile * RS_SUBS;
+    const dim3 grid((unsigned)((n_out + per_wg - 1) / per_wg), (unsigned)h->C);
+    const size_t lds = sizeof(float) * (size_t)L * (size_t)rs->TP;
+    const WideConv cv = wide_conv_of(h);
+    (void)hipGetLastError();                                        // the check below is for THIS launch: drop what an earlier call of the thread left behind
+    if (fmt == P25FE_FMT_CF32) hipLaunchKernelGGL((k_resample<P25FE_FMT_CF32, false>), grid, dim3(WV), lds, st, a, cv);
+    else if (fmt == P25FE_FMT_S16) hipLaunchKernelGGL((k_resample<P25FE_FMT_S16, false>), grid, dim3(WV), lds, st, a, cv);
+    else if (cv.lut) hipLaunchKernelGGL((k_resample<P25FE_FMT_U8, true>), grid, dim3(WV), lds, st, a, cv);
+    else hipLaunchKernelGGL((k_resample<P25FE_FMT_U8, false>), grid, dim3(WV), lds, st, a, cv);
+    HIPCHK(h, hipGetLastError());
+    return P25FE_OK;
+}
+
 extern "C" {
+
+int p25fe_resampler_design(uint32_t fs_in_hz, int32_t* L, int32_t* M, int32_t* T, float* taps, size_t cap)
+{
+    if (!L || !M || !T || fs_in_hz == 0) return P25FE_ERR_ARG;
+    uint64_t a = P25FE_RS_RATE_OUT_HZ, b = fs_in_hz;
+    while (b) { const uint64_t t = a % b; a = b; b = t; }
+    const int64_t l = (int64_t)(P25FE_RS_RATE_OUT_HZ / a), m = (int64_t)(fs_in_hz / a);
+    const int64_t t = ((int64_t)fs_in_hz + 29999) / 30000;
+    if (!rs_shape_ok(l, m, t)) return P25FE_ERR_ARG;
+    *L = (int32_t)l; *M = (int32_t)m; *T = (int32_t)t;
+    const size_t N = (size_t)(l * t);
+    if (cap < N || !taps) return P25FE_ERR_CAPACITY;
+    const double pi = 3.14159265358979323846;
+    const double fc = 60000.0 / ((double)l * (double)fs_in_hz);       // cutoff in cycles per sample of the prototype's rate
+    const double mid = ((double)N - 1.0) / 2.0, den = rs_i0(7.0);
+    std::vector<double> hd(N);
+    double sum = 0.0;
+    for (size_t k = 0; k < N; ++k) {
+        const double x = (double)k - mid, arg = 2.0 * fc * x;
+        const double sinc = arg == 0.0 ? 1.0 : sin(pi * arg) / (pi * arg);
+        const double r = N > 1 ? x / mid : 0.0;
+        const double w = rs_i0(7.0 * sqrt(r * r < 1.0 ? 1.0 - r * r : 0.0)) / den;
+        hd[k] = 2.0 * fc * sinc * w;
+        sum += hd[k];
+    }
+    for (size_t k = 0; k < N; ++k) taps[k] = (float)(hd[k] * (double)l / sum);
+    return P25FE_OK;
+}
+
+size_t p25fe_n_resample(int32_t L, int32_t M, uint64_t abs_first, size_t n)
+{
+    if (!rs_ratio_ok(L, M)) return 0;
+    // floor((abs_first + n) L / M) - floor(abs_first L / M) with abs_first + n split so that no sum wraps: the quotients and
+    // the remainders add up separately
+    const uint64_t l = (uint64_t)L, m = (uint64_t)M;
+    const uint64_t ra = abs_first % m, qn = (uint64_t)n / m, rn = (uint64_t)n % m;
+    // abs_first = qa m + ra, end = (qa + qn) m + (ra + rn): floor(end l / m) = (qa + qn) l + floor((ra + rn) l / m), and qa l cancels
+    return (size_t)(qn * l + ((ra + rn) * l) / m - (ra * l) / m);
+}
+
+int p25fe_resampler_create(p25fe_t* h, int32_t L, int32_t M, int32_t T, const float* taps, p25fe_resampler_t** out)
+{
+    if (out) *out = nullptr;
+    if (!out || !rs_shape_ok(L, M, T) || !taps || !h) return P25FE_ERR_ARG;      // (the shape first: it needs neither table nor handle)
+    for (int k = 0; k < L * T; ++k) if (!finite_f(taps[k])) return P25FE_ERR_ARG;
+    p25fe_resampler* rs = new (std::nothrow) p25fe_resampler;
+    if (!rs) return P25FE_ERR_NOMEM;
+    rs->h = h; rs->device = h->cfg.device; rs->L = L; rs->M = M; rs->T = T; rs->TP = rs_tap_pitch(T);
+    // the kernel's layout: phase-major rows of pitch TP, the pad zero
+    std::vector<float> tab((size_t)L * rs->TP, 0.0f);
+    for (int p = 0; p < L; ++p) for (int j = 0; j < T; ++j) tab[(size_t)p * rs->TP + j] = taps[(size_t)j * L + p];
+    rs->hist.assign((size_t)h->C * (size_t)(T - 1) * 8, 0);
+    int rc = P25FE_OK;
+    if (hipSetDevice(h->cfg.device) != hipSuccess || rs->d_taps.ensure(tab.size() * sizeof(float)) != hipSuccess ||
+        hipMemcpy(rs->d_taps.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+        rc = P25FE_ERR_HIP;
+    if (rc) { h->last_hip = (int)hipGetLastError(); delete rs; return rc; }
+    *out = rs;
+    return P25FE_OK;
+}
+
+void p25fe_resampler_destroy(p25fe_resampler_t* rs)
+{
+    if (!rs) return;
+    (void)hipSetDevice(rs->device);
+    delete rs;
+}
+
+int p25fe_resampler_reset(p25fe_resampler_t* rs)
+{
+    if (!rs) return P25FE_ERR_ARG;
+    rs->pos = 0; rs->fmt = -1;
+    std::fill(rs->hist.begin(), rs->hist.end(), (unsigned char)0);
+    return P25FE_OK;
+}
+
+int p25fe_resample_dev(p25fe_resampler_t* rs, const void* d_iq, int fmt, size_t ch_stride, size_t n_hist, size_t n, uint64_t abs_first,
+                       float* d_out, size_t out_stride, void* stream)
+{
+    if (!rs || !rs->h || !wide_fmt_known(fmt)) return P25FE_ERR_ARG;
+    return launch_resample(rs, d_iq, fmt, ch_stride, n_hist, n, abs_first, d_out, out_stride, (hipStream_t)stream);
+}
+
+int p25fe_resample(p25fe_resampler_t* rs, const void* iq, int fmt, size_t n, float* out, size_t cap, size_t* n_out)
+{
+    if (!rs || !rs->h || !n_out || !wide_fmt_known(fmt) || (n && !iq)) return P25FE_ERR_ARG;
+    if (rs->fmt >= 0 && fmt != rs->fmt) return P25FE_ERR_FORMAT;
+    if (position_refused(rs->pos) || n >= P25FE_MAX_POSITION) return P25FE_ERR_ARG;
+    p25fe_t* h = rs->h;
+    const size_t C = (size_t)h->C, bps = fmt_bytes(fmt), keep = (size_t)rs->T - 1;
+    const size_t no = p25fe_n_resample(rs->L, rs->M, rs->pos, n);
+    *n_out = no;
+    if (no > cap || (no && !out)) return P25FE_ERR_CAPACITY;
+    const size_t n_hist = rs->pos < keep ? (size_t)rs->pos : keep;
+    if (no) {
+        // device rows: [history, right-aligned in `lead` slots | n new samples], owned sample 0 of every row 16-byte aligned
+        const size_t lead = round_up(keep, 8), stride = lead + round_up(n, 8);
+        HIPCHK(h, hipSetDevice(h->cfg.device));
+        HIPCHK(h, rs->d_in.ensure(C * stride * bps));
+        HIPCHK(h, rs->d_out.ensure(C * no * sizeof(float) * 2));
+        unsigned char* din = rs->d_in.as<unsigned char>();
+        const unsigned char* src = static_cast<const unsigned char*>(iq);
+        // the rows are put together on the host and go over in ONE copy (no transfers of a few bytes to odd addresses)
+        rs->stage.assign(C * stride * bps, 0);
+        for (size_t c = 0; c < C; ++c) {
+            unsigned char* row = rs->stage.data() + c * stride * bps;
+            if (n_hist) memcpy(row + (lead - n_hist) * bps, rs->hist.data() + (c * keep + keep - n_hist) * bps, n_hist * bps);
+            memcpy(row + lead * bps, src + c * n * bps, n * bps);
+        }
+        HIPCHK(h, hipMemcpyAsync(din, rs->stage.data(), rs->stage.size(), hipMemcpyHostToDevice, h->stream));
+        if (int rc = launch_resample(rs, din + lead * bps, fmt, stride, n_hist, n, rs->pos, rs->d_out.as<float>(), no, h->stream)) return rc;
+        for (size_t c = 0; c < C; ++c)
+            HIPCHK(h, hipMemcpyAsync(out + c * cap * 2, rs->d_out.as<float>() + c * no * 2, no * sizeof(float) * 2, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    // the state moves: the last T - 1 samples of [history | new]
+    if (keep) {
+        const unsigned char* src = static_cast<const unsigned char*>(iq);
+        for (size_t c = 0; c < C; ++c) {
+            unsigned char* hc = rs->hist.data() + c * keep * bps;
+            if (n >= keep) memcpy(hc, src + (c * n + n - keep) * bps, keep * bps);
+            else { memmove(hc, hc + n * bps, (keep - n) * bps); memcpy(hc + (keep - n) * bps, src + c * n * bps, n * bps); }
+        }
+    }
+    rs->pos += n; rs->fmt = fmt;
+    return P25FE_OK;
+}
 
 // --------------------------------------------------------------------------------------------
 // device-resident ranges

@@ -1522,6 +1522,209 @@ __global__ __launch_bounds__(WV, P25FE_K0_WPS) void k_predecim_fmt(K0Args a, Wid
     static_assert(FMT == P25FE_FMT_S16 ? !LUTM : FMT == P25FE_FMT_U8, "narrow formats only");
     predecim_body<FMT, LUTM>(a, cv);
 }
+
+// ------------------------------------------------------------------------------------------
+// K0b: rational resampler L / M (SPEC 3.0b): any tuner rate -> 240 ksps, caller-supplied polyphase table; L, M, T and the
+// taps are run-time data.  Same construction as K0 (one wave per workgroup, K0's window loader, next window prefetched into
+// registers, stores one iteration late), but a lane OWNS outputs: lane t computes the outputs k = t + GL r (r < R <= 4) of a
+// sub-tile, GL = 64 - 64 % L.  GL is a multiple of L, so a lane's R outputs share one phase -- one tap read feeds R packed
+// FMAs -- and their windows lie GL M / L samples apart; consecutive lanes hold consecutive outputs, so their window reads step
+// by about M / L samples (irregular; the banks they hit depend on the ratio) and the output stores are whole runs of GL
+// samples without an LDS transposition.  The window is LINEAR in LDS (X[k] = x[base + k], RS_NIN positions, one size for
+// every ratio): the host fits the sub-tile to it -- tile = min(GL R, 1 + (RS_NIN - T) L / M) outputs --, so a large M / L or a
+// long table costs lanes, not LDS.  The table sits in dynamic LDS in phase-major rows of odd pitch TP (lanes of different
+// phases read different banks, lanes of one phase broadcast).
+// 64-bit positions: the host reduces abs_first to (p0, d0), the phase and the input index of owned output 0; a workgroup
+// divides one 64-bit product by L, everything after it is 32-bit arithmetic on a `long` window base.
+// ------------------------------------------------------------------------------------------
+constexpr int RS_R = 4;                      // outputs per lane (register block of one phase)
+constexpr int RS_SUBS = 4;                   // sub-tiles per workgroup
+constexpr int RS_NIN = 2040;                 // window positions: 16 / 8 / 4 vectors per lane cover it at every alignment
+constexpr int RS_WPS = 2;
+static_assert(RS_R == 4 && RS_NIN >= P25FE_RS_MAX_T + 1 && RS_NIN + 7 <= 2048, "window holds the longest table and fits the loader");
+constexpr int rs_tap_pitch(int T) { return T | 1; }
+
+struct RsArgs {
+    const void* x;          // owned sample 0 of channel 0, 16-B aligned
+    long ch_stride;         // samples
+    long n_hist, n_new;
+    float* y;               // cf32 out, channel 0
+    long y_stride;          // samples
+    long n_out;
+    const float* taps;      // device table, phase-major: tap j of phase p at [p * TP + j] (L * TP floats)
+    int L, M, T, TP;
+    int p0, d0;             // owned output 0: phase, and input index relative to owned sample 0
+    int gl, tile, R;        // lanes in use, outputs per sub-tile, outputs per lane (tile = gl * R, or tile < gl and R = 1)
+};
+
+template <int FMT, bool LUTM>
+__global__ __launch_bounds__(WV, RS_WPS) void k_resample(RsArgs a, WideConv cv)
+{
+    static_assert(FMT == P25FE_FMT_U8 || !LUTM, "only u8 has a table");
+    constexpr int LS = wide_log_spv(FMT), SPV = 1 << LS, NV = wide_nv(FMT, RS_NIN);
+    static_assert(SPV * NV * WV >= RS_NIN + SPV - 1, "the loader covers the window at every alignment");
+    __shared__ float2 X[RS_NIN];
+    extern __shared__ float RS_HT[];
+    const int tid = threadIdx.x, ch = blockIdx.y;
+    const float* lut = nullptr;
+    if constexpr (LUTM) {
+        __shared__ float LUT[256];
+        for (int k = tid; k < 256; k += WV) LUT[k] = cv.lut[k];
+        lut = LUT;
+    }
+    for (int k = tid; k < a.L * a.TP; k += WV) RS_HT[k] = a.taps[k];
+    const uint4* xb = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(a.x) + (size_t)fmt_bps(FMT) * ch * a.ch_stride);
+    float2* yb = reinterpret_cast<float2*>(a.y) + (size_t)ch * a.y_stride;
+    const int T = a.T, L = a.L, M = a.M;
+
+    const long m_wg0 = (long)blockIdx.x * ((long)a.tile * RS_SUBS);
+    const long u_wg = (long)a.p0 + m_wg0 * M;
+    long nt = (long)a.d0 + u_wg / L;                                // input index of the sub-tile's first output
+    int pt = (int)(u_wg % L);                                       // ... and its phase
+
+    uint4 v[NV];
+    // window of a sub-tile: positions k = 0 .. RS_NIN-1 are inputs base + k, base = nt - (T - 1)
+    auto load = [&](long base, bool none) {
+        const long v0 = base >> LS;
+        long lo = ((-a.n_hist) >> LS) - v0, hi = ((a.n_new - 1) >> LS) - v0;
+        lo = lo < -(1L << 30) ? -(1L << 30) : (lo > (1L << 30) ? (1L << 30) : lo);
+        hi = hi < -(1L << 30) ? -(1L << 30) : (hi > (1L << 30) ? (1L << 30) : hi);
+        const int lo32 = (int)lo, hi32 = none ? (int)lo : (int)hi;  // nothing follows the workgroup's last sub-tile: re-read one vector
+        const uint4* q = xb + v0;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+            int r = tid + j * WV;
+            r = r < lo32 ? lo32 : r;
+            r = r > hi32 ? hi32 : r;
+            v[j] = q[r];
+        }
+    };
+    auto stage = [&](long base) {
+        const long v0 = base >> LS;
+        const int sh = (int)(base - (v0 << LS));                    // 0 .. SPV - 1
+        const bool interior = (v0 << LS) >= -a.n_hist && (v0 << LS) + (long)SPV * NV * WV <= a.n_new;   // uniform
+#pragma unroll
+        for (int j = 0; j < NV; ++j) {
+#pragma unroll
+            for (int e = 0; e < SPV; ++e) {
+                const int k = SPV * (tid + j * WV) + e - sh;        // window position
+                float2 s2 = wide_sample<FMT, LUTM>(v[j], e, cv, lut);
+                if (!interior) {
+                    const long i = ((v0 + tid + (long)j * WV) << LS) + e;
+                    if (i < -a.n_hist || i >= a.n_new) s2 = make_float2(0.f, 0.f);
+                }
+                if (k >= 0 && k < RS_NIN) X[k] = s2;
+            }
+        }
+    };
+
+    float2 outv[RS_R];
+#pragma unroll
+    for (int r = 0; r < RS_R; ++r) outv[r] = make_float2(0.f, 0.f);
+    long out_m0 = -1;                                               // sub-tile whose outputs sit in outv (-1: none)
+    auto flush = [&]() {
+        if (out_m0 >= 0) {
+#pragma unroll
+            for (int r = 0; r < RS_R; ++r) {
+                const int k = tid + a.gl * r;
+                const long m = out_m0 + k;
+                if (tid < a.gl && r < a.R && k < a.tile && m < a.n_out) yb[m] = outv[r];
+            }
+        }
+    };
+
+    load(nt - (T - 1), false);
+    phase_sync();                                                   // the tables before their first use
+#pragma unroll 1
+    for (int it = 0; it < RS_SUBS; ++it) {
+        const long m0 = m_wg0 + (long)it * a.tile;
+        if (m0 >= a.n_out) break;                                   // uniform
+        stage(nt - (T - 1));
+        phase_sync();
+        flush();                                                    // stores before the prefetch (single in-order vmcnt queue)
+        const unsigned un = (unsigned)pt + (unsigned)a.tile * (unsigned)M;   // < 32 + 256 * 1024
+        const long nt_next = nt + un / (unsigned)L;
+        const int pt_next = (int)(un % (unsigned)L);
+        load(nt_next - (T - 1), it == RS_SUBS - 1 || m0 + a.tile >= a.n_out);
+
+        const unsigned ul = (unsigned)pt + (unsigned)tid * (unsigned)M;
+        const int q0 = (int)(ul / (unsigned)L), ph = (int)(ul % (unsigned)L);
+        const int xstep = (a.gl / L) * M;                           // window distance of a lane's outputs r and r + 1
+        const float2* xp[RS_R];
+        v2f acc[RS_R];
+#pragma unroll
+        for (int r = 0; r < RS_R; ++r) {
+            const bool act = tid < a.gl && r < a.R && tid + a.gl * r < a.tile;
+            xp[r] = X + (act ? q0 + r * xstep : 0) + (T - 1);       // idle slots walk the window's first T positions
+            acc[r] = v2f{0.f, 0.f};
+        }
+        const float* hp = RS_HT + ph * a.TP;
+        // Window reads in blocks of 8 (then 4) taps x RS_R outputs, issued from inline asm ahead of their use as in K1's walks: the
+        // 16 reads of taps j .. j+3 go out together, and each FMA step that consumes one of them issues the matching read of taps
+        // j+4 .. j+7 -- 15 window reads stay in flight behind every use.  Nothing is in flight across the loop's back edge (the
+        // compiler must never have to copy a register whose read has not landed).  The block's taps are ordinary loads issued
+        // after the first 16 reads: LDS returns in order, so the compiler's wait for them waits for nothing that the first use
+        // would not wait for anyway.
+        unsigned xb8[RS_R];                                         // byte address of the block's oldest sample per output
+#pragma unroll
+        for (int r = 0; r < RS_R; ++r) xb8[r] = lds_addr(xp[r]) - 8u * 7u;
+        int j = 0;
+#pragma unroll 1
+        for (; j + 8 <= T; j += 8) {
+            v2f g0[4 * RS_R], g1[4 * RS_R];
+            static_for<0, 4 * RS_R>([&](auto ic) {
+                constexpr int i = decltype(ic)::value, t = i / RS_R, r = i % RS_R;
+                g0[i] = lds_issue_b64<8 * (7 - t)>(xb8[r]);
+            });
+            float h[8];
+#pragma unroll
+            for (int t = 0; t < 8; ++t) h[t] = hp[j + t];
+            // all eight before the first use: a wait of the compiler's for a later one would count the window reads issued since
+            asm volatile("" : "+v"(h[0]), "+v"(h[1]), "+v"(h[2]), "+v"(h[3]), "+v"(h[4]), "+v"(h[5]), "+v"(h[6]), "+v"(h[7]));
+            static_for<0, 4 * RS_R>([&](auto ic) {
+                constexpr int i = decltype(ic)::value, t = i / RS_R, r = i % RS_R;
+                lds_landed<4 * RS_R - 1>(g0[i]);
+                acc[r] = __builtin_elementwise_fma(v2f{h[t], h[t]}, g0[i], acc[r]);
+                g1[i] = lds_issue_b64<8 * (3 - t)>(xb8[r]);
+            });
+            static_for<0, 4 * RS_R>([&](auto ic) {
+                constexpr int i = decltype(ic)::value, t = i / RS_R, r = i % RS_R;
+                lds_landed<4 * RS_R - 1 - i>(g1[i]);
+                acc[r] = __builtin_elementwise_fma(v2f{h[4 + t], h[4 + t]}, g1[i], acc[r]);
+            });
+#pragma unroll
+            for (int r = 0; r < RS_R; ++r) xb8[r] -= 64u;
+        }
+        if (j + 4 <= T) {                                           // uniform
+            v2f g0[4 * RS_R];
+            static_for<0, 4 * RS_R>([&](auto ic) {
+                constexpr int i = decltype(ic)::value, t = i / RS_R, r = i % RS_R;
+                g0[i] = lds_issue_b64<8 * (3 - t)>(xb8[r] + 32u);   // (xb8 itself may lie below the window here)
+            });
+            float h[4];
+#pragma unroll
+            for (int t = 0; t < 4; ++t) h[t] = hp[j + t];
+            static_for<0, 4 * RS_R>([&](auto ic) {
+                constexpr int i = decltype(ic)::value, t = i / RS_R, r = i % RS_R;
+                lds_landed<4 * RS_R - 1 - i>(g0[i]);
+                acc[r] = __builtin_elementwise_fma(v2f{h[t], h[t]}, g0[i], acc[r]);
+            });
+            j += 4;
+        }
+#pragma unroll 1
+        for (; j < T; ++j) {                                        // at most 3 taps
+            const float h = hp[j];
+#pragma unroll
+            for (int r = 0; r < RS_R; ++r) acc[r] = __builtin_elementwise_fma(v2f{h, h}, lds_read_v2(xp[r] - j), acc[r]);
+        }
+#pragma unroll
+        for (int r = 0; r < RS_R; ++r) outv[r] = make_float2(acc[r].x, acc[r].y);
+        out_m0 = m0;
+        nt = nt_next; pt = pt_next;
+        phase_sync();                                               // every lane's window reads precede the next staging
+    }
+    flush();
+}
 #endif
 
 // ------------------------------------------------------------------------------------------

@@ -531,3 +531,78 @@ def parse_results(t):
 
 def n_baseband(abs0, n):
     return _lib.load().p25fe_n_baseband(abs0, n)
+
+
+class Resampler:
+    """The rational resampler of docs/SPEC.md 3.0b (p25fe_resampler_t): any tuner sample rate -> 240 ksps by L / M with a
+    caller-supplied polyphase table, taps[j * L + p] = tap j of phase p.  Made for one FrontEnd (its device, channel count
+    and u8 conversion), which must outlive it."""
+
+    @staticmethod
+    def design(fs):
+        """(L, M, T, taps) for a tuner rate in Hz (p25fe_resampler_design; needs no device)"""
+        L_ = _lib.load()
+        l, m, t = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        rc = L_.p25fe_resampler_design(int(fs), C.byref(l), C.byref(m), C.byref(t), None, 0)
+        if rc != _lib.ERR_CAPACITY:
+            _lib.check(L_, None, rc if rc != _lib.OK else _lib.ERR_ARG)
+        taps = np.empty(l.value * t.value, dtype=np.float32)
+        _lib.check(L_, None, L_.p25fe_resampler_design(int(fs), C.byref(l), C.byref(m), C.byref(t), _p(taps), taps.size))
+        return l.value, m.value, t.value, taps
+
+    def __init__(self, fe, L, M, T, taps):
+        self.fe, self.lib = fe, fe.L
+        self.L, self.M, self.T = int(L), int(M), int(T)
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        if taps.size != self.L * self.T:
+            raise _lib.P25feError(_lib.ERR_ARG, "the table holds L * T taps")
+        self.rs = C.c_void_p()
+        _lib.check(self.lib, fe.h, self.lib.p25fe_resampler_create(fe.h, self.L, self.M, self.T, _p(taps), C.byref(self.rs)))
+
+    def close(self):
+        if getattr(self, "rs", None):
+            self.lib.p25fe_resampler_destroy(self.rs)
+            self.rs = None
+
+    __del__ = close
+
+    def n_out(self, abs0, n):
+        return int(self.lib.p25fe_n_resample(self.L, self.M, abs0, n))
+
+    def reset(self):
+        _lib.check(self.lib, self.fe.h, self.lib.p25fe_resampler_reset(self.rs))
+
+    def resample_dev(self, iq, n_hist=0, abs0=0, offset=0, out=None):
+        """cf32, int16 or uint8 [n, 2] or [C, n, 2] on the device -> (cf32 [C, n_out (padded), 2], n_out); `offset` = index of the
+        first owned sample inside `iq` (>= n_hist), abs0 its position in the stream."""
+        import torch
+        fmt, n_total, stride = self.fe._iq_view(iq)
+        n = n_total - offset
+        no = self.n_out(abs0, n)
+        if out is None:
+            out = torch.empty((self.fe.C, (no + 3) // 2 * 2, 2), dtype=torch.float32, device=iq.device)
+        _lib.check(self.lib, self.fe.h,
+                   self.lib.p25fe_resample_dev(self.rs, C.c_void_p(iq.data_ptr() + fmt_bytes(fmt) * offset), fmt, stride, n_hist, n, abs0,
+                                               C.c_void_p(out.data_ptr()), out.stride(0) // 2, self.fe._stream()))
+        return out, no
+
+    def resample(self, iq, cap=None):
+        """host streaming form: the next samples of the stream (complex64 [n] / [C, n], int16 or uint8 interleaved pairs [2 n] /
+        [C, 2 n]) -> complex64 [n_out] / [C, n_out]; the object keeps the history and the position between calls"""
+        iq = np.asarray(iq)
+        if iq.dtype == np.uint8:
+            fmt = FMT_U8
+        elif iq.dtype == np.int16:
+            fmt = FMT_S16
+        else:
+            fmt, iq = FMT_CF32, iq.astype(np.complex64, copy=False)
+        Cn = self.fe.C
+        iq = np.ascontiguousarray(iq).reshape(Cn, -1)
+        n = iq.shape[1] if fmt == FMT_CF32 else iq.shape[1] // 2
+        if cap is None:
+            cap = n * self.L // self.M + 1
+        out = np.empty((Cn, max(cap, 1)), dtype=np.complex64)
+        no = C.c_size_t(0)
+        _lib.check(self.lib, self.fe.h, self.lib.p25fe_resample(self.rs, _p(iq), fmt, n, _p(out), cap, C.byref(no)))
+        res = out[:, :no.value]
+        return res[0].copy() if Cn == 1 else res.copy()

@@ -1,7 +1,7 @@
 // p25fe_replay -- file-in / file-out driver in the role of the reference's command line for this path
 // (src/main.rs:95-102, 162-175, 278-283 and src/replay.rs:26-57): a deterministic harness for the hot path.
 //
-//   p25fe_replay [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] u8|s16|cf32|bb <in> <dibits.out>
+//   p25fe_replay [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] [-r RATE_HZ] u8|s16|cf32|bb <in> <dibits.out>
 //   p25fe_replay -W WINDOW_BYTES u8|s16|cf32 <in> <dibits.out>
 //
 //     u8    RTL-SDR style interleaved u8 I/Q, the reference's live input (src/consts.rs:6: 32768-byte chunks)
@@ -21,6 +21,10 @@
 //     -b N      file chunks per library call (default 64; 1 = the reference's cadence of one 32768-byte buffer per
 //               DemodTask iteration, which also fixes the every-4th-chunk power report of src/demod.rs:67, 95).
 //               The dibits do not depend on N (streaming semantics); only the PCIe transfer size does.
+//
+//     -r HZ     the capture's sample rate when it is not 240 ksps (u8, s16, cf32): every chunk first goes through the rational
+//               resampler (docs/SPEC.md 3.0b) with the table p25fe_resampler_design gives for HZ -- 2.5 or 10 Msps of an Airspy
+//               R2, 2.048 Msps of an RTL-SDR, ... -- and the 240 ksps cf32 stream it returns takes the cf32 mode's path.
 //
 //     -W BYTES  bulk mode for long captures (p25fe_run_host_windows): a READER THREAD fills pinned blocks of eight windows
 //               from the file while the library pipelines the previous block -- window k + 1 on its way to the GPU,
@@ -95,7 +99,7 @@ struct Sink {
 
 static int usage(const char* argv0)
 {
-    std::fprintf(stderr, "usage: %s [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] u8|s16|cf32|bb <in> <dibits.out>\n"
+    std::fprintf(stderr, "usage: %s [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] [-r RATE_HZ] u8|s16|cf32|bb <in> <dibits.out>\n"
                          "       %s -W WINDOW_BYTES u8|s16|cf32 <in> <dibits.out>\n", argv0, argv0);
     return 2;
 }
@@ -176,12 +180,17 @@ int main(int argc, char** argv)
 {
     const char *wpath = nullptr, *jpath = nullptr;
     size_t batch = 64, window_bytes = 0;
+    unsigned long rate_hz = 0;
     int a = 1;
     for (; a < argc && argv[a][0] == '-' && argv[a][1] != '\0'; a += 2) {
         if (a + 1 >= argc) return usage(argv[0]);
         if (!std::strcmp(argv[a], "-w")) wpath = argv[a + 1];
         else if (!std::strcmp(argv[a], "-j")) jpath = argv[a + 1];
         else if (!std::strcmp(argv[a], "-b")) batch = (size_t)std::strtoull(argv[a + 1], nullptr, 10);
+        else if (!std::strcmp(argv[a], "-r")) {
+            rate_hz = std::strtoul(argv[a + 1], nullptr, 10);
+            if (rate_hz == 0 || rate_hz > 0xfffffffful) return usage(argv[0]);
+        }
         else if (!std::strcmp(argv[a], "-W")) {
             char* end = nullptr;
             window_bytes = (size_t)std::strtoull(argv[a + 1], &end, 10);
@@ -196,7 +205,7 @@ int main(int argc, char** argv)
     if (!in) { std::fprintf(stderr, "unable to open %s\n", argv[a + 1]); return 1; }
     Handle h(0, 1);
     if (window_bytes) {
-        if (wpath || jpath || (mode != "u8" && mode != "s16" && mode != "cf32")) return usage(argv[0]);
+        if (wpath || jpath || rate_hz || (mode != "u8" && mode != "s16" && mode != "cf32")) return usage(argv[0]);
         return bulk(h, mode, in, argv[a + 2], window_bytes);
     }
     Chan<std::vector<uint8_t>> reader;
@@ -216,7 +225,39 @@ int main(int argc, char** argv)
     };
     RecvTask<Chan<Baseband>, Sink> recv(h, chan, sink);
 
-    if (mode == "u8") {
+    if (rate_hz) {
+        // a tuner rate other than 240 ksps: chunk -> p25fe_resample -> the cf32 mode's body
+        if (mode != "u8" && mode != "s16" && mode != "cf32") return usage(argv[0]);
+        const int fmt = mode == "u8" ? P25FE_FMT_U8 : (mode == "s16" ? P25FE_FMT_S16 : P25FE_FMT_CF32);
+        const size_t bps = fmt == P25FE_FMT_U8 ? 2 : (fmt == P25FE_FMT_S16 ? 4 : 8);
+        int32_t L = 0, M = 0, T = 0;
+        if (p25fe_resampler_design((uint32_t)rate_hz, &L, &M, &T, nullptr, 0) != P25FE_ERR_CAPACITY) {
+            std::fprintf(stderr, "no resampler for %lu Hz (240000 / rate in lowest terms must be L / M with L <= %d, L < M <= %d)\n", rate_hz,
+                         P25FE_RS_MAX_L, P25FE_RS_MAX_M);
+            return 1;
+        }
+        std::vector<float> taps((size_t)L * (size_t)T);
+        expect(p25fe_resampler_design((uint32_t)rate_hz, &L, &M, &T, taps.data(), taps.size()), "unable to design the resampler");
+        p25fe_resampler_t* rs = nullptr;
+        expect(p25fe_resampler_create(h.get(), L, M, T, taps.data(), &rs), "unable to create the resampler");
+        const size_t n_chunk = (size_t)BUF_SAMPLES * batch * (size_t)M / (size_t)L;     // about one cf32-mode chunk of 240 ksps samples
+        std::vector<char> buf(n_chunk * bps);
+        std::vector<float> x240(2 * (n_chunk * (size_t)L / (size_t)M + 2)), bb(x240.size() / 10 + 2);
+        unsigned notifier = 0;
+        while (in.read(buf.data(), (std::streamsize)buf.size()) || in.gcount() > 0) {
+            const size_t n = (size_t)in.gcount() / bps;
+            size_t n240 = 0, n_out = 0;
+            expect(p25fe_resample(rs, buf.data(), fmt, n, x240.data(), x240.size() / 2, &n240), "unable to resample");
+            float power = 0.f;
+            const bool want = (++notifier % 4) == 0;
+            expect(p25fe_demod_cf32(h.get(), x240.data(), n240, bb.data(), bb.size(), &n_out, want ? &power : nullptr),
+                   "unable to demodulate");
+            if (want) hub.send(HubEvent{power});
+            chan.send(Baseband{std::vector<float>(bb.begin(), bb.begin() + (long)n_out)});
+            recv.run(dump, hub);
+        }
+        p25fe_resampler_destroy(rs);
+    } else if (mode == "u8") {
         std::vector<uint8_t> buf(BUF_BYTES * batch);
         DemodTask<Chan<std::vector<uint8_t>>, Hub, Chan<Baseband>> demod(h, reader, hub, chan);
         while (in.read(reinterpret_cast<char*>(buf.data()), (std::streamsize)buf.size()) || in.gcount() > 0) {
