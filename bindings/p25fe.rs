@@ -153,6 +153,11 @@ pub const RS_MAX_L: i32 = 32;
 pub const RS_MAX_M: i32 = 1024;
 pub const RS_MAX_T: i32 = 1024;
 pub const RS_MAX_TABLE: i32 = 4096;
+/// p25fe_tuner_t: the tuner of docs/SPEC.md 3.0c (made from a Handle, which must outlive it)
+pub enum Tuner {}
+/// P25FE_TUNE_MAX_CH / _DEN: 1 <= channels <= 256; num / den in lowest terms, 1 <= den <= 8192, 2 |num| <= den
+pub const TUNE_MAX_CH: i32 = 256;
+pub const TUNE_MAX_DEN: i32 = 8192;
 pub enum Shard {}
 
 #[link(name = "p25fe")]
@@ -206,6 +211,16 @@ extern "C" {
     pub fn p25fe_resample_dev(rs: *mut Resampler, d_iq: *const c_void, fmt: c_int, ch_stride: usize, n_hist: usize, n: usize, abs_first: u64,
                               d_out: *mut f32, out_stride: usize, stream: *mut c_void) -> c_int;
     pub fn p25fe_resample(rs: *mut Resampler, iq: *const c_void, fmt: c_int, n: usize, out: *mut f32, cap: usize, n_out: *mut usize) -> c_int;
+    // tuner: K channels at num / den cycles per input sample out of one capture (the resampler with a mixer in front)
+    pub fn p25fe_tuner_freq(fs_in_hz: u32, offset_hz: i64, num: *mut i32, den: *mut i32) -> c_int;
+    pub fn p25fe_tuner_rotator(den: i32, cs: *mut f32, cap: usize) -> c_int;
+    pub fn p25fe_tuner_create(h: *mut Handle, l: i32, m: i32, t: i32, taps: *const f32, n_out_channels: i32, num: *const i32,
+                              den: *const i32, out: *mut *mut Tuner) -> c_int;
+    pub fn p25fe_tuner_destroy(tn: *mut Tuner);
+    pub fn p25fe_tuner_reset(tn: *mut Tuner) -> c_int;
+    pub fn p25fe_tune_dev(tn: *mut Tuner, d_iq: *const c_void, fmt: c_int, n_hist: usize, n: usize, abs_first: u64, d_out: *mut f32,
+                          out_stride: usize, stream: *mut c_void) -> c_int;
+    pub fn p25fe_tune(tn: *mut Tuner, iq: *const c_void, fmt: c_int, n: usize, out: *mut f32, cap: usize, n_out: *mut usize) -> c_int;
     pub fn p25fe_n_baseband(abs0: u64, n: usize) -> usize;
     pub fn p25fe_slice_dev(h: *mut Handle, d_bb: *const f32, bb_stride: usize, n_hist_bb: usize, n_bb: usize, abs_bb0: u64,
                            d_anchor_in: *const Anchor, d_dibits: *mut u8, dibit_stride: usize, d_sync_pos: *mut i64,

@@ -408,6 +408,54 @@ int p25fe_resample_dev(p25fe_resampler_t *rs, const void *d_iq, int fmt, size_t 
  * stream).  Synchronous. */
 int p25fe_resample(p25fe_resampler_t *rs, const void *iq, int fmt, size_t n, float *out, size_t cap, size_t *n_out);
 
+/* ---- tuner: K channels at chosen frequency offsets out of ONE capture of any supported rate (docs/SPEC.md 3.0c) --------------
+ * The resampler above with a mixer in front.  Channel k has the frequency num_k / den_k cycles per INPUT sample, in lowest terms
+ * (positive: above the capture's centre; 0 / 1: the centre): with i = ((num mod den)(n mod den)) mod den and the rotator table of
+ * den, c = C[i] = (float)cos(2 pi i / den), s = S[i] = (float)sin(2 pi i / den),
+ *     v_k[n] = ( fma(x[n].im, s, x[n].re * c), fma(-x[n].re, s, x[n].im * c) )       (= x[n] e^{-j 2 pi num n / den}; num = 0: v = x)
+ * and y_k[m] is the resampler's formula on v_k: the same table, counts (p25fe_n_resample), ownership and history rule
+ * (n_hist >= T - 1) for every channel.  A channel with num = 0 IS p25fe_resample_dev, bit for bit.  The phase is a function of the
+ * absolute index n, so the position grid of channel k is lcm(M, den_k).
+ * Limits (P25FE_ERR_ARG otherwise): the resampler's, 1 <= n_out_channels <= P25FE_TUNE_MAX_CH, 1 <= den <= P25FE_TUNE_MAX_DEN,
+ * 2 |num| <= den, gcd(|num|, den) = 1.  Every combination inside them runs. */
+#define P25FE_TUNE_MAX_CH  256
+#define P25FE_TUNE_MAX_DEN 8192
+typedef struct p25fe_tuner p25fe_tuner_t;
+
+/* offset_hz / fs_in_hz in lowest terms, the sign on *num; no device needed.  On the 12.5 kHz raster den is 200 at 2.5 Msps, 800 at
+ * 10 Msps, 4096 at 2.048 Msps, 192 at 2.4 Msps.  P25FE_ERR_ARG: a null pointer, fs_in_hz = 0, 2 |offset_hz| > fs_in_hz, or a reduced
+ * denominator above P25FE_TUNE_MAX_DEN. */
+int p25fe_tuner_freq(uint32_t fs_in_hz, int64_t offset_hz, int32_t *num, int32_t *den);
+/* The rotator table of den, 2 * den floats: C[0 .. den) then S[0 .. den), evaluated in double and rounded once; no device needed.
+ * This function is the table's definition (C[0] = 1 and S[0] = +0 exactly).  P25FE_ERR_ARG: den outside [1, P25FE_TUNE_MAX_DEN];
+ * P25FE_ERR_CAPACITY: cap < 2 * den (cs may then be null). */
+int p25fe_tuner_rotator(int32_t den, float *cs, size_t cap);
+
+/* A tuner on h's device with h's u8 conversion (h's n_channels does not matter: the input is ONE capture); h must outlive every
+ * USE of it (p25fe_tuner_destroy alone is safe after p25fe_destroy(h)).  Every argument is checked before any device is touched.
+ * The object holds the table, one rotator table per distinct denominator and the channels' numbers in device memory, and the
+ * state of the host streaming form. */
+int p25fe_tuner_create(p25fe_t *h, int32_t L, int32_t M, int32_t T, const float *taps,
+                       int32_t n_out_channels, const int32_t *num, const int32_t *den, p25fe_tuner_t **out);
+void p25fe_tuner_destroy(p25fe_tuner_t *tn);
+int p25fe_tuner_reset(p25fe_tuner_t *tn);              /* the host streaming form restarts at position 0 with zero history */
+
+/* A device-resident range of the capture, conventions as p25fe_resample_dev: d_iq points at owned sample 0 and is 16-byte aligned,
+ * only the aligned 16-byte vectors that hold samples [-n_hist, n) are read.  Writes exactly p25fe_n_resample(L, M, abs_first, n)
+ * cf32 samples to each of the rows d_out + k * out_stride (complex samples), k < n_out_channels, and nothing beyond them; enqueues
+ * on `stream`, synchronises nothing.  The rows are the input of an n_out_channels-channel handle's p25fe_run_dev / p25fe_demod_dev
+ * with ch_stride = out_stride; those calls want 16-byte aligned rows, so give d_out that alignment and an even out_stride.  u8 / s16
+ * input gives, bit for bit, the cf32 call's output on the converted samples.  P25FE_ERR_ARG: null or misaligned pointer (d_out: 8
+ * bytes), unknown format, out_stride < the count, abs_first >= 2^62. */
+int p25fe_tune_dev(p25fe_tuner_t *tn, const void *d_iq, int fmt, size_t n_hist, size_t n, uint64_t abs_first,
+                   float *d_out, size_t out_stride, void *stream);
+
+/* Host streaming form, p25fe_resample's semantics: iq holds the capture's next n samples, out is [n_out_channels][cap] cf32, *n_out
+ * = samples written per row.  The object keeps the last T - 1 samples and the stream position: any chunking gives the same
+ * concatenated output.  P25FE_ERR_CAPACITY (cap too small; *n_out = the count needed) leaves the state untouched; P25FE_ERR_FORMAT
+ * when the format differs from the stream's first call (p25fe_tuner_reset starts a new stream).  Synchronous. */
+int p25fe_tune(p25fe_tuner_t *tn, const void *iq, int fmt, size_t n, float *out, size_t cap, size_t *n_out);
+
 /* stages 6-7 on device baseband.  d_bb points at the first owned sample; n_hist_bb valid
  * samples precede it; abs_bb0 is its absolute index; d_anchor_in (nullable = no lock) is the
  * carry-in per channel.  d_result[c] is filled per channel.

@@ -16,6 +16,7 @@ FMT_CF32, FMT_U8, FMT_S16 = 0, 1, 2
 S16_SCALE = 2.0 ** -15                    # P25FE_S16_SCALE: an int16 v is the sample (float)v * 2^-15, exactly
 MAX_POSITION = 1 << 62                   # P25FE_MAX_POSITION: abs0 / abs_bb0 from here on are P25FE_ERR_ARG
 RS_MAX_L, RS_MAX_M, RS_MAX_T, RS_MAX_TABLE = 32, 1024, 1024, 4096   # P25FE_RS_MAX_*: limits of the rational resampler
+TUNE_MAX_CH, TUNE_MAX_DEN = 256, 8192    # P25FE_TUNE_MAX_*: limits of the tuner
 
 OK, ERR_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_CAPACITY, ERR_FORMAT, ERR_NOMEM, ERR_JIT, ERR_TIMEOUT = 0, -1, -2, -3, -4, -5, -6, -7, -8
 CLOCK_FIXED, CLOCK_TRACKING, CLOCK_TRACKING_RESLICE, CLOCK_CAUSAL_OK = 0, 1, 2, 0x100
@@ -79,6 +80,8 @@ SYMBOLS = [
     "p25fe_predecim_fmt_dev", "p25fe_channelise_fmt_dev",
     "p25fe_resampler_design", "p25fe_resampler_create", "p25fe_resampler_destroy", "p25fe_resampler_reset", "p25fe_n_resample",
     "p25fe_resample_dev", "p25fe_resample",
+    "p25fe_tuner_freq", "p25fe_tuner_rotator", "p25fe_tuner_create", "p25fe_tuner_destroy", "p25fe_tuner_reset", "p25fe_tune_dev",
+    "p25fe_tune",
 ]
 
 
@@ -183,6 +186,14 @@ def load():
     L.p25fe_n_resample.restype = sz
     L.p25fe_resample_dev.argtypes = [vp, vp, C.c_int, sz, sz, sz, u64, vp, sz, vp]
     L.p25fe_resample.argtypes = [vp, vp, C.c_int, sz, vp, sz, psz]
+    L.p25fe_tuner_freq.argtypes = [C.c_uint32, C.c_int64, pi32, pi32]
+    L.p25fe_tuner_rotator.argtypes = [C.c_int32, vp, sz]
+    L.p25fe_tuner_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, vp, vp, C.POINTER(vp)]
+    L.p25fe_tuner_destroy.argtypes = [vp]
+    L.p25fe_tuner_destroy.restype = None
+    L.p25fe_tuner_reset.argtypes = [vp]
+    L.p25fe_tune_dev.argtypes = [vp, vp, C.c_int, sz, sz, u64, vp, sz, vp]
+    L.p25fe_tune.argtypes = [vp, vp, C.c_int, sz, vp, sz, psz]
     L.p25fe_n_predecim.argtypes = [u64, sz]
     L.p25fe_n_predecim.restype = sz
     L.p25fe_n_baseband.argtypes = [u64, sz]

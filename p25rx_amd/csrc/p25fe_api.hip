@@ -1409,6 +1409,72 @@ static int launch_resample(p25fe_resampler* rs, const void* d_iq, int fmt, size_
     return P25FE_OK;
 }
 
+// --------------------------------------------------------------------------------------------
+// Tuner (SPEC 3.0c; kernel: k_tune): the resampler's object for ONE input capture and K output rows, plus the channels'
+// frequencies: one rotator table per distinct denominator and the per-channel numbers (TuneCh) in device memory.
+// --------------------------------------------------------------------------------------------
+struct p25fe_tuner {
+    p25fe_t* h = nullptr;
+    int device = 0;                        // h's, kept here: destroying the object must not read the handle
+    int L = 0, M = 0, T = 0, TP = 0, K = 0;
+    int rot_off = 0;                       // floats of dynamic LDS in front of the rotator's copy
+    size_t lds = 0;                        // dynamic LDS of a launch: the table, and the largest rotator that is copied there
+    DevBuf d_taps, d_rot, d_ch, d_in, d_out;
+    uint64_t pos = 0;                      // samples consumed
+    int fmt = -1;                          // format of the stream (-1: none yet)
+    std::vector<unsigned char> stage;      // host image of the device row of one p25fe_tune call
+    std::vector<unsigned char> hist;       // [T - 1] samples in the stream's format, oldest first
+};
+
+static uint64_t gcd_u64(uint64_t a, uint64_t b) { while (b) { const uint64_t t = a % b; a = b; b = t; } return a; }
+// num / den in lowest terms inside the tuner's limits (0 / 1 is the centre)
+static bool tn_freq_ok(int64_t num, int64_t den)
+{
+    if (den < 1 || den > P25FE_TUNE_MAX_DEN) return false;
+    const int64_t an = num < 0 ? -num : num;
+    return 2 * an <= den && gcd_u64((uint64_t)an, (uint64_t)den) == 1;
+}
+
+static int launch_tune(p25fe_tuner* tn, const void* d_iq, int fmt, size_t n_hist, size_t n, uint64_t abs_first, float* d_out,
+                       size_t out_stride, hipStream_t st)
+{
+    p25fe_t* h = tn->h;
+    if (!d_iq || !d_out || position_refused(abs_first)) return P25FE_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_iq) & 15u) != 0 || (reinterpret_cast<uintptr_t>(d_out) & 7u) != 0) return P25FE_ERR_ARG;
+    const size_t n_out = p25fe_n_resample(tn->L, tn->M, abs_first, n);
+    if (out_stride < n_out) return P25FE_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (n_out == 0) return P25FE_OK;
+    const int L = tn->L, M = tn->M, T = tn->T;
+    TuneArgs ta;
+    RsArgs& a = ta.r;
+    a.x = d_iq; a.ch_stride = 0; a.n_hist = (long)n_hist; a.n_new = (long)n;
+    a.y = d_out; a.y_stride = (long)out_stride; a.n_out = (long)n_out;
+    a.taps = tn->d_taps.as<float>(); a.L = L; a.M = M; a.T = T; a.TP = tn->TP;
+    // owned output 0 and the sub-tile's fit: launch_resample's, word for word (the position grid of the RESAMPLER is M; the mixer's
+    // phase takes the whole position)
+    const int ra = (int)(abs_first % (uint64_t)M), mr = ra * L / M, ur = mr * M + M - 1;
+    a.p0 = ur % L; a.d0 = ur / L - ra;
+    const int fit = 1 + (RS_NIN - T) * L / M;
+    a.gl = WV - WV % L;
+    if (fit >= a.gl) { a.R = fit / a.gl < RS_R ? fit / a.gl : RS_R; a.tile = a.gl * a.R; }
+    else { a.R = 1; a.tile = fit; }
+    ta.ch = tn->d_ch.as<TuneCh>(); ta.K = tn->K; ta.rot_off = tn->rot_off; ta.abs_first = abs_first;
+    // workgroup index = sub-tile group * K + channel: the channel varies fastest.  Groups beyond grid.x's range go to grid.y
+    const size_t per_wg = (size_t)a.tile * RS_SUBS, groups = (n_out + per_wg - 1) / per_wg;
+    const size_t gx = std::min(groups, (size_t)0x7fffffffu / (size_t)tn->K), gy = (groups + gx - 1) / gx;
+    if (gy > 65535) return P25FE_ERR_ARG;
+    const dim3 grid((unsigned)(gx * (size_t)tn->K), (unsigned)gy);
+    const WideConv cv = wide_conv_of(h);
+    (void)hipGetLastError();                                        // the check below is for THIS launch
+    if (fmt == P25FE_FMT_CF32) hipLaunchKernelGGL((k_tune<P25FE_FMT_CF32, false>), grid, dim3(WV), tn->lds, st, ta, cv);
+    else if (fmt == P25FE_FMT_S16) hipLaunchKernelGGL((k_tune<P25FE_FMT_S16, false>), grid, dim3(WV), tn->lds, st, ta, cv);
+    else if (cv.lut) hipLaunchKernelGGL((k_tune<P25FE_FMT_U8, true>), grid, dim3(WV), tn->lds, st, ta, cv);
+    else hipLaunchKernelGGL((k_tune<P25FE_FMT_U8, false>), grid, dim3(WV), tn->lds, st, ta, cv);
+    HIPCHK(h, hipGetLastError());
+    return P25FE_OK;
+}
+
 extern "C" {
 
 int p25fe_resampler_design(uint32_t fs_in_hz, int32_t* L, int32_t* M, int32_t* T, float* taps, size_t cap)
@@ -1535,6 +1601,140 @@ int p25fe_resample(p25fe_resampler_t* rs, const void* iq, int fmt, size_t n, flo
         }
     }
     rs->pos += n; rs->fmt = fmt;
+    return P25FE_OK;
+}
+
+int p25fe_tuner_freq(uint32_t fs_in_hz, int64_t offset_hz, int32_t* num, int32_t* den)
+{
+    if (!num || !den || fs_in_hz == 0) return P25FE_ERR_ARG;
+    const uint64_t ao = offset_hz < 0 ? 0 - (uint64_t)offset_hz : (uint64_t)offset_hz;
+    if (ao > fs_in_hz || 2 * ao > fs_in_hz) return P25FE_ERR_ARG;
+    const uint64_t g = gcd_u64(ao, fs_in_hz);                       // gcd(0, fs) = fs: the centre is 0 / 1
+    const uint64_t d = fs_in_hz / g, nn = ao / g;
+    if (d > P25FE_TUNE_MAX_DEN) return P25FE_ERR_ARG;
+    *num = offset_hz < 0 ? -(int32_t)nn : (int32_t)nn; *den = (int32_t)d;
+    return P25FE_OK;
+}
+
+int p25fe_tuner_rotator(int32_t den, float* cs, size_t cap)
+{
+    if (den < 1 || den > P25FE_TUNE_MAX_DEN) return P25FE_ERR_ARG;
+    if (cap < 2 * (size_t)den || !cs) return P25FE_ERR_CAPACITY;
+    const double two_pi = 2.0 * 3.14159265358979323846;
+    for (int32_t i = 0; i < den; ++i) {
+        const double w = two_pi * (double)i / (double)den;          // (2 pi i) / den, in this order
+        cs[i] = (float)cos(w); cs[den + i] = (float)sin(w);
+    }
+    return P25FE_OK;
+}
+
+int p25fe_tuner_create(p25fe_t* h, int32_t L, int32_t M, int32_t T, const float* taps, int32_t n_out_channels, const int32_t* num,
+                       const int32_t* den, p25fe_tuner_t** out)
+{
+    if (out) *out = nullptr;
+    if (!out || !rs_shape_ok(L, M, T) || n_out_channels < 1 || n_out_channels > P25FE_TUNE_MAX_CH || !taps || !num || !den) return P25FE_ERR_ARG;
+    for (int k = 0; k < n_out_channels; ++k) if (!tn_freq_ok(num[k], den[k])) return P25FE_ERR_ARG;
+    for (int k = 0; k < L * T; ++k) if (!finite_f(taps[k])) return P25FE_ERR_ARG;
+    if (!h) return P25FE_ERR_ARG;
+    p25fe_tuner* tn = new (std::nothrow) p25fe_tuner;
+    if (!tn) return P25FE_ERR_NOMEM;
+    const int K = n_out_channels;
+    tn->h = h; tn->device = h->cfg.device; tn->L = L; tn->M = M; tn->T = T; tn->TP = rs_tap_pitch(T); tn->K = K;
+    std::vector<float> tab((size_t)L * tn->TP, 0.0f);               // the kernel's layout: phase-major rows of pitch TP, the pad zero
+    for (int p = 0; p < L; ++p) for (int j = 0; j < T; ++j) tab[(size_t)p * tn->TP + j] = taps[(size_t)j * L + p];
+    // one rotator per distinct denominator, (cos, sin) interleaved, one after the other in one buffer
+    std::vector<long> at(P25FE_TUNE_MAX_DEN + 1, -1);
+    std::vector<float> rot, cs;
+    int lds_den = 0;
+    for (int k = 0; k < K; ++k) {
+        const int D = den[k];
+        if (num[k] != 0 && D <= TN_ROT_LDS_DEN && D > lds_den) lds_den = D;
+        if (at[D] >= 0) continue;
+        at[D] = (long)(rot.size() / 2);
+        cs.resize(2 * (size_t)D);
+        (void)p25fe_tuner_rotator(D, cs.data(), cs.size());
+        for (int i = 0; i < D; ++i) { rot.push_back(cs[i]); rot.push_back(cs[D + i]); }
+    }
+    tn->rot_off = (int)round_up(tab.size(), 2);
+    tn->lds = sizeof(float) * ((size_t)tn->rot_off + 2 * (size_t)lds_den);
+    tn->hist.assign((size_t)(T - 1) * 8, 0);
+    int rc = P25FE_OK;
+    if (hipSetDevice(h->cfg.device) != hipSuccess || tn->d_taps.ensure(tab.size() * sizeof(float)) != hipSuccess ||
+        tn->d_rot.ensure(rot.size() * sizeof(float)) != hipSuccess || tn->d_ch.ensure((size_t)K * sizeof(TuneCh)) != hipSuccess)
+        rc = P25FE_ERR_HIP;
+    if (!rc) {
+        std::vector<TuneCh> ch((size_t)K);
+        for (int k = 0; k < K; ++k) {
+            ch[k].rot = tn->d_rot.as<float2>() + at[den[k]];
+            ch[k].D = den[k];
+            ch[k].nm = (int)(((int64_t)num[k] % den[k] + den[k]) % den[k]);
+        }
+        if (hipMemcpy(tn->d_taps.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(tn->d_rot.p, rot.data(), rot.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(tn->d_ch.p, ch.data(), ch.size() * sizeof(TuneCh), hipMemcpyHostToDevice) != hipSuccess)
+            rc = P25FE_ERR_HIP;
+    }
+    if (rc) { h->last_hip = (int)hipGetLastError(); delete tn; return rc; }
+    *out = tn;
+    return P25FE_OK;
+}
+
+void p25fe_tuner_destroy(p25fe_tuner_t* tn)
+{
+    if (!tn) return;
+    (void)hipSetDevice(tn->device);
+    delete tn;
+}
+
+int p25fe_tuner_reset(p25fe_tuner_t* tn)
+{
+    if (!tn) return P25FE_ERR_ARG;
+    tn->pos = 0; tn->fmt = -1;
+    std::fill(tn->hist.begin(), tn->hist.end(), (unsigned char)0);
+    return P25FE_OK;
+}
+
+int p25fe_tune_dev(p25fe_tuner_t* tn, const void* d_iq, int fmt, size_t n_hist, size_t n, uint64_t abs_first, float* d_out,
+                   size_t out_stride, void* stream)
+{
+    if (!tn || !tn->h || !wide_fmt_known(fmt)) return P25FE_ERR_ARG;
+    return launch_tune(tn, d_iq, fmt, n_hist, n, abs_first, d_out, out_stride, (hipStream_t)stream);
+}
+
+int p25fe_tune(p25fe_tuner_t* tn, const void* iq, int fmt, size_t n, float* out, size_t cap, size_t* n_out)
+{
+    if (!tn || !tn->h || !n_out || !wide_fmt_known(fmt) || (n && !iq)) return P25FE_ERR_ARG;
+    if (tn->fmt >= 0 && fmt != tn->fmt) return P25FE_ERR_FORMAT;
+    if (position_refused(tn->pos) || n >= P25FE_MAX_POSITION) return P25FE_ERR_ARG;
+    p25fe_t* h = tn->h;
+    const size_t K = (size_t)tn->K, bps = fmt_bytes(fmt), keep = (size_t)tn->T - 1;
+    const size_t no = p25fe_n_resample(tn->L, tn->M, tn->pos, n);
+    *n_out = no;
+    if (no > cap || (no && !out)) return P25FE_ERR_CAPACITY;
+    const size_t n_hist = tn->pos < keep ? (size_t)tn->pos : keep;
+    const unsigned char* src = static_cast<const unsigned char*>(iq);
+    if (no) {
+        // the device row: [history, right-aligned in `lead` slots | n new samples], owned sample 0 16-byte aligned, in ONE copy
+        const size_t lead = round_up(keep, 8), len = lead + round_up(n, 8);
+        HIPCHK(h, hipSetDevice(h->cfg.device));
+        HIPCHK(h, tn->d_in.ensure(len * bps));
+        HIPCHK(h, tn->d_out.ensure(K * no * sizeof(float) * 2));
+        unsigned char* din = tn->d_in.as<unsigned char>();
+        tn->stage.assign(len * bps, 0);
+        if (n_hist) memcpy(tn->stage.data() + (lead - n_hist) * bps, tn->hist.data() + (keep - n_hist) * bps, n_hist * bps);
+        memcpy(tn->stage.data() + lead * bps, src, n * bps);
+        HIPCHK(h, hipMemcpyAsync(din, tn->stage.data(), tn->stage.size(), hipMemcpyHostToDevice, h->stream));
+        if (int rc = launch_tune(tn, din + lead * bps, fmt, n_hist, n, tn->pos, tn->d_out.as<float>(), no, h->stream)) return rc;
+        for (size_t k = 0; k < K; ++k)
+            HIPCHK(h, hipMemcpyAsync(out + k * cap * 2, tn->d_out.as<float>() + k * no * 2, no * sizeof(float) * 2, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    if (keep) {                                                      // the state moves: the last T - 1 samples of [history | new]
+        unsigned char* hc = tn->hist.data();
+        if (n >= keep) memcpy(hc, src + (n - keep) * bps, keep * bps);
+        else { memmove(hc, hc + n * bps, (keep - n) * bps); memcpy(hc + (keep - n) * bps, src, n * bps); }
+    }
+    tn->pos += n; tn->fmt = fmt;
     return P25FE_OK;
 }
 

@@ -606,3 +606,92 @@ class Resampler:
         _lib.check(self.lib, self.fe.h, self.lib.p25fe_resample(self.rs, _p(iq), fmt, n, _p(out), cap, C.byref(no)))
         res = out[:, :no.value]
         return res[0].copy() if Cn == 1 else res.copy()
+
+
+class Tuner:
+    """The tuner of docs/SPEC.md 3.0c (p25fe_tuner_t): K channels at rational frequency offsets out of ONE capture of any supported
+    rate, each a 240 ksps cf32 row -- the resampler with a mixer in front.  freqs = [(num, den), ...] in cycles per input sample,
+    lowest terms.  Made for one FrontEnd (its device and u8 conversion; its channel count does not matter), which must outlive it."""
+
+    @staticmethod
+    def freq(fs_hz, offset_hz):
+        """(num, den) = offset_hz / fs_hz in lowest terms (p25fe_tuner_freq; needs no device)"""
+        L_ = _lib.load()
+        num, den = C.c_int32(0), C.c_int32(0)
+        _lib.check(L_, None, L_.p25fe_tuner_freq(int(fs_hz), int(offset_hz), C.byref(num), C.byref(den)))
+        return num.value, den.value
+
+    @staticmethod
+    def rotator(den):
+        """(C, S) of a denominator, float32 [den] each (p25fe_tuner_rotator: the table's definition; needs no device)"""
+        L_ = _lib.load()
+        cs = np.empty(2 * max(int(den), 0), dtype=np.float32)
+        _lib.check(L_, None, L_.p25fe_tuner_rotator(int(den), _p(cs), cs.size))
+        return cs[:den].copy(), cs[den:].copy()
+
+    @staticmethod
+    def design(fs_hz, offsets_hz):
+        """(L, M, T, taps, freqs) for a tuner rate and the channels' offsets from its centre in Hz"""
+        L, M, T, taps = Resampler.design(fs_hz)
+        return L, M, T, taps, [Tuner.freq(fs_hz, o) for o in offsets_hz]
+
+    def __init__(self, fe, L, M, T, taps, freqs):
+        self.fe, self.lib = fe, fe.L
+        self.L, self.M, self.T = int(L), int(M), int(T)
+        taps = np.ascontiguousarray(taps, dtype=np.float32)
+        if taps.size != self.L * self.T:
+            raise _lib.P25feError(_lib.ERR_ARG, "the table holds L * T taps")
+        self.freqs = [(int(a), int(b)) for a, b in freqs]
+        self.K = len(self.freqs)
+        num = np.array([f[0] for f in self.freqs], dtype=np.int32)
+        den = np.array([f[1] for f in self.freqs], dtype=np.int32)
+        self.tn = C.c_void_p()
+        _lib.check(self.lib, fe.h, self.lib.p25fe_tuner_create(fe.h, self.L, self.M, self.T, _p(taps), self.K, _p(num), _p(den),
+                                                               C.byref(self.tn)))
+
+    def close(self):
+        if getattr(self, "tn", None):
+            self.lib.p25fe_tuner_destroy(self.tn)
+            self.tn = None
+
+    __del__ = close
+
+    def n_out(self, abs0, n):
+        return int(self.lib.p25fe_n_resample(self.L, self.M, abs0, n))
+
+    def reset(self):
+        _lib.check(self.lib, self.fe.h, self.lib.p25fe_tuner_reset(self.tn))
+
+    def tune_dev(self, iq, n_hist=0, abs0=0, offset=0, out=None):
+        """cf32, int16 or uint8 [n, 2] on the device -> (cf32 [K, n_out (padded), 2], n_out); `offset` = index of the first owned
+        sample inside `iq` (>= n_hist), abs0 its position in the stream.  The rows feed a K-channel FrontEnd's run_dev / demod_dev."""
+        import torch
+        assert iq.is_cuda and iq.dim() == 2 and iq.shape[1] == 2 and iq.is_contiguous()
+        fmt = _torch_fmt(iq.dtype)
+        n = iq.shape[0] - offset
+        no = self.n_out(abs0, n)
+        if out is None:
+            out = torch.empty((self.K, (no + 3) // 2 * 2, 2), dtype=torch.float32, device=iq.device)
+        _lib.check(self.lib, self.fe.h,
+                   self.lib.p25fe_tune_dev(self.tn, C.c_void_p(iq.data_ptr() + fmt_bytes(fmt) * offset), fmt, n_hist, n, abs0,
+                                           C.c_void_p(out.data_ptr()), out.stride(0) // 2, self.fe._stream()))
+        return out, no
+
+    def tune(self, iq, cap=None):
+        """host streaming form: the capture's next samples (complex64 [n], int16 or uint8 interleaved pairs [2 n]) -> complex64
+        [K, n_out]; the object keeps the history and the position between calls"""
+        iq = np.asarray(iq)
+        if iq.dtype == np.uint8:
+            fmt = FMT_U8
+        elif iq.dtype == np.int16:
+            fmt = FMT_S16
+        else:
+            fmt, iq = FMT_CF32, iq.astype(np.complex64, copy=False)
+        iq = np.ascontiguousarray(iq).reshape(-1)
+        n = iq.size if fmt == FMT_CF32 else iq.size // 2
+        if cap is None:
+            cap = n * self.L // self.M + 1
+        out = np.empty((self.K, max(cap, 1)), dtype=np.complex64)
+        no = C.c_size_t(0)
+        _lib.check(self.lib, self.fe.h, self.lib.p25fe_tune(self.tn, _p(iq), fmt, n, _p(out), cap, C.byref(no)))
+        return out[:, :no.value].copy()

@@ -1,7 +1,7 @@
 // p25fe_replay -- file-in / file-out driver in the role of the reference's command line for this path
 // (src/main.rs:95-102, 162-175, 278-283 and src/replay.rs:26-57): a deterministic harness for the hot path.
 //
-//   p25fe_replay [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] [-r RATE_HZ] u8|s16|cf32|bb <in> <dibits.out>
+//   p25fe_replay [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] [-r RATE_HZ [-f OFFSET_HZ]] u8|s16|cf32|bb <in> <dibits.out>
 //   p25fe_replay -W WINDOW_BYTES u8|s16|cf32 <in> <dibits.out>
 //
 //     u8    RTL-SDR style interleaved u8 I/Q, the reference's live input (src/consts.rs:6: 32768-byte chunks)
@@ -25,6 +25,10 @@
 //     -r HZ     the capture's sample rate when it is not 240 ksps (u8, s16, cf32): every chunk first goes through the rational
 //               resampler (docs/SPEC.md 3.0b) with the table p25fe_resampler_design gives for HZ -- 2.5 or 10 Msps of an Airspy
 //               R2, 2.048 Msps of an RTL-SDR, ... -- and the 240 ksps cf32 stream it returns takes the cf32 mode's path.
+//
+//     -f HZ     with -r: the channel's offset from the capture's centre in Hz (negative: below it).  The chunks then go through the
+//               tuner (docs/SPEC.md 3.0c, p25fe_tune) with the same table: OFFSET_HZ / RATE_HZ in lowest terms must have a
+//               denominator of at most 8192, which every 12.5 kHz or 6.25 kHz raster at the customary rates has.
 //
 //     -W BYTES  bulk mode for long captures (p25fe_run_host_windows): a READER THREAD fills pinned blocks of eight windows
 //               from the file while the library pipelines the previous block -- window k + 1 on its way to the GPU,
@@ -99,7 +103,7 @@ struct Sink {
 
 static int usage(const char* argv0)
 {
-    std::fprintf(stderr, "usage: %s [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] [-r RATE_HZ] u8|s16|cf32|bb <in> <dibits.out>\n"
+    std::fprintf(stderr, "usage: %s [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] [-r RATE_HZ [-f OFFSET_HZ]] u8|s16|cf32|bb <in> <dibits.out>\n"
                          "       %s -W WINDOW_BYTES u8|s16|cf32 <in> <dibits.out>\n", argv0, argv0);
     return 2;
 }
@@ -181,6 +185,8 @@ int main(int argc, char** argv)
     const char *wpath = nullptr, *jpath = nullptr;
     size_t batch = 64, window_bytes = 0;
     unsigned long rate_hz = 0;
+    long long offset_hz = 0;
+    bool tune = false;
     int a = 1;
     for (; a < argc && argv[a][0] == '-' && argv[a][1] != '\0'; a += 2) {
         if (a + 1 >= argc) return usage(argv[0]);
@@ -191,6 +197,7 @@ int main(int argc, char** argv)
             rate_hz = std::strtoul(argv[a + 1], nullptr, 10);
             if (rate_hz == 0 || rate_hz > 0xfffffffful) return usage(argv[0]);
         }
+        else if (!std::strcmp(argv[a], "-f")) { offset_hz = std::strtoll(argv[a + 1], nullptr, 10); tune = true; }
         else if (!std::strcmp(argv[a], "-W")) {
             char* end = nullptr;
             window_bytes = (size_t)std::strtoull(argv[a + 1], &end, 10);
@@ -199,13 +206,13 @@ int main(int argc, char** argv)
         }
         else return usage(argv[0]);
     }
-    if (argc - a != 3 || batch == 0) return usage(argv[0]);
+    if (argc - a != 3 || batch == 0 || (tune && !rate_hz)) return usage(argv[0]);
     const std::string mode = argv[a];
     std::ifstream in(argv[a + 1], std::ios::binary);
     if (!in) { std::fprintf(stderr, "unable to open %s\n", argv[a + 1]); return 1; }
     Handle h(0, 1);
     if (window_bytes) {
-        if (wpath || jpath || rate_hz || (mode != "u8" && mode != "s16" && mode != "cf32")) return usage(argv[0]);
+        if (wpath || jpath || rate_hz || tune || (mode != "u8" && mode != "s16" && mode != "cf32")) return usage(argv[0]);
         return bulk(h, mode, in, argv[a + 2], window_bytes);
     }
     Chan<std::vector<uint8_t>> reader;
@@ -239,7 +246,18 @@ int main(int argc, char** argv)
         std::vector<float> taps((size_t)L * (size_t)T);
         expect(p25fe_resampler_design((uint32_t)rate_hz, &L, &M, &T, taps.data(), taps.size()), "unable to design the resampler");
         p25fe_resampler_t* rs = nullptr;
-        expect(p25fe_resampler_create(h.get(), L, M, T, taps.data(), &rs), "unable to create the resampler");
+        p25fe_tuner_t* tn = nullptr;
+        if (tune) {
+            int32_t num = 0, den = 0;
+            if (p25fe_tuner_freq((uint32_t)rate_hz, offset_hz, &num, &den) != P25FE_OK) {
+                std::fprintf(stderr, "no tuner for %lld Hz at %lu Hz (beyond half the rate, or offset / rate in lowest terms has a denominator above %d)\n",
+                             offset_hz, rate_hz, P25FE_TUNE_MAX_DEN);
+                return 1;
+            }
+            expect(p25fe_tuner_create(h.get(), L, M, T, taps.data(), 1, &num, &den, &tn), "unable to create the tuner");
+        } else {
+            expect(p25fe_resampler_create(h.get(), L, M, T, taps.data(), &rs), "unable to create the resampler");
+        }
         const size_t n_chunk = (size_t)BUF_SAMPLES * batch * (size_t)M / (size_t)L;     // about one cf32-mode chunk of 240 ksps samples
         std::vector<char> buf(n_chunk * bps);
         std::vector<float> x240(2 * (n_chunk * (size_t)L / (size_t)M + 2)), bb(x240.size() / 10 + 2);
@@ -247,7 +265,8 @@ int main(int argc, char** argv)
         while (in.read(buf.data(), (std::streamsize)buf.size()) || in.gcount() > 0) {
             const size_t n = (size_t)in.gcount() / bps;
             size_t n240 = 0, n_out = 0;
-            expect(p25fe_resample(rs, buf.data(), fmt, n, x240.data(), x240.size() / 2, &n240), "unable to resample");
+            if (tn) expect(p25fe_tune(tn, buf.data(), fmt, n, x240.data(), x240.size() / 2, &n240), "unable to tune");
+            else expect(p25fe_resample(rs, buf.data(), fmt, n, x240.data(), x240.size() / 2, &n240), "unable to resample");
             float power = 0.f;
             const bool want = (++notifier % 4) == 0;
             expect(p25fe_demod_cf32(h.get(), x240.data(), n240, bb.data(), bb.size(), &n_out, want ? &power : nullptr),
@@ -257,6 +276,7 @@ int main(int argc, char** argv)
             recv.run(dump, hub);
         }
         p25fe_resampler_destroy(rs);
+        p25fe_tuner_destroy(tn);
     } else if (mode == "u8") {
         std::vector<uint8_t> buf(BUF_BYTES * batch);
         DemodTask<Chan<std::vector<uint8_t>>, Hub, Chan<Baseband>> demod(h, reader, hub, chan);

@@ -1,0 +1,20 @@
+"""The tuner's host-only functions (p25fe_tuner_freq, p25fe_tuner_rotator, the create-time checks; docs/SPEC.md 3.0c) under
+AddressSanitizer + UBSan: a stand-alone program (tests/native/tune_host_driver.cpp) linked against the host-side sanitizer build
+of the library that tests/test_sanitizers.py uses.  Host code only; no GPU."""
+import os
+import subprocess
+
+from test_sanitizers import ROOT, run_clean
+
+
+def test_tuner_host_functions_under_asan_ubsan():
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "p25rx_amd", "csrc"), "asan"], env=dict(os.environ, HIPCC=hipcc))
+    exe = os.path.join(ROOT, "build", "tune_host_asan")
+    # host code only is instrumented (the driver has no device code), as for tests/native/k1_geometry_driver.cpp
+    subprocess.check_call([hipcc, "-x", "hip", "--offload-arch=gfx950", "-O1", "-g", "-std=c++17",
+                           "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=all",
+                           "-fno-omit-frame-pointer", "-I" + os.path.join(ROOT, "include"), "-o", exe,
+                           os.path.join(ROOT, "tests", "native", "tune_host_driver.cpp"), "-L" + os.path.join(ROOT, "build"),
+                           "-lp25fe_asan", "-Wl,-rpath," + os.path.join(ROOT, "build"), "-Wl,-rpath,/opt/rocm/lib"])
+    assert "tune host driver ok" in run_clean(exe)
