@@ -1335,26 +1335,36 @@ static int launch_k6(p25fe_t* h, const void* d_iq, int fmt, size_t n_hist, size_
 }
 
 // --------------------------------------------------------------------------------------------
-// Rational resampler (SPEC 3.0b; kernel: k_resample).  The object: the ratio, the table's device copy in the kernel's layout, and the
-// state of the host streaming form (position, format, the last T - 1 samples per channel as they came in).
+// Rational resampler (SPEC 3.0b; kernel: k_resample) and tuner (SPEC 3.0c; kernel: k_tune).  The tuner is the resampler with a mixer
+// in front, on the device and here: RsCore is what both objects hold -- the ratio, the table's device copy in the kernel's layout,
+// and the state of the host streaming form (position, format, the last T - 1 samples per input row as they came in).  The resampler
+// is C input rows to C output rows; the tuner is ONE input row to K output rows, plus the channels' frequencies: one rotator table per
+// distinct denominator and the per-channel numbers (TuneCh) in device memory.
 // --------------------------------------------------------------------------------------------
-struct p25fe_resampler {
+struct RsCore {
     p25fe_t* h = nullptr;
     int device = 0;                        // h's, kept here: destroying the object must not read the handle
     int L = 0, M = 0, T = 0, TP = 0;
+    size_t rows_in = 0;                    // input rows: the handle's channels (resampler), 1 (tuner)
     DevBuf d_taps, d_in, d_out;
-    uint64_t pos = 0;                      // samples consumed per channel
+    uint64_t pos = 0;                      // samples consumed per row
     int fmt = -1;                          // format of the stream (-1: none yet)
-    std::vector<unsigned char> stage;      // host image of the device rows of one p25fe_resample call
-    std::vector<unsigned char> hist;       // [C][T - 1] samples in the stream's format, oldest first (the valid ones are the last min(pos, T - 1))
+    std::vector<unsigned char> stage;      // host image of the device rows of one streaming call
+    std::vector<unsigned char> hist;       // [rows_in][T - 1] samples in the stream's format, oldest first (the valid ones are the last min(pos, T - 1))
+};
+struct p25fe_resampler : RsCore {};
+struct p25fe_tuner : RsCore {
+    int K = 0;
+    int rot_off = 0;                       // floats of dynamic LDS in front of the rotator's copy
+    size_t lds = 0;                        // dynamic LDS of a launch: the table, and the largest rotator that is copied there
+    DevBuf d_rot, d_ch;
 };
 
+static uint64_t gcd_u64(uint64_t a, uint64_t b) { while (b) { const uint64_t t = a % b; a = b; b = t; } return a; }
 static bool rs_ratio_ok(int64_t L, int64_t M)
 {
     if (L < 1 || L > P25FE_RS_MAX_L || M <= L || M > P25FE_RS_MAX_M) return false;
-    int64_t a = M, b = L;
-    while (b) { const int64_t t = a % b; a = b; b = t; }
-    return a == 1;
+    return gcd_u64((uint64_t)M, (uint64_t)L) == 1;
 }
 static bool rs_shape_ok(int64_t L, int64_t M, int64_t T)
 {
@@ -1369,64 +1379,6 @@ static double rs_i0(double x)
     for (int k = 1; k < 64; ++k) { t *= (x / (2.0 * k)) * (x / (2.0 * k)); s += t; if (t < 1e-18 * s) break; }
     return s;
 }
-
-static int launch_resample(p25fe_resampler* rs, const void* d_iq, int fmt, size_t ch_stride, size_t n_hist, size_t n, uint64_t abs_first,
-                           float* d_out, size_t out_stride, hipStream_t st)
-{
-    p25fe_t* h = rs->h;
-    if (!d_iq || !d_out || position_refused(abs_first)) return P25FE_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(d_iq) & 15u) != 0 || (reinterpret_cast<uintptr_t>(d_out) & 7u) != 0 ||
-        (h->C > 1 && ch_stride % fmt_stride_unit(fmt) != 0))
-        return P25FE_ERR_ARG;
-    const size_t n_out = p25fe_n_resample(rs->L, rs->M, abs_first, n);
-    if (out_stride < n_out) return P25FE_ERR_ARG;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (n_out == 0) return P25FE_OK;
-    const int L = rs->L, M = rs->M, T = rs->T;
-    RsArgs a;
-    a.x = d_iq; a.ch_stride = (long)ch_stride; a.n_hist = (long)n_hist; a.n_new = (long)n;
-    a.y = d_out; a.y_stride = (long)out_stride; a.n_out = (long)n_out;
-    a.taps = rs->d_taps.as<float>(); a.L = L; a.M = M; a.T = T; a.TP = rs->TP;
-    // owned output 0 is output floor(abs_first L / M) of the stream; with abs_first = qa M + ra it is output qa L + mr, whose
-    // u = (qa L + mr) M + M - 1: its input index is qa M + (mr M + M - 1) div L -- only ra matters (the position grid is M)
-    const int ra = (int)(abs_first % (uint64_t)M), mr = ra * L / M, ur = mr * M + M - 1;
-    a.p0 = ur % L; a.d0 = ur / L - ra;
-    // the sub-tile fits the window: its last output's newest sample sits at position <= (L - 1 + (tile - 1) M) / L + T - 1 < RS_NIN
-    const int fit = 1 + (RS_NIN - T) * L / M;
-    a.gl = WV - WV % L;
-    if (fit >= a.gl) { a.R = fit / a.gl < RS_R ? fit / a.gl : RS_R; a.tile = a.gl * a.R; }
-    else { a.R = 1; a.tile = fit; }
-    const size_t per_wg = (size_t)a.tile * RS_SUBS;
-    const dim3 grid((unsigned)((n_out + per_wg - 1) / per_wg), (unsigned)h->C);
-    const size_t lds = sizeof(float) * (size_t)L * (size_t)rs->TP;
-    const WideConv cv = wide_conv_of(h);
-    (void)hipGetLastError();                                        // the check below is for THIS launch: drop what an earlier call of the thread left behind
-    if (fmt == P25FE_FMT_CF32) hipLaunchKernelGGL((k_resample<P25FE_FMT_CF32, false>), grid, dim3(WV), lds, st, a, cv);
-    else if (fmt == P25FE_FMT_S16) hipLaunchKernelGGL((k_resample<P25FE_FMT_S16, false>), grid, dim3(WV), lds, st, a, cv);
-    else if (cv.lut) hipLaunchKernelGGL((k_resample<P25FE_FMT_U8, true>), grid, dim3(WV), lds, st, a, cv);
-    else hipLaunchKernelGGL((k_resample<P25FE_FMT_U8, false>), grid, dim3(WV), lds, st, a, cv);
-    HIPCHK(h, hipGetLastError());
-    return P25FE_OK;
-}
-
-// --------------------------------------------------------------------------------------------
-// Tuner (SPEC 3.0c; kernel: k_tune): the resampler's object for ONE input capture and K output rows, plus the channels'
-// frequencies: one rotator table per distinct denominator and the per-channel numbers (TuneCh) in device memory.
-// --------------------------------------------------------------------------------------------
-struct p25fe_tuner {
-    p25fe_t* h = nullptr;
-    int device = 0;                        // h's, kept here: destroying the object must not read the handle
-    int L = 0, M = 0, T = 0, TP = 0, K = 0;
-    int rot_off = 0;                       // floats of dynamic LDS in front of the rotator's copy
-    size_t lds = 0;                        // dynamic LDS of a launch: the table, and the largest rotator that is copied there
-    DevBuf d_taps, d_rot, d_ch, d_in, d_out;
-    uint64_t pos = 0;                      // samples consumed
-    int fmt = -1;                          // format of the stream (-1: none yet)
-    std::vector<unsigned char> stage;      // host image of the device row of one p25fe_tune call
-    std::vector<unsigned char> hist;       // [T - 1] samples in the stream's format, oldest first
-};
-
-static uint64_t gcd_u64(uint64_t a, uint64_t b) { while (b) { const uint64_t t = a % b; a = b; b = t; } return a; }
 // num / den in lowest terms inside the tuner's limits (0 / 1 is the centre)
 static bool tn_freq_ok(int64_t num, int64_t den)
 {
@@ -1435,43 +1387,163 @@ static bool tn_freq_ok(int64_t num, int64_t den)
     return 2 * an <= den && gcd_u64((uint64_t)an, (uint64_t)den) == 1;
 }
 
-static int launch_tune(p25fe_tuner* tn, const void* d_iq, int fmt, size_t n_hist, size_t n, uint64_t abs_first, float* d_out,
-                       size_t out_stride, hipStream_t st)
+// A new object of either kind: the shape and the table are checked first (they need no handle, and no device is touched before
+// they pass), then the table goes to the device in the kernel's layout.  *out stays null on any failure.
+template <class Obj>
+static int rs_create(Obj** out, p25fe_t* h, int32_t L, int32_t M, int32_t T, const float* taps, size_t rows_in)
 {
-    p25fe_t* h = tn->h;
-    if (!d_iq || !d_out || position_refused(abs_first)) return P25FE_ERR_ARG;
-    if ((reinterpret_cast<uintptr_t>(d_iq) & 15u) != 0 || (reinterpret_cast<uintptr_t>(d_out) & 7u) != 0) return P25FE_ERR_ARG;
-    const size_t n_out = p25fe_n_resample(tn->L, tn->M, abs_first, n);
-    if (out_stride < n_out) return P25FE_ERR_ARG;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (n_out == 0) return P25FE_OK;
-    const int L = tn->L, M = tn->M, T = tn->T;
-    TuneArgs ta;
-    RsArgs& a = ta.r;
-    a.x = d_iq; a.ch_stride = 0; a.n_hist = (long)n_hist; a.n_new = (long)n;
+    if (!rs_shape_ok(L, M, T) || !taps) return P25FE_ERR_ARG;
+    for (int k = 0; k < L * T; ++k) if (!finite_f(taps[k])) return P25FE_ERR_ARG;
+    if (!h) return P25FE_ERR_ARG;
+    Obj* o = new (std::nothrow) Obj;
+    if (!o) return P25FE_ERR_NOMEM;
+    o->h = h; o->device = h->cfg.device; o->L = L; o->M = M; o->T = T; o->TP = rs_tap_pitch(T); o->rows_in = rows_in;
+    // the kernel's layout: phase-major rows of pitch TP, the pad zero
+    std::vector<float> tab((size_t)L * o->TP, 0.0f);
+    for (int p = 0; p < L; ++p) for (int j = 0; j < T; ++j) tab[(size_t)p * o->TP + j] = taps[(size_t)j * L + p];
+    o->hist.assign(rows_in * (size_t)(T - 1) * 8, 0);
+    if (hipSetDevice(h->cfg.device) != hipSuccess || o->d_taps.ensure(tab.size() * sizeof(float)) != hipSuccess ||
+        hipMemcpy(o->d_taps.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        h->last_hip = (int)hipGetLastError(); delete o; return P25FE_ERR_HIP;
+    }
+    *out = o;
+    return P25FE_OK;
+}
+
+// the kernel's arguments for one range of the stream (everything but the tuner's own)
+static void rs_fill_args(const RsCore* o, RsArgs& a, const void* d_iq, size_t ch_stride, size_t n_hist, size_t n, uint64_t abs_first,
+                         float* d_out, size_t out_stride, size_t n_out)
+{
+    const int L = o->L, M = o->M, T = o->T;
+    a.x = d_iq; a.ch_stride = (long)ch_stride; a.n_hist = (long)n_hist; a.n_new = (long)n;
     a.y = d_out; a.y_stride = (long)out_stride; a.n_out = (long)n_out;
-    a.taps = tn->d_taps.as<float>(); a.L = L; a.M = M; a.T = T; a.TP = tn->TP;
-    // owned output 0 and the sub-tile's fit: launch_resample's, word for word (the position grid of the RESAMPLER is M; the mixer's
-    // phase takes the whole position)
+    a.taps = o->d_taps.as<float>(); a.L = L; a.M = M; a.T = T; a.TP = o->TP;
+    // owned output 0 is output floor(abs_first L / M) of the stream; with abs_first = qa M + ra it is output qa L + mr, whose
+    // u = (qa L + mr) M + M - 1: its input index is qa M + (mr M + M - 1) div L -- only ra matters (the position grid of the
+    // resampler is M; the tuner's mixer takes the whole position)
     const int ra = (int)(abs_first % (uint64_t)M), mr = ra * L / M, ur = mr * M + M - 1;
     a.p0 = ur % L; a.d0 = ur / L - ra;
+    // the sub-tile fits the window: its last output's newest sample sits at position <= (L - 1 + (tile - 1) M) / L + T - 1 < RS_NIN
     const int fit = 1 + (RS_NIN - T) * L / M;
     a.gl = WV - WV % L;
     if (fit >= a.gl) { a.R = fit / a.gl < RS_R ? fit / a.gl : RS_R; a.tile = a.gl * a.R; }
     else { a.R = 1; a.tile = fit; }
-    ta.ch = tn->d_ch.as<TuneCh>(); ta.K = tn->K; ta.rot_off = tn->rot_off; ta.abs_first = abs_first;
-    // workgroup index = sub-tile group * K + channel: the channel varies fastest.  Groups beyond grid.x's range go to grid.y
-    const size_t per_wg = (size_t)a.tile * RS_SUBS, groups = (n_out + per_wg - 1) / per_wg;
-    const size_t gx = std::min(groups, (size_t)0x7fffffffu / (size_t)tn->K), gy = (groups + gx - 1) / gx;
-    if (gy > 65535) return P25FE_ERR_ARG;
-    const dim3 grid((unsigned)(gx * (size_t)tn->K), (unsigned)gy);
+}
+
+// what a launch refuses about its pointers: the position, the alignment of both, and, where there is more than one input row,
+// the rows' distance
+static bool rs_pointers_refused(const RsCore* o, const void* d_iq, int fmt, size_t ch_stride, uint64_t abs_first, const float* d_out)
+{
+    if (!d_iq || !d_out || position_refused(abs_first)) return true;
+    return (reinterpret_cast<uintptr_t>(d_iq) & 15u) != 0 || (reinterpret_cast<uintptr_t>(d_out) & 7u) != 0 ||
+           (o->rows_in > 1 && ch_stride % fmt_stride_unit(fmt) != 0);
+}
+
+template <int FMT, bool LUTM>
+static void rs_launch_as(dim3 grid, size_t lds, hipStream_t st, const RsArgs& a, const WideConv& cv)
+{
+    hipLaunchKernelGGL((k_resample<FMT, LUTM>), grid, dim3(WV), lds, st, a, cv);
+}
+template <int FMT, bool LUTM>
+static void rs_launch_as(dim3 grid, size_t lds, hipStream_t st, const TuneArgs& a, const WideConv& cv)
+{
+    hipLaunchKernelGGL((k_tune<FMT, LUTM>), grid, dim3(WV), lds, st, a, cv);
+}
+// the instance of either kernel for a format: cf32, s16, u8 with the table as arithmetic or looked up
+template <class Args>
+static void rs_dispatch(int fmt, dim3 grid, size_t lds, hipStream_t st, const Args& a, const WideConv& cv)
+{
+    if (fmt == P25FE_FMT_CF32) rs_launch_as<P25FE_FMT_CF32, false>(grid, lds, st, a, cv);
+    else if (fmt == P25FE_FMT_S16) rs_launch_as<P25FE_FMT_S16, false>(grid, lds, st, a, cv);
+    else if (cv.lut) rs_launch_as<P25FE_FMT_U8, true>(grid, lds, st, a, cv);
+    else rs_launch_as<P25FE_FMT_U8, false>(grid, lds, st, a, cv);
+}
+
+// One range through k_resample (tn null: o->rows_in rows in and out) or k_tune (tn is o: one row in, tn->K rows out).
+static int rs_launch(RsCore* o, const p25fe_tuner* tn, const void* d_iq, int fmt, size_t ch_stride, size_t n_hist, size_t n,
+                     uint64_t abs_first, float* d_out, size_t out_stride, hipStream_t st)
+{
+    p25fe_t* h = o->h;
+    if (rs_pointers_refused(o, d_iq, fmt, ch_stride, abs_first, d_out)) return P25FE_ERR_ARG;
+    const size_t n_out = p25fe_n_resample(o->L, o->M, abs_first, n);
+    if (out_stride < n_out) return P25FE_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (n_out == 0) return P25FE_OK;
+    TuneArgs ta;
+    rs_fill_args(o, ta.r, d_iq, ch_stride, n_hist, n, abs_first, d_out, out_stride, n_out);
+    const size_t per_wg = (size_t)ta.r.tile * RS_SUBS, groups = (n_out + per_wg - 1) / per_wg;
+    dim3 grid((unsigned)groups, (unsigned)o->rows_in);
+    if (tn) {
+        ta.ch = tn->d_ch.as<TuneCh>(); ta.K = tn->K; ta.rot_off = tn->rot_off; ta.abs_first = abs_first;
+        // workgroup index = sub-tile group * K + channel: the channel varies fastest.  Groups beyond grid.x's range go to grid.y
+        const size_t gx = std::min(groups, (size_t)0x7fffffffu / (size_t)tn->K), gy = (groups + gx - 1) / gx;
+        if (gy > 65535) return P25FE_ERR_ARG;
+        grid = dim3((unsigned)(gx * (size_t)tn->K), (unsigned)gy);
+    }
     const WideConv cv = wide_conv_of(h);
-    (void)hipGetLastError();                                        // the check below is for THIS launch
-    if (fmt == P25FE_FMT_CF32) hipLaunchKernelGGL((k_tune<P25FE_FMT_CF32, false>), grid, dim3(WV), tn->lds, st, ta, cv);
-    else if (fmt == P25FE_FMT_S16) hipLaunchKernelGGL((k_tune<P25FE_FMT_S16, false>), grid, dim3(WV), tn->lds, st, ta, cv);
-    else if (cv.lut) hipLaunchKernelGGL((k_tune<P25FE_FMT_U8, true>), grid, dim3(WV), tn->lds, st, ta, cv);
-    else hipLaunchKernelGGL((k_tune<P25FE_FMT_U8, false>), grid, dim3(WV), tn->lds, st, ta, cv);
+    (void)hipGetLastError();                                        // the check below is for THIS launch: drop what an earlier call of the thread left behind
+    if (tn) rs_dispatch(fmt, grid, tn->lds, st, ta, cv);
+    else rs_dispatch(fmt, grid, sizeof(float) * (size_t)o->L * (size_t)o->TP, st, ta.r, cv);
     HIPCHK(h, hipGetLastError());
+    return P25FE_OK;
+}
+
+// The host streaming call of either object (tn as in rs_launch): n new samples of each input row, *n_out outputs in each output row
+// (row r at out + r * cap).  The state (history, position, format) moves on whether or not the range yields an output.
+static int rs_stream(RsCore* o, const p25fe_tuner* tn, const void* iq, int fmt, size_t n, float* out, size_t cap, size_t* n_out)
+{
+    if (!o || !o->h || !n_out || !wide_fmt_known(fmt) || (n && !iq)) return P25FE_ERR_ARG;
+    if (o->fmt >= 0 && fmt != o->fmt) return P25FE_ERR_FORMAT;
+    if (position_refused(o->pos) || n >= P25FE_MAX_POSITION) return P25FE_ERR_ARG;
+    p25fe_t* h = o->h;
+    const size_t C = o->rows_in, rows_out = tn ? (size_t)tn->K : C, bps = fmt_bytes(fmt), keep = (size_t)o->T - 1;
+    const size_t no = p25fe_n_resample(o->L, o->M, o->pos, n);
+    *n_out = no;
+    if (no > cap || (no && !out)) return P25FE_ERR_CAPACITY;
+    const size_t n_hist = o->pos < keep ? (size_t)o->pos : keep;
+    const unsigned char* src = static_cast<const unsigned char*>(iq);
+    if (no) {
+        // device rows: [history, right-aligned in `lead` slots | n new samples], owned sample 0 of every row 16-byte aligned
+        const size_t lead = round_up(keep, 8), stride = lead + round_up(n, 8);
+        HIPCHK(h, hipSetDevice(h->cfg.device));
+        HIPCHK(h, o->d_in.ensure(C * stride * bps));
+        HIPCHK(h, o->d_out.ensure(rows_out * no * sizeof(float) * 2));
+        unsigned char* din = o->d_in.as<unsigned char>();
+        // the rows are put together on the host and go over in ONE copy (no transfers of a few bytes to odd addresses)
+        o->stage.assign(C * stride * bps, 0);
+        for (size_t c = 0; c < C; ++c) {
+            unsigned char* row = o->stage.data() + c * stride * bps;
+            if (n_hist) memcpy(row + (lead - n_hist) * bps, o->hist.data() + (c * keep + keep - n_hist) * bps, n_hist * bps);
+            memcpy(row + lead * bps, src + c * n * bps, n * bps);
+        }
+        HIPCHK(h, hipMemcpyAsync(din, o->stage.data(), o->stage.size(), hipMemcpyHostToDevice, h->stream));
+        if (int rc = rs_launch(o, tn, din + lead * bps, fmt, stride, n_hist, n, o->pos, o->d_out.as<float>(), no, h->stream)) return rc;
+        for (size_t r = 0; r < rows_out; ++r)
+            HIPCHK(h, hipMemcpyAsync(out + r * cap * 2, o->d_out.as<float>() + r * no * 2, no * sizeof(float) * 2, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    // the state moves: the last T - 1 samples of [history | new]
+    for (size_t c = 0; keep && c < C; ++c) {
+        unsigned char* hc = o->hist.data() + c * keep * bps;
+        if (n >= keep) memcpy(hc, src + (c * n + n - keep) * bps, keep * bps);
+        else { memmove(hc, hc + n * bps, (keep - n) * bps); memcpy(hc + (keep - n) * bps, src + c * n * bps, n * bps); }
+    }
+    o->pos += n; o->fmt = fmt;
+    return P25FE_OK;
+}
+
+template <class Obj>
+static void rs_destroy(Obj* o)
+{
+    if (!o) return;
+    (void)hipSetDevice(o->device);
+    delete o;
+}
+static int rs_reset(RsCore* o)
+{
+    if (!o) return P25FE_ERR_ARG;
+    o->pos = 0; o->fmt = -1;
+    std::fill(o->hist.begin(), o->hist.end(), (unsigned char)0);
     return P25FE_OK;
 }
 
@@ -1480,8 +1552,7 @@ extern "C" {
 int p25fe_resampler_design(uint32_t fs_in_hz, int32_t* L, int32_t* M, int32_t* T, float* taps, size_t cap)
 {
     if (!L || !M || !T || fs_in_hz == 0) return P25FE_ERR_ARG;
-    uint64_t a = P25FE_RS_RATE_OUT_HZ, b = fs_in_hz;
-    while (b) { const uint64_t t = a % b; a = b; b = t; }
+    const uint64_t a = gcd_u64(P25FE_RS_RATE_OUT_HZ, fs_in_hz);
     const int64_t l = (int64_t)(P25FE_RS_RATE_OUT_HZ / a), m = (int64_t)(fs_in_hz / a);
     const int64_t t = ((int64_t)fs_in_hz + 29999) / 30000;
     if (!rs_shape_ok(l, m, t)) return P25FE_ERR_ARG;
@@ -1519,89 +1590,24 @@ size_t p25fe_n_resample(int32_t L, int32_t M, uint64_t abs_first, size_t n)
 int p25fe_resampler_create(p25fe_t* h, int32_t L, int32_t M, int32_t T, const float* taps, p25fe_resampler_t** out)
 {
     if (out) *out = nullptr;
-    if (!out || !rs_shape_ok(L, M, T) || !taps || !h) return P25FE_ERR_ARG;      // (the shape first: it needs neither table nor handle)
-    for (int k = 0; k < L * T; ++k) if (!finite_f(taps[k])) return P25FE_ERR_ARG;
-    p25fe_resampler* rs = new (std::nothrow) p25fe_resampler;
-    if (!rs) return P25FE_ERR_NOMEM;
-    rs->h = h; rs->device = h->cfg.device; rs->L = L; rs->M = M; rs->T = T; rs->TP = rs_tap_pitch(T);
-    // the kernel's layout: phase-major rows of pitch TP, the pad zero
-    std::vector<float> tab((size_t)L * rs->TP, 0.0f);
-    for (int p = 0; p < L; ++p) for (int j = 0; j < T; ++j) tab[(size_t)p * rs->TP + j] = taps[(size_t)j * L + p];
-    rs->hist.assign((size_t)h->C * (size_t)(T - 1) * 8, 0);
-    int rc = P25FE_OK;
-    if (hipSetDevice(h->cfg.device) != hipSuccess || rs->d_taps.ensure(tab.size() * sizeof(float)) != hipSuccess ||
-        hipMemcpy(rs->d_taps.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-        rc = P25FE_ERR_HIP;
-    if (rc) { h->last_hip = (int)hipGetLastError(); delete rs; return rc; }
-    *out = rs;
-    return P25FE_OK;
+    if (!out) return P25FE_ERR_ARG;
+    return rs_create(out, h, L, M, T, taps, h ? (size_t)h->C : 0);
 }
 
-void p25fe_resampler_destroy(p25fe_resampler_t* rs)
-{
-    if (!rs) return;
-    (void)hipSetDevice(rs->device);
-    delete rs;
-}
+void p25fe_resampler_destroy(p25fe_resampler_t* rs) { rs_destroy(rs); }
 
-int p25fe_resampler_reset(p25fe_resampler_t* rs)
-{
-    if (!rs) return P25FE_ERR_ARG;
-    rs->pos = 0; rs->fmt = -1;
-    std::fill(rs->hist.begin(), rs->hist.end(), (unsigned char)0);
-    return P25FE_OK;
-}
+int p25fe_resampler_reset(p25fe_resampler_t* rs) { return rs_reset(rs); }
 
 int p25fe_resample_dev(p25fe_resampler_t* rs, const void* d_iq, int fmt, size_t ch_stride, size_t n_hist, size_t n, uint64_t abs_first,
                        float* d_out, size_t out_stride, void* stream)
 {
     if (!rs || !rs->h || !wide_fmt_known(fmt)) return P25FE_ERR_ARG;
-    return launch_resample(rs, d_iq, fmt, ch_stride, n_hist, n, abs_first, d_out, out_stride, (hipStream_t)stream);
+    return rs_launch(rs, nullptr, d_iq, fmt, ch_stride, n_hist, n, abs_first, d_out, out_stride, (hipStream_t)stream);
 }
 
 int p25fe_resample(p25fe_resampler_t* rs, const void* iq, int fmt, size_t n, float* out, size_t cap, size_t* n_out)
 {
-    if (!rs || !rs->h || !n_out || !wide_fmt_known(fmt) || (n && !iq)) return P25FE_ERR_ARG;
-    if (rs->fmt >= 0 && fmt != rs->fmt) return P25FE_ERR_FORMAT;
-    if (position_refused(rs->pos) || n >= P25FE_MAX_POSITION) return P25FE_ERR_ARG;
-    p25fe_t* h = rs->h;
-    const size_t C = (size_t)h->C, bps = fmt_bytes(fmt), keep = (size_t)rs->T - 1;
-    const size_t no = p25fe_n_resample(rs->L, rs->M, rs->pos, n);
-    *n_out = no;
-    if (no > cap || (no && !out)) return P25FE_ERR_CAPACITY;
-    const size_t n_hist = rs->pos < keep ? (size_t)rs->pos : keep;
-    if (no) {
-        // device rows: [history, right-aligned in `lead` slots | n new samples], owned sample 0 of every row 16-byte aligned
-        const size_t lead = round_up(keep, 8), stride = lead + round_up(n, 8);
-        HIPCHK(h, hipSetDevice(h->cfg.device));
-        HIPCHK(h, rs->d_in.ensure(C * stride * bps));
-        HIPCHK(h, rs->d_out.ensure(C * no * sizeof(float) * 2));
-        unsigned char* din = rs->d_in.as<unsigned char>();
-        const unsigned char* src = static_cast<const unsigned char*>(iq);
-        // the rows are put together on the host and go over in ONE copy (no transfers of a few bytes to odd addresses)
-        rs->stage.assign(C * stride * bps, 0);
-        for (size_t c = 0; c < C; ++c) {
-            unsigned char* row = rs->stage.data() + c * stride * bps;
-            if (n_hist) memcpy(row + (lead - n_hist) * bps, rs->hist.data() + (c * keep + keep - n_hist) * bps, n_hist * bps);
-            memcpy(row + lead * bps, src + c * n * bps, n * bps);
-        }
-        HIPCHK(h, hipMemcpyAsync(din, rs->stage.data(), rs->stage.size(), hipMemcpyHostToDevice, h->stream));
-        if (int rc = launch_resample(rs, din + lead * bps, fmt, stride, n_hist, n, rs->pos, rs->d_out.as<float>(), no, h->stream)) return rc;
-        for (size_t c = 0; c < C; ++c)
-            HIPCHK(h, hipMemcpyAsync(out + c * cap * 2, rs->d_out.as<float>() + c * no * 2, no * sizeof(float) * 2, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    // the state moves: the last T - 1 samples of [history | new]
-    if (keep) {
-        const unsigned char* src = static_cast<const unsigned char*>(iq);
-        for (size_t c = 0; c < C; ++c) {
-            unsigned char* hc = rs->hist.data() + c * keep * bps;
-            if (n >= keep) memcpy(hc, src + (c * n + n - keep) * bps, keep * bps);
-            else { memmove(hc, hc + n * bps, (keep - n) * bps); memcpy(hc + (keep - n) * bps, src + c * n * bps, n * bps); }
-        }
-    }
-    rs->pos += n; rs->fmt = fmt;
-    return P25FE_OK;
+    return rs_stream(rs, nullptr, iq, fmt, n, out, cap, n_out);
 }
 
 int p25fe_tuner_freq(uint32_t fs_in_hz, int64_t offset_hz, int32_t* num, int32_t* den)
@@ -1632,16 +1638,11 @@ int p25fe_tuner_create(p25fe_t* h, int32_t L, int32_t M, int32_t T, const float*
                        const int32_t* den, p25fe_tuner_t** out)
 {
     if (out) *out = nullptr;
-    if (!out || !rs_shape_ok(L, M, T) || n_out_channels < 1 || n_out_channels > P25FE_TUNE_MAX_CH || !taps || !num || !den) return P25FE_ERR_ARG;
+    if (!out || n_out_channels < 1 || n_out_channels > P25FE_TUNE_MAX_CH || !num || !den) return P25FE_ERR_ARG;
     for (int k = 0; k < n_out_channels; ++k) if (!tn_freq_ok(num[k], den[k])) return P25FE_ERR_ARG;
-    for (int k = 0; k < L * T; ++k) if (!finite_f(taps[k])) return P25FE_ERR_ARG;
-    if (!h) return P25FE_ERR_ARG;
-    p25fe_tuner* tn = new (std::nothrow) p25fe_tuner;
-    if (!tn) return P25FE_ERR_NOMEM;
-    const int K = n_out_channels;
-    tn->h = h; tn->device = h->cfg.device; tn->L = L; tn->M = M; tn->T = T; tn->TP = rs_tap_pitch(T); tn->K = K;
-    std::vector<float> tab((size_t)L * tn->TP, 0.0f);               // the kernel's layout: phase-major rows of pitch TP, the pad zero
-    for (int p = 0; p < L; ++p) for (int j = 0; j < T; ++j) tab[(size_t)p * tn->TP + j] = taps[(size_t)j * L + p];
+    p25fe_tuner* tn = nullptr;
+    if (int rc = rs_create(&tn, h, L, M, T, taps, 1)) return rc;    // (the handle is looked at last)
+    const int K = tn->K = n_out_channels;
     // one rotator per distinct denominator, (cos, sin) interleaved, one after the other in one buffer
     std::vector<long> at(P25FE_TUNE_MAX_DEN + 1, -1);
     std::vector<float> rot, cs;
@@ -1655,87 +1656,40 @@ int p25fe_tuner_create(p25fe_t* h, int32_t L, int32_t M, int32_t T, const float*
         (void)p25fe_tuner_rotator(D, cs.data(), cs.size());
         for (int i = 0; i < D; ++i) { rot.push_back(cs[i]); rot.push_back(cs[D + i]); }
     }
-    tn->rot_off = (int)round_up(tab.size(), 2);
+    tn->rot_off = (int)round_up((size_t)L * tn->TP, 2);
     tn->lds = sizeof(float) * ((size_t)tn->rot_off + 2 * (size_t)lds_den);
-    tn->hist.assign((size_t)(T - 1) * 8, 0);
-    int rc = P25FE_OK;
-    if (hipSetDevice(h->cfg.device) != hipSuccess || tn->d_taps.ensure(tab.size() * sizeof(float)) != hipSuccess ||
-        tn->d_rot.ensure(rot.size() * sizeof(float)) != hipSuccess || tn->d_ch.ensure((size_t)K * sizeof(TuneCh)) != hipSuccess)
-        rc = P25FE_ERR_HIP;
-    if (!rc) {
-        std::vector<TuneCh> ch((size_t)K);
+    std::vector<TuneCh> ch((size_t)K);
+    if (tn->d_rot.ensure(rot.size() * sizeof(float)) == hipSuccess && tn->d_ch.ensure((size_t)K * sizeof(TuneCh)) == hipSuccess) {
         for (int k = 0; k < K; ++k) {
             ch[k].rot = tn->d_rot.as<float2>() + at[den[k]];
             ch[k].D = den[k];
             ch[k].nm = (int)(((int64_t)num[k] % den[k] + den[k]) % den[k]);
         }
-        if (hipMemcpy(tn->d_taps.p, tab.data(), tab.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(tn->d_rot.p, rot.data(), rot.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy(tn->d_ch.p, ch.data(), ch.size() * sizeof(TuneCh), hipMemcpyHostToDevice) != hipSuccess)
-            rc = P25FE_ERR_HIP;
+        if (hipMemcpy(tn->d_rot.p, rot.data(), rot.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
+            hipMemcpy(tn->d_ch.p, ch.data(), ch.size() * sizeof(TuneCh), hipMemcpyHostToDevice) == hipSuccess) {
+            *out = tn;
+            return P25FE_OK;
+        }
     }
-    if (rc) { h->last_hip = (int)hipGetLastError(); delete tn; return rc; }
-    *out = tn;
-    return P25FE_OK;
-}
-
-void p25fe_tuner_destroy(p25fe_tuner_t* tn)
-{
-    if (!tn) return;
-    (void)hipSetDevice(tn->device);
+    h->last_hip = (int)hipGetLastError();
     delete tn;
+    return P25FE_ERR_HIP;
 }
 
-int p25fe_tuner_reset(p25fe_tuner_t* tn)
-{
-    if (!tn) return P25FE_ERR_ARG;
-    tn->pos = 0; tn->fmt = -1;
-    std::fill(tn->hist.begin(), tn->hist.end(), (unsigned char)0);
-    return P25FE_OK;
-}
+void p25fe_tuner_destroy(p25fe_tuner_t* tn) { rs_destroy(tn); }
+
+int p25fe_tuner_reset(p25fe_tuner_t* tn) { return rs_reset(tn); }
 
 int p25fe_tune_dev(p25fe_tuner_t* tn, const void* d_iq, int fmt, size_t n_hist, size_t n, uint64_t abs_first, float* d_out,
                    size_t out_stride, void* stream)
 {
     if (!tn || !tn->h || !wide_fmt_known(fmt)) return P25FE_ERR_ARG;
-    return launch_tune(tn, d_iq, fmt, n_hist, n, abs_first, d_out, out_stride, (hipStream_t)stream);
+    return rs_launch(tn, tn, d_iq, fmt, 0, n_hist, n, abs_first, d_out, out_stride, (hipStream_t)stream);
 }
 
 int p25fe_tune(p25fe_tuner_t* tn, const void* iq, int fmt, size_t n, float* out, size_t cap, size_t* n_out)
 {
-    if (!tn || !tn->h || !n_out || !wide_fmt_known(fmt) || (n && !iq)) return P25FE_ERR_ARG;
-    if (tn->fmt >= 0 && fmt != tn->fmt) return P25FE_ERR_FORMAT;
-    if (position_refused(tn->pos) || n >= P25FE_MAX_POSITION) return P25FE_ERR_ARG;
-    p25fe_t* h = tn->h;
-    const size_t K = (size_t)tn->K, bps = fmt_bytes(fmt), keep = (size_t)tn->T - 1;
-    const size_t no = p25fe_n_resample(tn->L, tn->M, tn->pos, n);
-    *n_out = no;
-    if (no > cap || (no && !out)) return P25FE_ERR_CAPACITY;
-    const size_t n_hist = tn->pos < keep ? (size_t)tn->pos : keep;
-    const unsigned char* src = static_cast<const unsigned char*>(iq);
-    if (no) {
-        // the device row: [history, right-aligned in `lead` slots | n new samples], owned sample 0 16-byte aligned, in ONE copy
-        const size_t lead = round_up(keep, 8), len = lead + round_up(n, 8);
-        HIPCHK(h, hipSetDevice(h->cfg.device));
-        HIPCHK(h, tn->d_in.ensure(len * bps));
-        HIPCHK(h, tn->d_out.ensure(K * no * sizeof(float) * 2));
-        unsigned char* din = tn->d_in.as<unsigned char>();
-        tn->stage.assign(len * bps, 0);
-        if (n_hist) memcpy(tn->stage.data() + (lead - n_hist) * bps, tn->hist.data() + (keep - n_hist) * bps, n_hist * bps);
-        memcpy(tn->stage.data() + lead * bps, src, n * bps);
-        HIPCHK(h, hipMemcpyAsync(din, tn->stage.data(), tn->stage.size(), hipMemcpyHostToDevice, h->stream));
-        if (int rc = launch_tune(tn, din + lead * bps, fmt, n_hist, n, tn->pos, tn->d_out.as<float>(), no, h->stream)) return rc;
-        for (size_t k = 0; k < K; ++k)
-            HIPCHK(h, hipMemcpyAsync(out + k * cap * 2, tn->d_out.as<float>() + k * no * 2, no * sizeof(float) * 2, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    if (keep) {                                                      // the state moves: the last T - 1 samples of [history | new]
-        unsigned char* hc = tn->hist.data();
-        if (n >= keep) memcpy(hc, src + (n - keep) * bps, keep * bps);
-        else { memmove(hc, hc + n * bps, (keep - n) * bps); memcpy(hc + (keep - n) * bps, src, n * bps); }
-    }
-    tn->pos += n; tn->fmt = fmt;
-    return P25FE_OK;
+    return rs_stream(tn, tn, iq, fmt, n, out, cap, n_out);
 }
 
 // --------------------------------------------------------------------------------------------

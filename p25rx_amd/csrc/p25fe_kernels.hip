@@ -1557,179 +1557,11 @@ struct RsArgs {
     int gl, tile, R;        // lanes in use, outputs per sub-tile, outputs per lane (tile = gl * R, or tile < gl and R = 1)
 };
 
-template <int FMT, bool LUTM>
-__global__ __launch_bounds__(WV, RS_WPS) void k_resample(RsArgs a, WideConv cv)
-{
-    static_assert(FMT == P25FE_FMT_U8 || !LUTM, "only u8 has a table");
-    constexpr int LS = wide_log_spv(FMT), SPV = 1 << LS, NV = wide_nv(FMT, RS_NIN);
-    static_assert(SPV * NV * WV >= RS_NIN + SPV - 1, "the loader covers the window at every alignment");
-    __shared__ float2 X[RS_NIN];
-    extern __shared__ float RS_HT[];
-    const int tid = threadIdx.x, ch = blockIdx.y;
-    const float* lut = nullptr;
-    if constexpr (LUTM) {
-        __shared__ float LUT[256];
-        for (int k = tid; k < 256; k += WV) LUT[k] = cv.lut[k];
-        lut = LUT;
-    }
-    for (int k = tid; k < a.L * a.TP; k += WV) RS_HT[k] = a.taps[k];
-    const uint4* xb = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(a.x) + (size_t)fmt_bps(FMT) * ch * a.ch_stride);
-    float2* yb = reinterpret_cast<float2*>(a.y) + (size_t)ch * a.y_stride;
-    const int T = a.T, L = a.L, M = a.M;
-
-    const long m_wg0 = (long)blockIdx.x * ((long)a.tile * RS_SUBS);
-    const long u_wg = (long)a.p0 + m_wg0 * M;
-    long nt = (long)a.d0 + u_wg / L;                                // input index of the sub-tile's first output
-    int pt = (int)(u_wg % L);                                       // ... and its phase
-
-    uint4 v[NV];
-    // window of a sub-tile: positions k = 0 .. RS_NIN-1 are inputs base + k, base = nt - (T - 1)
-    auto load = [&](long base, bool none) {
-        const long v0 = base >> LS;
-        long lo = ((-a.n_hist) >> LS) - v0, hi = ((a.n_new - 1) >> LS) - v0;
-        lo = lo < -(1L << 30) ? -(1L << 30) : (lo > (1L << 30) ? (1L << 30) : lo);
-        hi = hi < -(1L << 30) ? -(1L << 30) : (hi > (1L << 30) ? (1L << 30) : hi);
-        const int lo32 = (int)lo, hi32 = none ? (int)lo : (int)hi;  // nothing follows the workgroup's last sub-tile: re-read one vector
-        const uint4* q = xb + v0;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            int r = tid + j * WV;
-            r = r < lo32 ? lo32 : r;
-            r = r > hi32 ? hi32 : r;
-            v[j] = q[r];
-        }
-    };
-    auto stage = [&](long base) {
-        const long v0 = base >> LS;
-        const int sh = (int)(base - (v0 << LS));                    // 0 .. SPV - 1
-        const bool interior = (v0 << LS) >= -a.n_hist && (v0 << LS) + (long)SPV * NV * WV <= a.n_new;   // uniform
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-#pragma unroll
-            for (int e = 0; e < SPV; ++e) {
-                const int k = SPV * (tid + j * WV) + e - sh;        // window position
-                float2 s2 = wide_sample<FMT, LUTM>(v[j], e, cv, lut);
-                if (!interior) {
-                    const long i = ((v0 + tid + (long)j * WV) << LS) + e;
-                    if (i < -a.n_hist || i >= a.n_new) s2 = make_float2(0.f, 0.f);
-                }
-                if (k >= 0 && k < RS_NIN) X[k] = s2;
-            }
-        }
-    };
-
-    float2 outv[RS_R];
-#pragma unroll
-    for (int r = 0; r < RS_R; ++r) outv[r] = make_float2(0.f, 0.f);
-    long out_m0 = -1;                                               // sub-tile whose outputs sit in outv (-1: none)
-    auto flush = [&]() {
-        if (out_m0 >= 0) {
-#pragma unroll
-            for (int r = 0; r < RS_R; ++r) {
-                const int k = tid + a.gl * r;
-                const long m = out_m0 + k;
-                if (tid < a.gl && r < a.R && k < a.tile && m < a.n_out) yb[m] = outv[r];
-            }
-        }
-    };
-
-    load(nt - (T - 1), false);
-    phase_sync();                                                   // the tables before their first use
-#pragma unroll 1
-    for (int it = 0; it < RS_SUBS; ++it) {
-        const long m0 = m_wg0 + (long)it * a.tile;
-        if (m0 >= a.n_out) break;                                   // uniform
-        stage(nt - (T - 1));
-        phase_sync();
-        flush();                                                    // stores before the prefetch (single in-order vmcnt queue)
-        const unsigned un = (unsigned)pt + (unsigned)a.tile * (unsigned)M;   // < 32 + 256 * 1024
-        const long nt_next = nt + un / (unsigned)L;
-        const int pt_next = (int)(un % (unsigned)L);
-        load(nt_next - (T - 1), it == RS_SUBS - 1 || m0 + a.tile >= a.n_out);
-
-        const unsigned ul = (unsigned)pt + (unsigned)tid * (unsigned)M;
-        const int q0 = (int)(ul / (unsigned)L), ph = (int)(ul % (unsigned)L);
-        const int xstep = (a.gl / L) * M;                           // window distance of a lane's outputs r and r + 1
-        const float2* xp[RS_R];
-        v2f acc[RS_R];
-#pragma unroll
-        for (int r = 0; r < RS_R; ++r) {
-            const bool act = tid < a.gl && r < a.R && tid + a.gl * r < a.tile;
-            xp[r] = X + (act ? q0 + r * xstep : 0) + (T - 1);       // idle slots walk the window's first T positions
-            acc[r] = v2f{0.f, 0.f};
-        }
-        const float* hp = RS_HT + ph * a.TP;
-        // Window reads in blocks of 8 (then 4) taps x RS_R outputs, issued from inline asm ahead of their use as in K1's walks: the
-        // 16 reads of taps j .. j+3 go out together, and each FMA step that consumes one of them issues the matching read of taps
-        // j+4 .. j+7 -- 15 window reads stay in flight behind every use.  Nothing is in flight across the loop's back edge (the
-        // compiler must never have to copy a register whose read has not landed).  The block's taps are ordinary loads issued
-        // after the first 16 reads: LDS returns in order, so the compiler's wait for them waits for nothing that the first use
-        // would not wait for anyway.
-        unsigned xb8[RS_R];                                         // byte address of the block's oldest sample per output
-#pragma unroll
-        for (int r = 0; r < RS_R; ++r) xb8[r] = lds_addr(xp[r]) - 8u * 7u;
-        int j = 0;
-#pragma unroll 1
-        for (; j + 8 <= T; j += 8) {
-            v2f g0[4 * RS_R], g1[4 * RS_R];
-            static_for<0, 4 * RS_R>([&](auto ic) {
-                constexpr int i = decltype(ic)::value, t = i / RS_R, r = i % RS_R;
-                g0[i] = lds_issue_b64<8 * (7 - t)>(xb8[r]);
-            });
-            float h[8];
-#pragma unroll
-            for (int t = 0; t < 8; ++t) h[t] = hp[j + t];
-            // all eight before the first use: a wait of the compiler's for a later one would count the window reads issued since
-            asm volatile("" : "+v"(h[0]), "+v"(h[1]), "+v"(h[2]), "+v"(h[3]), "+v"(h[4]), "+v"(h[5]), "+v"(h[6]), "+v"(h[7]));
-            static_for<0, 4 * RS_R>([&](auto ic) {
-                constexpr int i = decltype(ic)::value, t = i / RS_R, r = i % RS_R;
-                lds_landed<4 * RS_R - 1>(g0[i]);
-                acc[r] = __builtin_elementwise_fma(v2f{h[t], h[t]}, g0[i], acc[r]);
-                g1[i] = lds_issue_b64<8 * (3 - t)>(xb8[r]);
-            });
-            static_for<0, 4 * RS_R>([&](auto ic) {
-                constexpr int i = decltype(ic)::value, t = i / RS_R, r = i % RS_R;
-                lds_landed<4 * RS_R - 1 - i>(g1[i]);
-                acc[r] = __builtin_elementwise_fma(v2f{h[4 + t], h[4 + t]}, g1[i], acc[r]);
-            });
-#pragma unroll
-            for (int r = 0; r < RS_R; ++r) xb8[r] -= 64u;
-        }
-        if (j + 4 <= T) {                                           // uniform
-            v2f g0[4 * RS_R];
-            static_for<0, 4 * RS_R>([&](auto ic) {
-                constexpr int i = decltype(ic)::value, t = i / RS_R, r = i % RS_R;
-                g0[i] = lds_issue_b64<8 * (3 - t)>(xb8[r] + 32u);   // (xb8 itself may lie below the window here)
-            });
-            float h[4];
-#pragma unroll
-            for (int t = 0; t < 4; ++t) h[t] = hp[j + t];
-            static_for<0, 4 * RS_R>([&](auto ic) {
-                constexpr int i = decltype(ic)::value, t = i / RS_R, r = i % RS_R;
-                lds_landed<4 * RS_R - 1 - i>(g0[i]);
-                acc[r] = __builtin_elementwise_fma(v2f{h[t], h[t]}, g0[i], acc[r]);
-            });
-            j += 4;
-        }
-#pragma unroll 1
-        for (; j < T; ++j) {                                        // at most 3 taps
-            const float h = hp[j];
-#pragma unroll
-            for (int r = 0; r < RS_R; ++r) acc[r] = __builtin_elementwise_fma(v2f{h, h}, lds_read_v2(xp[r] - j), acc[r]);
-        }
-#pragma unroll
-        for (int r = 0; r < RS_R; ++r) outv[r] = make_float2(acc[r].x, acc[r].y);
-        out_m0 = m0;
-        nt = nt_next; pt = pt_next;
-        phase_sync();                                               // every lane's window reads precede the next staging
-    }
-    flush();
-}
-
 // ------------------------------------------------------------------------------------------
 // K0c: tuner (SPEC 3.0c): K channels at rational frequency offsets num_k / den_k (cycles per input sample) out of ONE capture,
-// each mixed down and resampled by L / M -- the resampler with a mixer in front.  The kernel is K0b's construction throughout
-// (window loader, linear window, lane-owns-outputs mapping, rs_fir, stores one iteration late); what is new:
+// each mixed down and resampled by L / M -- the resampler with a mixer in front.  K0b and K0c are ONE body, resample_body
+// <FMT, LUTM, MIX>: window loader, linear window, lane-owns-outputs mapping, rs_fir and the stores one iteration late are the
+// resampler's; what MIX adds sits in the body's entry and in its staging pass, under `if constexpr`:
 //   * the channel is the FASTEST-varying part of the workgroup index (blockIdx.x = sub-tile group * K + channel), so the K
 //     workgroups that read one window of the capture are dispatched together: one of them fetches it from HBM, the others find it
 //     in L2 / MALL;
@@ -1741,8 +1573,21 @@ __global__ __launch_bounds__(WV, RS_WPS) void k_resample(RsArgs a, WideConv cv)
 //     gathered from global memory (L2-resident: at most 64 KB) otherwise -- the same numbers either way;
 //   * the per-channel numbers sit in device memory (TuneCh), read with scalar loads.
 // ------------------------------------------------------------------------------------------
-// K0b's tap loop of one sub-tile as a function, for K0c: acc[r] += sum_j hp[j] xp[r][-j], j ascending.  (k_resample keeps its own
-// inlined copy: calling this from it moves its register allocation, which tests/test_isa_resample.py pins.)
+constexpr int TN_ROT_LDS_DEN = 512;          // largest denominator whose rotator goes to LDS (8 bytes per entry: 4 KB)
+
+struct TuneCh {
+    const float2* rot;      // (C_D[i], S_D[i]), i < D, device
+    int D, nm;              // denominator; num mod D in [0, D) (0: the capture's centre, no product)
+};
+struct TuneArgs {
+    RsArgs r;               // the resampler's, for ONE input row (ch_stride unused); y_stride = distance of the K output rows
+    const TuneCh* ch;       // [K]
+    int K;
+    int rot_off;            // floats from the start of dynamic LDS to the rotator's copy (even)
+    unsigned long abs_first;// position of owned sample 0 (< 2^62)
+};
+
+// The tap loop of one sub-tile: acc[r] += sum_j hp[j] xp[r][-j], j ascending.
 __device__ __forceinline__ void rs_fir(const float2* const (&xp)[RS_R], const float* hp, int T, v2f (&acc)[RS_R])
 {
     // Window reads in blocks of 8 (then 4) taps x RS_R outputs, issued from inline asm ahead of their use as in K1's walks: the
@@ -1805,22 +1650,9 @@ __device__ __forceinline__ void rs_fir(const float2* const (&xp)[RS_R], const fl
     }
 }
 
-constexpr int TN_ROT_LDS_DEN = 512;          // largest denominator whose rotator goes to LDS (8 bytes per entry: 4 KB)
-
-struct TuneCh {
-    const float2* rot;      // (C_D[i], S_D[i]), i < D, device
-    int D, nm;              // denominator; num mod D in [0, D) (0: the capture's centre, no product)
-};
-struct TuneArgs {
-    RsArgs r;               // the resampler's, for ONE input row (ch_stride unused); y_stride = distance of the K output rows
-    const TuneCh* ch;       // [K]
-    int K;
-    int rot_off;            // floats from the start of dynamic LDS to the rotator's copy (even)
-    unsigned long abs_first;// position of owned sample 0 (< 2^62)
-};
-
-template <int FMT, bool LUTM>
-__global__ __launch_bounds__(WV, RS_WPS) void k_tune(TuneArgs ta, WideConv cv)
+// ta: the tuner's arguments (a is ta->r) when MIX, unused otherwise
+template <int FMT, bool LUTM, bool MIX>
+__device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* ta, const WideConv& cv)
 {
     static_assert(FMT == P25FE_FMT_U8 || !LUTM, "only u8 has a table");
     constexpr int LS = wide_log_spv(FMT), SPV = 1 << LS, NV = wide_nv(FMT, RS_NIN);
@@ -1828,12 +1660,22 @@ __global__ __launch_bounds__(WV, RS_WPS) void k_tune(TuneArgs ta, WideConv cv)
     static_assert((P25FE_TUNE_MAX_DEN - 1) * (P25FE_TUNE_MAX_DEN - 1) < (1 << 26) && SPV * WV <= P25FE_TUNE_MAX_DEN, "32-bit index arithmetic");
     __shared__ float2 X[RS_NIN];
     extern __shared__ float RS_HT[];
-    const RsArgs& a = ta.r;
     const int tid = threadIdx.x;
-    const unsigned kc = blockIdx.x % (unsigned)ta.K;                // the channel varies fastest
-    const long wg = (long)blockIdx.y * (gridDim.x / (unsigned)ta.K) + blockIdx.x / (unsigned)ta.K;
-    const TuneCh c = ta.ch[kc];
-    const unsigned D = (unsigned)c.D, nm = (unsigned)c.nm;
+    // the entry: workgroup index -> (sub-tile group wg, output row), and the rows' bases
+    long wg = blockIdx.x;
+    unsigned row = blockIdx.y;                                      // the resampler's channel: input row and output row
+    const uint4* xb;
+    TuneCh c{};
+    if constexpr (MIX) {
+        row = blockIdx.x % (unsigned)ta->K;                         // the tuner's channel varies fastest; every channel reads the one input row
+        wg = (long)blockIdx.y * (gridDim.x / (unsigned)ta->K) + blockIdx.x / (unsigned)ta->K;
+        c = ta->ch[row];
+        xb = reinterpret_cast<const uint4*>(a.x);
+    } else {
+        xb = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(a.x) + (size_t)fmt_bps(FMT) * row * a.ch_stride);
+    }
+    float2* yb = reinterpret_cast<float2*>(a.y) + (size_t)row * a.y_stride;
+    const unsigned D = (unsigned)c.D, nm = (unsigned)c.nm;          // (MIX only, as everything that names them)
     const float* lut = nullptr;
     if constexpr (LUTM) {
         __shared__ float LUT[256];
@@ -1841,24 +1683,31 @@ __global__ __launch_bounds__(WV, RS_WPS) void k_tune(TuneArgs ta, WideConv cv)
         lut = LUT;
     }
     for (int k = tid; k < a.L * a.TP; k += WV) RS_HT[k] = a.taps[k];
-    float2* const ROT = reinterpret_cast<float2*>(RS_HT + ta.rot_off);
-    const int mode = nm == 0 ? 0 : (D <= (unsigned)TN_ROT_LDS_DEN ? 1 : 2);      // uniform: no product / table in LDS / table gathered
-    if (mode == 1)
-        for (unsigned k = tid; k < D; k += WV) ROT[k] = c.rot[k];
-    const uint4* xb = reinterpret_cast<const uint4*>(a.x);
-    float2* yb = reinterpret_cast<float2*>(a.y) + (size_t)kc * a.y_stride;
+    const float2* ROT = nullptr;
+    int mode = 0;                                                   // uniform: no product / table in LDS / table gathered
+    if constexpr (MIX) {
+        float2* const rot = reinterpret_cast<float2*>(RS_HT + ta->rot_off);
+        mode = nm == 0 ? 0 : (D <= (unsigned)TN_ROT_LDS_DEN ? 1 : 2);
+        if (mode == 1)
+            for (unsigned k = tid; k < D; k += WV) rot[k] = c.rot[k];
+        ROT = rot;
+    }
     const int T = a.T, L = a.L, M = a.M;
 
     const long m_wg0 = wg * ((long)a.tile * RS_SUBS);
-    if (m_wg0 >= a.n_out) return;                                   // (a last row of grid.y may be partial)
+    if constexpr (MIX)
+        if (m_wg0 >= a.n_out) return;                               // (a last row of grid.y may be partial)
     const long u_wg = (long)a.p0 + m_wg0 * M;
     long nt = (long)a.d0 + u_wg / L;                                // input index of the sub-tile's first output
     int pt = (int)(u_wg % L);                                       // ... and its phase
-    // (position of the window's first sample) mod D: the one 64-bit reduction; it follows the window in 32 bits
-    long rb64 = ((long)ta.abs_first + (nt - (T - 1))) % (long)D;
-    unsigned rb = (unsigned)(rb64 < 0 ? rb64 + (long)D : rb64);
-    const unsigned il = (nm * (unsigned)(SPV * tid)) % D;           // this lane's index offset inside a vector row
-    const unsigned sv = (nm * (unsigned)(SPV * WV)) % D;            // ... and from one of its vectors to the next
+    unsigned rb = 0, il = 0, sv = 0;
+    if constexpr (MIX) {
+        // (position of the window's first sample) mod D: the one 64-bit reduction; it follows the window in 32 bits
+        const long rb64 = ((long)ta->abs_first + (nt - (T - 1))) % (long)D;
+        rb = (unsigned)(rb64 < 0 ? rb64 + (long)D : rb64);
+        il = (nm * (unsigned)(SPV * tid)) % D;                      // this lane's index offset inside a vector row
+        sv = (nm * (unsigned)(SPV * WV)) % D;                       // ... and from one of its vectors to the next
+    }
 
     uint4 v[NV];
     // window of a sub-tile: positions k = 0 .. RS_NIN-1 are inputs base + k, base = nt - (T - 1)
@@ -1877,16 +1726,21 @@ __global__ __launch_bounds__(WV, RS_WPS) void k_tune(TuneArgs ta, WideConv cv)
             v[j] = q[r];
         }
     };
+    // MODE: 0 no product (the resampler, and a channel at the capture's centre) / 1 rotator in LDS / 2 rotator gathered
     auto stage = [&](long base, auto mc) {
         constexpr int MODE = decltype(mc)::value;
+        static_assert(MIX || MODE == 0, "only the tuner mixes");
         const long v0 = base >> LS;
         const int sh = (int)(base - (v0 << LS));                    // 0 .. SPV - 1
         const bool interior = (v0 << LS) >= -a.n_hist && (v0 << LS) + (long)SPV * NV * WV <= a.n_new;   // uniform
-        // rotator index of this lane's first element: sample (v0 << LS) + SPV tid sits at position rb - sh (mod D; D may be below sh)
-        const unsigned shd = (unsigned)sh % D;
-        const unsigned r0 = rb >= shd ? rb - shd : rb + D - shd;
-        unsigned iv = (nm * r0) % D + il;
-        iv = iv >= D ? iv - D : iv;
+        unsigned iv = 0;
+        if constexpr (MODE != 0) {
+            // rotator index of this lane's first element: sample (v0 << LS) + SPV tid sits at position rb - sh (mod D; D may be below sh)
+            const unsigned shd = (unsigned)sh % D;
+            const unsigned r0 = rb >= shd ? rb - shd : rb + D - shd;
+            iv = (nm * r0) % D + il;
+            iv = iv >= D ? iv - D : iv;
+        }
 #pragma unroll
         for (int j = 0; j < NV; ++j) {
             unsigned ie = iv;
@@ -1906,8 +1760,10 @@ __global__ __launch_bounds__(WV, RS_WPS) void k_tune(TuneArgs ta, WideConv cv)
                 }
                 if (k >= 0 && k < RS_NIN) X[k] = s2;
             }
-            iv += sv;
-            iv = iv >= D ? iv - D : iv;
+            if constexpr (MODE != 0) {
+                iv += sv;
+                iv = iv >= D ? iv - D : iv;
+            }
         }
     };
 
@@ -1932,7 +1788,8 @@ __global__ __launch_bounds__(WV, RS_WPS) void k_tune(TuneArgs ta, WideConv cv)
     for (int it = 0; it < RS_SUBS; ++it) {
         const long m0 = m_wg0 + (long)it * a.tile;
         if (m0 >= a.n_out) break;                                   // uniform
-        if (mode == 0) stage(nt - (T - 1), icst<0>{});
+        if constexpr (!MIX) stage(nt - (T - 1), icst<0>{});
+        else if (mode == 0) stage(nt - (T - 1), icst<0>{});
         else if (mode == 1) stage(nt - (T - 1), icst<1>{});
         else stage(nt - (T - 1), icst<2>{});
         phase_sync();
@@ -1959,11 +1816,15 @@ __global__ __launch_bounds__(WV, RS_WPS) void k_tune(TuneArgs ta, WideConv cv)
         for (int r = 0; r < RS_R; ++r) outv[r] = make_float2(acc[r].x, acc[r].y);
         out_m0 = m0;
         nt = nt_next; pt = pt_next;
-        rb = (rb + dn % D) % D;
+        if constexpr (MIX) rb = (rb + dn % D) % D;
         phase_sync();                                               // every lane's window reads precede the next staging
     }
     flush();
 }
+template <int FMT, bool LUTM>
+__global__ __launch_bounds__(WV, RS_WPS) void k_resample(RsArgs a, WideConv cv) { resample_body<FMT, LUTM, false>(a, nullptr, cv); }
+template <int FMT, bool LUTM>
+__global__ __launch_bounds__(WV, RS_WPS) void k_tune(TuneArgs ta, WideConv cv) { resample_body<FMT, LUTM, true>(ta.r, &ta, cv); }
 #endif
 
 // ------------------------------------------------------------------------------------------
