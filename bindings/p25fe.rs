@@ -153,7 +153,7 @@ pub const RS_MAX_L: i32 = 32;
 pub const RS_MAX_M: i32 = 1024;
 pub const RS_MAX_T: i32 = 1024;
 pub const RS_MAX_TABLE: i32 = 4096;
-/// p25fe_tuner_t: the tuner of docs/SPEC.md 3.0c (made from a Handle, which must outlive it)
+/// p25fe_tuner_t: the tuner of docs/SPEC.md 3.0c (rational channels) or 3.0d (NCO channels), made from a Handle, which must outlive it
 pub enum Tuner {}
 /// P25FE_TUNE_MAX_CH / _DEN: 1 <= channels <= 256; num / den in lowest terms, 1 <= den <= 8192, 2 |num| <= den
 pub const TUNE_MAX_CH: i32 = 256;
@@ -221,6 +221,11 @@ extern "C" {
     pub fn p25fe_tune_dev(tn: *mut Tuner, d_iq: *const c_void, fmt: c_int, n_hist: usize, n: usize, abs_first: u64, d_out: *mut f32,
                           out_stride: usize, stream: *mut c_void) -> c_int;
     pub fn p25fe_tune(tn: *mut Tuner, iq: *const c_void, fmt: c_int, n: usize, out: *mut f32, cap: usize, n_out: *mut usize) -> c_int;
+    // tuner, NCO channels (docs/SPEC.md 3.0d): step / 2^32 cycles per input sample, any frequency offset; the object is a Tuner
+    pub fn p25fe_nco_step(fs_in_hz: u32, offset_hz: f64, step: *mut i32) -> c_int;
+    pub fn p25fe_nco_factor(step: i32, n: u64, cs: *mut f32) -> c_int;
+    pub fn p25fe_nco_create(h: *mut Handle, l: i32, m: i32, t: i32, taps: *const f32, n_out_channels: i32, step: *const i32,
+                                  out: *mut *mut Tuner) -> c_int;
     pub fn p25fe_n_baseband(abs0: u64, n: usize) -> usize;
     pub fn p25fe_slice_dev(h: *mut Handle, d_bb: *const f32, bb_stride: usize, n_hist_bb: usize, n_bb: usize, abs_bb0: u64,
                            d_anchor_in: *const Anchor, d_dibits: *mut u8, dibit_stride: usize, d_sync_pos: *mut i64,

@@ -456,6 +456,29 @@ int p25fe_tune_dev(p25fe_tuner_t *tn, const void *d_iq, int fmt, size_t n_hist, 
  * when the format differs from the stream's first call (p25fe_tuner_reset starts a new stream).  Synchronous. */
 int p25fe_tune(p25fe_tuner_t *tn, const void *iq, int fmt, size_t n, float *out, size_t cap, size_t *n_out);
 
+/* ---- tuner, NCO channels: any frequency offset, for off-raster and ppm tuning (docs/SPEC.md 3.0d) --------------------------------
+ * Another kind of the same object.  Channel k has the frequency step_k / 2^32 cycles per INPUT sample, step a signed 32-bit
+ * integer (positive: above the capture's centre; resolution fs / 2^32).  The phase is an integer function of the absolute index,
+ *     ph = ((uint32)step * (uint32)(n mod 2^32)) mod 2^32,    a = ((ph + 2^23) mod 2^32) >> 24,    r = (int32)(ph - (a << 24)),
+ *     t = (float)r * (float)(2 pi / 2^32),  t2 = t * t,  cf = fma(t2, -0.5f, 1.0f),  sf = fma(t2 * t, (float)(-1 / 6), t),
+ *     c = fma(-S[a], sf, C[a] * cf),  s = fma(C[a], sf, S[a] * cf)             with C, S = p25fe_tuner_rotator(256, ...),
+ * and v_k[n], y_k[m] follow from (c, s) as above (step = 0: v = x).  A channel with step = 0 IS p25fe_resample_dev and a channel
+ * with step = num * 2^24, num odd, |num| <= 127, IS the rational channel num / 256, both bit for bit.  The position grid of
+ * channel k is lcm(M, 2^32 / gcd(step_k, 2^32)); positions congruent modulo lcm(M, 2^32) give the same bits for every step.
+ * Limits: the resampler's and 1 <= n_out_channels <= P25FE_TUNE_MAX_CH; every step value is valid. */
+
+/* step = nearbyint(offset_hz / fs_in_hz * 2^32) in double, ties to even, wrapped to 32 bits (+2^31 becomes -2^31: Nyquist either
+ * way); no device needed.  P25FE_ERR_ARG: a null pointer, fs_in_hz = 0, an offset that is not finite, 2 |offset_hz| > fs_in_hz. */
+int p25fe_nco_step(uint32_t fs_in_hz, double offset_hz, int32_t *step);
+/* (c, s) of the formula above for a step and an absolute index, computed on the host with exactly the kernel's operations; no
+ * device needed.  P25FE_ERR_ARG: a null pointer. */
+int p25fe_nco_factor(int32_t step, uint64_t n, float cs[2]);
+/* p25fe_tuner_create for NCO channels: the same checks in the same order and the same lifetime rules.  The object is used and
+ * destroyed with p25fe_tune_dev, p25fe_tune, p25fe_tuner_reset and p25fe_tuner_destroy.  It holds the table, the ONE rotator table
+ * of denominator 256 and the channels' steps in device memory. */
+int p25fe_nco_create(p25fe_t *h, int32_t L, int32_t M, int32_t T, const float *taps,
+                           int32_t n_out_channels, const int32_t *step, p25fe_tuner_t **out);
+
 /* stages 6-7 on device baseband.  d_bb points at the first owned sample; n_hist_bb valid
  * samples precede it; abs_bb0 is its absolute index; d_anchor_in (nullable = no lock) is the
  * carry-in per channel.  d_result[c] is filled per channel.

@@ -82,6 +82,7 @@ SYMBOLS = [
     "p25fe_resample_dev", "p25fe_resample",
     "p25fe_tuner_freq", "p25fe_tuner_rotator", "p25fe_tuner_create", "p25fe_tuner_destroy", "p25fe_tuner_reset", "p25fe_tune_dev",
     "p25fe_tune",
+    "p25fe_nco_step", "p25fe_nco_factor", "p25fe_nco_create",
 ]
 
 
@@ -194,6 +195,9 @@ def load():
     L.p25fe_tuner_reset.argtypes = [vp]
     L.p25fe_tune_dev.argtypes = [vp, vp, C.c_int, sz, sz, u64, vp, sz, vp]
     L.p25fe_tune.argtypes = [vp, vp, C.c_int, sz, vp, sz, psz]
+    L.p25fe_nco_step.argtypes = [C.c_uint32, C.c_double, pi32]
+    L.p25fe_nco_factor.argtypes = [C.c_int32, u64, vp]
+    L.p25fe_nco_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, vp, C.POINTER(vp)]
     L.p25fe_n_predecim.argtypes = [u64, sz]
     L.p25fe_n_predecim.restype = sz
     L.p25fe_n_baseband.argtypes = [u64, sz]

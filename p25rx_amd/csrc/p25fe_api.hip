@@ -1339,7 +1339,8 @@ static int launch_k6(p25fe_t* h, const void* d_iq, int fmt, size_t n_hist, size_
 // in front, on the device and here: RsCore is what both objects hold -- the ratio, the table's device copy in the kernel's layout,
 // and the state of the host streaming form (position, format, the last T - 1 samples per input row as they came in).  The resampler
 // is C input rows to C output rows; the tuner is ONE input row to K output rows, plus the channels' frequencies: one rotator table per
-// distinct denominator and the per-channel numbers (TuneCh) in device memory.
+// distinct denominator and the per-channel numbers (TuneCh) in device memory.  A tuner of NCO channels (SPEC 3.0d; kernel:
+// k_tune_nco) is the same object with another kind: ONE rotator table, of denominator 256, and a step per channel in TuneCh.
 // --------------------------------------------------------------------------------------------
 struct RsCore {
     p25fe_t* h = nullptr;
@@ -1355,6 +1356,7 @@ struct RsCore {
 struct p25fe_resampler : RsCore {};
 struct p25fe_tuner : RsCore {
     int K = 0;
+    bool nco = false;                      // the kind: rational channels (k_tune) or NCO channels (k_tune_nco)
     int rot_off = 0;                       // floats of dynamic LDS in front of the rotator's copy
     size_t lds = 0;                        // dynamic LDS of a launch: the table, and the largest rotator that is copied there
     DevBuf d_rot, d_ch;
@@ -1449,7 +1451,13 @@ static void rs_launch_as(dim3 grid, size_t lds, hipStream_t st, const TuneArgs& 
 {
     hipLaunchKernelGGL((k_tune<FMT, LUTM>), grid, dim3(WV), lds, st, a, cv);
 }
-// the instance of either kernel for a format: cf32, s16, u8 with the table as arithmetic or looked up
+struct NcoArgs : TuneArgs {};              // the tuner's arguments on their way to k_tune_nco
+template <int FMT, bool LUTM>
+static void rs_launch_as(dim3 grid, size_t lds, hipStream_t st, const NcoArgs& a, const WideConv& cv)
+{
+    hipLaunchKernelGGL((k_tune_nco<FMT, LUTM>), grid, dim3(WV), lds, st, static_cast<const TuneArgs&>(a), cv);
+}
+// the instance of a kernel for a format: cf32, s16, u8 with the table as arithmetic or looked up
 template <class Args>
 static void rs_dispatch(int fmt, dim3 grid, size_t lds, hipStream_t st, const Args& a, const WideConv& cv)
 {
@@ -1459,7 +1467,7 @@ static void rs_dispatch(int fmt, dim3 grid, size_t lds, hipStream_t st, const Ar
     else rs_launch_as<P25FE_FMT_U8, false>(grid, lds, st, a, cv);
 }
 
-// One range through k_resample (tn null: o->rows_in rows in and out) or k_tune (tn is o: one row in, tn->K rows out).
+// One range through k_resample (tn null: o->rows_in rows in and out) or k_tune / k_tune_nco (tn is o: one row in, tn->K rows out).
 static int rs_launch(RsCore* o, const p25fe_tuner* tn, const void* d_iq, int fmt, size_t ch_stride, size_t n_hist, size_t n,
                      uint64_t abs_first, float* d_out, size_t out_stride, hipStream_t st)
 {
@@ -1469,7 +1477,7 @@ static int rs_launch(RsCore* o, const p25fe_tuner* tn, const void* d_iq, int fmt
     if (out_stride < n_out) return P25FE_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (n_out == 0) return P25FE_OK;
-    TuneArgs ta;
+    NcoArgs ta;
     rs_fill_args(o, ta.r, d_iq, ch_stride, n_hist, n, abs_first, d_out, out_stride, n_out);
     const size_t per_wg = (size_t)ta.r.tile * RS_SUBS, groups = (n_out + per_wg - 1) / per_wg;
     dim3 grid((unsigned)groups, (unsigned)o->rows_in);
@@ -1482,7 +1490,8 @@ static int rs_launch(RsCore* o, const p25fe_tuner* tn, const void* d_iq, int fmt
     }
     const WideConv cv = wide_conv_of(h);
     (void)hipGetLastError();                                        // the check below is for THIS launch: drop what an earlier call of the thread left behind
-    if (tn) rs_dispatch(fmt, grid, tn->lds, st, ta, cv);
+    if (tn && tn->nco) rs_dispatch(fmt, grid, tn->lds, st, ta, cv);
+    else if (tn) rs_dispatch(fmt, grid, tn->lds, st, static_cast<const TuneArgs&>(ta), cv);
     else rs_dispatch(fmt, grid, sizeof(float) * (size_t)o->L * (size_t)o->TP, st, ta.r, cv);
     HIPCHK(h, hipGetLastError());
     return P25FE_OK;
@@ -1665,6 +1674,65 @@ int p25fe_tuner_create(p25fe_t* h, int32_t L, int32_t M, int32_t T, const float*
             ch[k].D = den[k];
             ch[k].nm = (int)(((int64_t)num[k] % den[k] + den[k]) % den[k]);
         }
+        if (hipMemcpy(tn->d_rot.p, rot.data(), rot.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
+            hipMemcpy(tn->d_ch.p, ch.data(), ch.size() * sizeof(TuneCh), hipMemcpyHostToDevice) == hipSuccess) {
+            *out = tn;
+            return P25FE_OK;
+        }
+    }
+    h->last_hip = (int)hipGetLastError();
+    delete tn;
+    return P25FE_ERR_HIP;
+}
+
+int p25fe_nco_step(uint32_t fs_in_hz, double offset_hz, int32_t* step)
+{
+    if (!step || fs_in_hz == 0 || !(offset_hz - offset_hz == 0.0) || 2.0 * fabs(offset_hz) > (double)fs_in_hz) return P25FE_ERR_ARG;
+    // |offset / fs| <= 1/2, so the product is within [-2^31, 2^31] and exact as a power-of-two scaling; ties go to even
+    const double q = nearbyint(ldexp(offset_hz / (double)fs_in_hz, 32));
+    *step = (int32_t)(uint32_t)(int64_t)q;                          // +2^31 wraps to -2^31: both are the Nyquist frequency
+    return P25FE_OK;
+}
+
+int p25fe_nco_factor(int32_t step, uint64_t n, float cs[2])
+{
+    if (!cs) return P25FE_ERR_ARG;
+    static const std::vector<float> rot = [] {
+        std::vector<float> r(2 * (size_t)TN_NCO_DEN);
+        (void)p25fe_tuner_rotator(TN_NCO_DEN, r.data(), r.size());
+        return r;
+    }();
+    // SPEC 3.0d, the operations the kernel's nco_factor does, in its order (this file is compiled without contraction)
+    const uint32_t ph = (uint32_t)step * (uint32_t)n;
+    const uint32_t ia = (ph + (1u << 23)) >> 24;
+    const int32_t r = (int32_t)(ph - (ia << 24));
+    const float t = (float)r * (float)(6.283185307179586476925 / 4294967296.0);
+    const float t2 = t * t;
+    const float cf = fmaf(t2, -0.5f, 1.0f);
+    const float sf = fmaf(t2 * t, (float)(-1.0 / 6.0), t);
+    const float C = rot[ia], S = rot[TN_NCO_DEN + ia];
+    cs[0] = fmaf(-S, sf, C * cf);
+    cs[1] = fmaf(C, sf, S * cf);
+    return P25FE_OK;
+}
+
+int p25fe_nco_create(p25fe_t* h, int32_t L, int32_t M, int32_t T, const float* taps, int32_t n_out_channels, const int32_t* step,
+                           p25fe_tuner_t** out)
+{
+    if (out) *out = nullptr;
+    if (!out || n_out_channels < 1 || n_out_channels > P25FE_TUNE_MAX_CH || !step) return P25FE_ERR_ARG;
+    p25fe_tuner* tn = nullptr;
+    if (int rc = rs_create(&tn, h, L, M, T, taps, 1)) return rc;    // (the handle is looked at last)
+    const int K = tn->K = n_out_channels;
+    tn->nco = true;
+    std::vector<float> cs(2 * (size_t)TN_NCO_DEN), rot;
+    (void)p25fe_tuner_rotator(TN_NCO_DEN, cs.data(), cs.size());
+    for (int i = 0; i < TN_NCO_DEN; ++i) { rot.push_back(cs[i]); rot.push_back(cs[TN_NCO_DEN + i]); }
+    tn->rot_off = (int)round_up((size_t)L * tn->TP, 2);
+    tn->lds = sizeof(float) * ((size_t)tn->rot_off + 2 * (size_t)TN_NCO_DEN);
+    std::vector<TuneCh> ch((size_t)K);
+    if (tn->d_rot.ensure(rot.size() * sizeof(float)) == hipSuccess && tn->d_ch.ensure((size_t)K * sizeof(TuneCh)) == hipSuccess) {
+        for (int k = 0; k < K; ++k) { ch[k].rot = tn->d_rot.as<float2>(); ch[k].D = TN_NCO_DEN; ch[k].nm = step[k]; }
         if (hipMemcpy(tn->d_rot.p, rot.data(), rot.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
             hipMemcpy(tn->d_ch.p, ch.data(), ch.size() * sizeof(TuneCh), hipMemcpyHostToDevice) == hipSuccess) {
             *out = tn;

@@ -1572,12 +1572,20 @@ struct RsArgs {
 //   * the rotator table (interleaved (cos, sin) pairs) is copied to dynamic LDS behind the taps when den <= TN_ROT_LDS_DEN and
 //     gathered from global memory (L2-resident: at most 64 KB) otherwise -- the same numbers either way;
 //   * the per-channel numbers sit in device memory (TuneCh), read with scalar loads.
+// NCO channels (SPEC 3.0d, k_tune_nco) are the third value of MIX: a channel's frequency is step / 2^32 cycles per sample, its phase
+// the wrapping 32-bit product step * n.  The top eight bits of the phase (rounded) pick an entry of the ONE rotator table of
+// denominator 256, which every channel copies to LDS; the signed residual below them turns that entry by a third-order sine and a
+// second-order cosine.  The phase is linear in n with no modulus but the register's own: a workgroup multiplies once, a lane adds
+// step per element and step SPV 64 per vector.  A channel with step = 0 skips the product.
 // ------------------------------------------------------------------------------------------
 constexpr int TN_ROT_LDS_DEN = 512;          // largest denominator whose rotator goes to LDS (8 bytes per entry: 4 KB)
+constexpr int TN_NCO_DEN = 256;              // the NCO's coarse table: 2^32 / 256 = 2^24 phase units per entry
+constexpr int MIX_NONE = 0, MIX_RATIONAL = 1, MIX_NCO = 2;
 
 struct TuneCh {
     const float2* rot;      // (C_D[i], S_D[i]), i < D, device
     int D, nm;              // denominator; num mod D in [0, D) (0: the capture's centre, no product)
+                            // an NCO channel: D = TN_NCO_DEN, nm = step (any value; 0: no product)
 };
 struct TuneArgs {
     RsArgs r;               // the resampler's, for ONE input row (ch_stride unused); y_stride = distance of the K output rows
@@ -1586,6 +1594,19 @@ struct TuneArgs {
     int rot_off;            // floats from the start of dynamic LDS to the rotator's copy (even)
     unsigned long abs_first;// position of owned sample 0 (< 2^62)
 };
+
+// The NCO's factor (c, s) = e^{+j 2 pi ph / 2^32} to fp32 (SPEC 3.0d): ROT is the rotator of TN_NCO_DEN as (cos, sin) pairs
+__device__ __forceinline__ float2 nco_factor(unsigned ph, const float2* ROT)
+{
+    const unsigned ia = (ph + (1u << 23)) >> 24;
+    const int r = (int)(ph - (ia << 24));                           // -2^23 <= r < 2^23
+    const float t = (float)r * (float)(6.283185307179586476925 / 4294967296.0);
+    const float t2 = t * t;
+    const float cf = __builtin_fmaf(t2, -0.5f, 1.0f);
+    const float sf = __builtin_fmaf(t2 * t, (float)(-1.0 / 6.0), t);
+    const float2 cs = ROT[ia];
+    return make_float2(__builtin_fmaf(-cs.y, sf, cs.x * cf), __builtin_fmaf(cs.x, sf, cs.y * cf));
+}
 
 // The tap loop of one sub-tile: acc[r] += sum_j hp[j] xp[r][-j], j ascending.
 __device__ __forceinline__ void rs_fir(const float2* const (&xp)[RS_R], const float* hp, int T, v2f (&acc)[RS_R])
@@ -1651,7 +1672,7 @@ __device__ __forceinline__ void rs_fir(const float2* const (&xp)[RS_R], const fl
 }
 
 // ta: the tuner's arguments (a is ta->r) when MIX, unused otherwise
-template <int FMT, bool LUTM, bool MIX>
+template <int FMT, bool LUTM, int MIX>
 __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* ta, const WideConv& cv)
 {
     static_assert(FMT == P25FE_FMT_U8 || !LUTM, "only u8 has a table");
@@ -1666,7 +1687,7 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
     unsigned row = blockIdx.y;                                      // the resampler's channel: input row and output row
     const uint4* xb;
     TuneCh c{};
-    if constexpr (MIX) {
+    if constexpr (MIX != MIX_NONE) {
         row = blockIdx.x % (unsigned)ta->K;                         // the tuner's channel varies fastest; every channel reads the one input row
         wg = (long)blockIdx.y * (gridDim.x / (unsigned)ta->K) + blockIdx.x / (unsigned)ta->K;
         c = ta->ch[row];
@@ -1684,29 +1705,42 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
     }
     for (int k = tid; k < a.L * a.TP; k += WV) RS_HT[k] = a.taps[k];
     const float2* ROT = nullptr;
-    int mode = 0;                                                   // uniform: no product / table in LDS / table gathered
-    if constexpr (MIX) {
+    int mode = 0;                                                   // uniform: no product / table in LDS / table gathered / NCO
+    if constexpr (MIX == MIX_RATIONAL) {
         float2* const rot = reinterpret_cast<float2*>(RS_HT + ta->rot_off);
         mode = nm == 0 ? 0 : (D <= (unsigned)TN_ROT_LDS_DEN ? 1 : 2);
         if (mode == 1)
             for (unsigned k = tid; k < D; k += WV) rot[k] = c.rot[k];
         ROT = rot;
     }
+    if constexpr (MIX == MIX_NCO) {
+        float2* const rot = reinterpret_cast<float2*>(RS_HT + ta->rot_off);
+        mode = nm == 0 ? 0 : 3;
+        if (mode == 3)
+            for (int k = tid; k < TN_NCO_DEN; k += WV) rot[k] = c.rot[k];
+        ROT = rot;
+    }
     const int T = a.T, L = a.L, M = a.M;
 
     const long m_wg0 = wg * ((long)a.tile * RS_SUBS);
-    if constexpr (MIX)
+    if constexpr (MIX != MIX_NONE)
         if (m_wg0 >= a.n_out) return;                               // (a last row of grid.y may be partial)
     const long u_wg = (long)a.p0 + m_wg0 * M;
     long nt = (long)a.d0 + u_wg / L;                                // input index of the sub-tile's first output
     int pt = (int)(u_wg % L);                                       // ... and its phase
     unsigned rb = 0, il = 0, sv = 0;
-    if constexpr (MIX) {
+    if constexpr (MIX == MIX_RATIONAL) {
         // (position of the window's first sample) mod D: the one 64-bit reduction; it follows the window in 32 bits
         const long rb64 = ((long)ta->abs_first + (nt - (T - 1))) % (long)D;
         rb = (unsigned)(rb64 < 0 ? rb64 + (long)D : rb64);
         il = (nm * (unsigned)(SPV * tid)) % D;                      // this lane's index offset inside a vector row
         sv = (nm * (unsigned)(SPV * WV)) % D;                       // ... and from one of its vectors to the next
+    }
+    if constexpr (MIX == MIX_NCO) {
+        // rb is the PHASE of the window's first sample, step * position mod 2^32: the one product; it follows the window by adds
+        rb = nm * (unsigned)((long)ta->abs_first + (nt - (T - 1)));
+        il = nm * (unsigned)(SPV * tid);
+        sv = nm * (unsigned)(SPV * WV);
     }
 
     uint4 v[NV];
@@ -1726,15 +1760,16 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
             v[j] = q[r];
         }
     };
-    // MODE: 0 no product (the resampler, and a channel at the capture's centre) / 1 rotator in LDS / 2 rotator gathered
+    // MODE: 0 no product (the resampler, and a channel at the capture's centre) / 1 rotator in LDS / 2 rotator gathered / 3 NCO
     auto stage = [&](long base, auto mc) {
         constexpr int MODE = decltype(mc)::value;
-        static_assert(MIX || MODE == 0, "only the tuner mixes");
+        static_assert(MODE == 0 || (MIX == MIX_RATIONAL && MODE <= 2) || (MIX == MIX_NCO && MODE == 3), "only the tuner mixes");
         const long v0 = base >> LS;
         const int sh = (int)(base - (v0 << LS));                    // 0 .. SPV - 1
         const bool interior = (v0 << LS) >= -a.n_hist && (v0 << LS) + (long)SPV * NV * WV <= a.n_new;   // uniform
         unsigned iv = 0;
-        if constexpr (MODE != 0) {
+        if constexpr (MODE == 3) iv = rb - nm * (unsigned)sh + il;  // phase of this lane's first element (it sits sh before the window)
+        else if constexpr (MODE != 0) {
             // rotator index of this lane's first element: sample (v0 << LS) + SPV tid sits at position rb - sh (mod D; D may be below sh)
             const unsigned shd = (unsigned)sh % D;
             const unsigned r0 = rb >= shd ? rb - shd : rb + D - shd;
@@ -1748,7 +1783,11 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
             for (int e = 0; e < SPV; ++e) {
                 const int k = SPV * (tid + j * WV) + e - sh;        // window position
                 float2 s2 = wide_sample<FMT, LUTM>(v[j], e, cv, lut);
-                if constexpr (MODE != 0) {
+                if constexpr (MODE == 3) {
+                    const float2 cs = nco_factor(ie, ROT);
+                    s2 = make_float2(__builtin_fmaf(s2.y, cs.y, s2.x * cs.x), __builtin_fmaf(-s2.x, cs.y, s2.y * cs.x));
+                    ie += nm;
+                } else if constexpr (MODE != 0) {
                     const float2 cs = MODE == 1 ? ROT[ie] : c.rot[ie];
                     s2 = make_float2(__builtin_fmaf(s2.y, cs.y, s2.x * cs.x), __builtin_fmaf(-s2.x, cs.y, s2.y * cs.x));
                     ie += nm;
@@ -1760,7 +1799,8 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
                 }
                 if (k >= 0 && k < RS_NIN) X[k] = s2;
             }
-            if constexpr (MODE != 0) {
+            if constexpr (MODE == 3) iv += sv;
+            else if constexpr (MODE != 0) {
                 iv += sv;
                 iv = iv >= D ? iv - D : iv;
             }
@@ -1788,8 +1828,9 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
     for (int it = 0; it < RS_SUBS; ++it) {
         const long m0 = m_wg0 + (long)it * a.tile;
         if (m0 >= a.n_out) break;                                   // uniform
-        if constexpr (!MIX) stage(nt - (T - 1), icst<0>{});
+        if constexpr (MIX == MIX_NONE) stage(nt - (T - 1), icst<0>{});
         else if (mode == 0) stage(nt - (T - 1), icst<0>{});
+        else if constexpr (MIX == MIX_NCO) stage(nt - (T - 1), icst<3>{});
         else if (mode == 1) stage(nt - (T - 1), icst<1>{});
         else stage(nt - (T - 1), icst<2>{});
         phase_sync();
@@ -1816,15 +1857,18 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
         for (int r = 0; r < RS_R; ++r) outv[r] = make_float2(acc[r].x, acc[r].y);
         out_m0 = m0;
         nt = nt_next; pt = pt_next;
-        if constexpr (MIX) rb = (rb + dn % D) % D;
+        if constexpr (MIX == MIX_RATIONAL) rb = (rb + dn % D) % D;
+        if constexpr (MIX == MIX_NCO) rb += nm * dn;
         phase_sync();                                               // every lane's window reads precede the next staging
     }
     flush();
 }
 template <int FMT, bool LUTM>
-__global__ __launch_bounds__(WV, RS_WPS) void k_resample(RsArgs a, WideConv cv) { resample_body<FMT, LUTM, false>(a, nullptr, cv); }
+__global__ __launch_bounds__(WV, RS_WPS) void k_resample(RsArgs a, WideConv cv) { resample_body<FMT, LUTM, MIX_NONE>(a, nullptr, cv); }
 template <int FMT, bool LUTM>
-__global__ __launch_bounds__(WV, RS_WPS) void k_tune(TuneArgs ta, WideConv cv) { resample_body<FMT, LUTM, true>(ta.r, &ta, cv); }
+__global__ __launch_bounds__(WV, RS_WPS) void k_tune(TuneArgs ta, WideConv cv) { resample_body<FMT, LUTM, MIX_RATIONAL>(ta.r, &ta, cv); }
+template <int FMT, bool LUTM>
+__global__ __launch_bounds__(WV, RS_WPS) void k_tune_nco(TuneArgs ta, WideConv cv) { resample_body<FMT, LUTM, MIX_NCO>(ta.r, &ta, cv); }
 #endif
 
 // ------------------------------------------------------------------------------------------

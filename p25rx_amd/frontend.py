@@ -611,7 +611,8 @@ class Resampler:
 class Tuner:
     """The tuner of docs/SPEC.md 3.0c (p25fe_tuner_t): K channels at rational frequency offsets out of ONE capture of any supported
     rate, each a 240 ksps cf32 row -- the resampler with a mixer in front.  freqs = [(num, den), ...] in cycles per input sample,
-    lowest terms.  Made for one FrontEnd (its device and u8 conversion; its channel count does not matter), which must outlive it."""
+    lowest terms.  Made for one FrontEnd (its device and u8 conversion; its channel count does not matter), which must outlive it.
+    Tuner.nco makes the other kind (SPEC 3.0d): channels at step / 2^32 cycles per input sample, any offset; its methods are these."""
 
     @staticmethod
     def freq(fs_hz, offset_hz):
@@ -635,19 +636,55 @@ class Tuner:
         L, M, T, taps = Resampler.design(fs_hz)
         return L, M, T, taps, [Tuner.freq(fs_hz, o) for o in offsets_hz]
 
-    def __init__(self, fe, L, M, T, taps, freqs):
+    @staticmethod
+    def nco_step(fs_hz, offset_hz):
+        """step = offset_hz / fs_hz * 2^32 rounded, as a signed 32-bit integer (p25fe_nco_step; needs no device)"""
+        L_ = _lib.load()
+        step = C.c_int32(0)
+        _lib.check(L_, None, L_.p25fe_nco_step(int(fs_hz), float(offset_hz), C.byref(step)))
+        return step.value
+
+    @staticmethod
+    def nco_factor(step, n):
+        """(c, s) of SPEC 3.0d for a step and an absolute index, as the kernel computes them (p25fe_nco_factor)"""
+        L_ = _lib.load()
+        cs = np.empty(2, dtype=np.float32)
+        _lib.check(L_, None, L_.p25fe_nco_factor(int(step), int(n), _p(cs)))
+        return cs[0], cs[1]
+
+    @staticmethod
+    def design_nco(fs_hz, offsets_hz):
+        """(L, M, T, taps, steps) for a tuner rate and the channels' offsets from its centre in Hz (fractional offsets welcome)"""
+        L, M, T, taps = Resampler.design(fs_hz)
+        return L, M, T, taps, [Tuner.nco_step(fs_hz, o) for o in offsets_hz]
+
+    def __init__(self, fe, L, M, T, taps, freqs=None, steps=None):
         self.fe, self.lib = fe, fe.L
         self.L, self.M, self.T = int(L), int(M), int(T)
         taps = np.ascontiguousarray(taps, dtype=np.float32)
         if taps.size != self.L * self.T:
             raise _lib.P25feError(_lib.ERR_ARG, "the table holds L * T taps")
+        if (freqs is None) == (steps is None):
+            raise _lib.P25feError(_lib.ERR_ARG, "a tuner is one kind: freqs or steps")
+        self.tn = C.c_void_p()
+        if steps is not None:
+            self.steps = [int(s) for s in steps]
+            self.K = len(self.steps)
+            step = np.array(self.steps, dtype=np.int64).astype(np.int32)
+            _lib.check(self.lib, fe.h, self.lib.p25fe_nco_create(fe.h, self.L, self.M, self.T, _p(taps), self.K, _p(step),
+                                                                       C.byref(self.tn)))
+            return
         self.freqs = [(int(a), int(b)) for a, b in freqs]
         self.K = len(self.freqs)
         num = np.array([f[0] for f in self.freqs], dtype=np.int32)
         den = np.array([f[1] for f in self.freqs], dtype=np.int32)
-        self.tn = C.c_void_p()
         _lib.check(self.lib, fe.h, self.lib.p25fe_tuner_create(fe.h, self.L, self.M, self.T, _p(taps), self.K, _p(num), _p(den),
                                                                C.byref(self.tn)))
+
+    @classmethod
+    def nco(cls, fe, L, M, T, taps, steps):
+        """a tuner of NCO channels (p25fe_nco_create): steps = signed 32-bit integers, step / 2^32 cycles per input sample"""
+        return cls(fe, L, M, T, taps, steps=steps)
 
     def close(self):
         if getattr(self, "tn", None):

@@ -1,7 +1,7 @@
 // p25fe_replay -- file-in / file-out driver in the role of the reference's command line for this path
 // (src/main.rs:95-102, 162-175, 278-283 and src/replay.rs:26-57): a deterministic harness for the hot path.
 //
-//   p25fe_replay [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] [-r RATE_HZ [-f OFFSET_HZ]] u8|s16|cf32|bb <in> <dibits.out>
+//   p25fe_replay [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] [-r RATE_HZ [-f OFFSET_HZ | -F OFFSET_HZ]] u8|s16|cf32|bb <in> <dibits.out>
 //   p25fe_replay -W WINDOW_BYTES u8|s16|cf32 <in> <dibits.out>
 //
 //     u8    RTL-SDR style interleaved u8 I/Q, the reference's live input (src/consts.rs:6: 32768-byte chunks)
@@ -29,6 +29,10 @@
 //     -f HZ     with -r: the channel's offset from the capture's centre in Hz (negative: below it).  The chunks then go through the
 //               tuner (docs/SPEC.md 3.0c, p25fe_tune) with the same table: OFFSET_HZ / RATE_HZ in lowest terms must have a
 //               denominator of at most 8192, which every 12.5 kHz or 6.25 kHz raster at the customary rates has.
+//
+//     -F HZ     with -r, instead of -f: the offset as a decimal that may be fractional, at any value up to half the rate -- a channel
+//               off the raster, or on it with the crystal's ppm error taken out.  The chunks go through the tuner's NCO channel
+//               (docs/SPEC.md 3.0d, p25fe_nco_create) at the step p25fe_nco_step gives: the nearest multiple of RATE_HZ / 2^32.
 //
 //     -W BYTES  bulk mode for long captures (p25fe_run_host_windows): a READER THREAD fills pinned blocks of eight windows
 //               from the file while the library pipelines the previous block -- window k + 1 on its way to the GPU,
@@ -103,7 +107,7 @@ struct Sink {
 
 static int usage(const char* argv0)
 {
-    std::fprintf(stderr, "usage: %s [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] [-r RATE_HZ [-f OFFSET_HZ]] u8|s16|cf32|bb <in> <dibits.out>\n"
+    std::fprintf(stderr, "usage: %s [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] [-r RATE_HZ [-f OFFSET_HZ | -F OFFSET_HZ]] u8|s16|cf32|bb <in> <dibits.out>\n"
                          "       %s -W WINDOW_BYTES u8|s16|cf32 <in> <dibits.out>\n", argv0, argv0);
     return 2;
 }
@@ -186,7 +190,8 @@ int main(int argc, char** argv)
     size_t batch = 64, window_bytes = 0;
     unsigned long rate_hz = 0;
     long long offset_hz = 0;
-    bool tune = false;
+    double offset_nco_hz = 0.0;
+    bool tune = false, nco = false;
     int a = 1;
     for (; a < argc && argv[a][0] == '-' && argv[a][1] != '\0'; a += 2) {
         if (a + 1 >= argc) return usage(argv[0]);
@@ -198,6 +203,12 @@ int main(int argc, char** argv)
             if (rate_hz == 0 || rate_hz > 0xfffffffful) return usage(argv[0]);
         }
         else if (!std::strcmp(argv[a], "-f")) { offset_hz = std::strtoll(argv[a + 1], nullptr, 10); tune = true; }
+        else if (!std::strcmp(argv[a], "-F")) {
+            char* end = nullptr;
+            offset_nco_hz = std::strtod(argv[a + 1], &end);
+            if (end == argv[a + 1] || *end != '\0') return usage(argv[0]);
+            tune = nco = true;
+        }
         else if (!std::strcmp(argv[a], "-W")) {
             char* end = nullptr;
             window_bytes = (size_t)std::strtoull(argv[a + 1], &end, 10);
@@ -206,7 +217,9 @@ int main(int argc, char** argv)
         }
         else return usage(argv[0]);
     }
-    if (argc - a != 3 || batch == 0 || (tune && !rate_hz)) return usage(argv[0]);
+    bool rational = false;                                            // -f and -F exclude each other
+    for (int k = 1; k < a; k += 2) rational = rational || !std::strcmp(argv[k], "-f");
+    if (argc - a != 3 || batch == 0 || (tune && !rate_hz) || (nco && rational)) return usage(argv[0]);
     const std::string mode = argv[a];
     std::ifstream in(argv[a + 1], std::ios::binary);
     if (!in) { std::fprintf(stderr, "unable to open %s\n", argv[a + 1]); return 1; }
@@ -247,7 +260,14 @@ int main(int argc, char** argv)
         expect(p25fe_resampler_design((uint32_t)rate_hz, &L, &M, &T, taps.data(), taps.size()), "unable to design the resampler");
         p25fe_resampler_t* rs = nullptr;
         p25fe_tuner_t* tn = nullptr;
-        if (tune) {
+        if (nco) {
+            int32_t step = 0;
+            if (p25fe_nco_step((uint32_t)rate_hz, offset_nco_hz, &step) != P25FE_OK) {
+                std::fprintf(stderr, "no tuner for %g Hz at %lu Hz (beyond half the rate)\n", offset_nco_hz, rate_hz);
+                return 1;
+            }
+            expect(p25fe_nco_create(h.get(), L, M, T, taps.data(), 1, &step, &tn), "unable to create the tuner");
+        } else if (tune) {
             int32_t num = 0, den = 0;
             if (p25fe_tuner_freq((uint32_t)rate_hz, offset_hz, &num, &den) != P25FE_OK) {
                 std::fprintf(stderr, "no tuner for %lld Hz at %lu Hz (beyond half the rate, or offset / rate in lowest terms has a denominator above %d)\n",

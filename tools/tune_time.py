@@ -4,12 +4,14 @@ device-resident capture (at least 1e8 samples, held as cf32, s16 and u8; what th
 Cases, per input format:
   (i)   2.5 Msps (12/125, designed table, channels on the 12.5 kHz raster: den 200) and 2.048 Msps (15/128, den 4096): the tuner with
         K = 1, 8 and 32 channels, beside K calls of p25fe_resample_dev on the same capture -- which tune nothing, but are the only
-        path to K rows that the library had before, and move the same bytes;
+        path to K rows that the library had before, and move the same bytes; and the tuner of NCO channels (k_tune_nco, SPEC
+        3.0d) with the same K at p25fe_nco_step of the same offsets, beside the rational tuner;
   (ii)  2.4 Msps (1/10, T = 80, SPEC 3.0's taps, den 192): the tuner with K = 32 beside p25fe_channelise_dev (all 192 channels of the
         raster) on the capture's first fifth (the channeliser's 192 rows of the whole capture would not be a fair buffer to hold).
 Every case sits between its own pair of device events and the cases alternate round by round, so a drift of the machine falls on
 all of them alike.  Before anything is timed, the centre channel of every tuner is compared bit for bit with the resampler's output.
-Per case: median / min / max in ms, ms per channel, and for the tuner its time against K resampler calls.
+Per case: median / min / max in ms, ms per channel, for the tuner its time against K resampler calls and for the NCO tuner its time
+against the rational tuner of the same K.
 One JSON line, also written to <out>/tune_time_<box>_<tag>.json.
 usage: tune_time.py [--samples 120000000] [--reps 20] [--out profiles] [--box NAME] [--tag run1]"""
 import argparse, json, os, socket, statistics, sys
@@ -47,10 +49,16 @@ def raster(fs, K):
     return [Tuner.freq(fs, 12500 * ((k + 1) // 2) * (-1 if k % 2 else 1)) for k in range(K)]
 
 
-rates = {}
+def raster_nco(fs, K):
+    """the same offsets as steps of the NCO"""
+    return [Tuner.nco_step(fs, 12500.0 * ((k + 1) // 2) * (-1 if k % 2 else 1)) for k in range(K)]
+
+
+rates, ncos = {}, {}
 for fs in (2500000, 2048000):
     L, M, T, taps = Resampler.design(fs)
     rates["%d/%d" % (L, M)] = (Resampler(fe, L, M, T, taps), {K: Tuner(fe, L, M, T, taps, raster(fs, K)) for K in KS}, L, M)
+    ncos["%d/%d" % (L, M)] = {K: Tuner.nco(fe, L, M, T, taps, raster_nco(fs, K)) for K in KS}
 spec = json.load(open(os.path.join(ROOT, "tests", "golden", "spec.json")))
 pre = np.array(spec["pre_taps"], dtype=np.float32)
 tn24 = Tuner(fe, 1, 10, 80, pre, raster(2400000, 32))
@@ -67,6 +75,9 @@ for name, (rs, tns, L, M) in rates.items():                          # the centr
         r, nr = rs.resample_dev(caps[f])
         assert no == nr and torch.equal(y[0, :no].view(torch.int32), r[0, :nr].view(torch.int32)), (name, f)
         assert not torch.equal(y[1, :no].view(torch.int32), r[0, :nr].view(torch.int32)), (name, f)
+        z, nz = ncos[name][8].tune_dev(caps[f], out=out[8:16])         # ... and so is the NCO's
+        assert nz == nr and torch.equal(z[0, :nz].view(torch.int32), r[0, :nr].view(torch.int32)), (name, f)
+        assert not torch.equal(z[1, :nz].view(torch.int32), r[0, :nr].view(torch.int32)), (name, f)
         del r
 torch.cuda.synchronize()
 
@@ -75,6 +86,7 @@ for name, (rs, tns, L, M) in rates.items():
     for f in caps:
         for K in KS:
             cases["tune_%s_K%d_%s" % (name, K, f)] = (lambda tn=tns[K], f=f, K=K: tn.tune_dev(caps[f], out=out[:K]), K)
+            cases["nco_%s_K%d_%s" % (name, K, f)] = (lambda tn=ncos[name][K], f=f, K=K: tn.tune_dev(caps[f], out=out[:K]), K)
 
             def k_calls(rs=rs, f=f, K=K):
                 for k in range(K):
@@ -111,6 +123,8 @@ for name in rates:
         for K in KS:
             t = res["cases"]["tune_%s_K%d_%s" % (name, K, f)]
             t["vs_k_resampler_calls"] = round(t["ms_median"] / res["cases"]["rs_x%d_%s_%s" % (K, name, f)]["ms_median"], 3)
+            o = res["cases"]["nco_%s_K%d_%s" % (name, K, f)]
+            o["vs_rational_tuner"] = round(o["ms_median"] / t["ms_median"], 3)
 line = json.dumps(res)
 print(line, flush=True)
 os.makedirs(a.out, exist_ok=True)
