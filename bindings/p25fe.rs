@@ -155,6 +155,23 @@ pub const RS_MAX_T: i32 = 1024;
 pub const RS_MAX_TABLE: i32 = 4096;
 /// p25fe_tuner_t: the tuner of docs/SPEC.md 3.0c (rational channels) or 3.0d (NCO channels), made from a Handle, which must outlive it
 pub enum Tuner {}
+/// p25fe_afc_t: the frequency measure of docs/SPEC.md 3.0f (made from a Handle, which must outlive it)
+pub enum Afc {}
+/// p25fe_afc_acc_t: one row's sums, 32 bytes
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct AfcAcc {
+    pub re: i64,
+    pub im: i64,
+    pub pow: i64,
+    pub n: u64,
+}
+/// P25FE_AFC_*: 2 <= D <= 64, 1 <= T <= 512, 1 <= rows <= 256, 0 <= shift <= 40
+pub const AFC_MIN_D: i32 = 2;
+pub const AFC_MAX_D: i32 = 64;
+pub const AFC_MAX_T: i32 = 512;
+pub const AFC_MAX_CH: i32 = 256;
+pub const AFC_MAX_SHIFT: i32 = 40;
 /// P25FE_TUNE_MAX_CH / _DEN: 1 <= channels <= 256; num / den in lowest terms, 1 <= den <= 8192, 2 |num| <= den
 pub const TUNE_MAX_CH: i32 = 256;
 pub const TUNE_MAX_DEN: i32 = 8192;
@@ -226,6 +243,16 @@ extern "C" {
     pub fn p25fe_nco_factor(step: i32, n: u64, cs: *mut f32) -> c_int;
     pub fn p25fe_nco_create(h: *mut Handle, l: i32, m: i32, t: i32, taps: *const f32, n_out_channels: i32, step: *const i32,
                                   out: *mut *mut Tuner) -> c_int;
+    // AFC (docs/SPEC.md 3.0e, 3.0f): an NCO channel's step changed in a stream without a phase jump, and the frequency measure
+    pub fn p25fe_afc_set_step(tn: *mut Tuner, k: i32, step: i32, abs_at: u64, stream: *mut c_void) -> c_int;
+    pub fn p25fe_afc_get_step(tn: *const Tuner, k: i32, step: *mut i32, ph0: *mut u32) -> c_int;
+    pub fn p25fe_afc_factor(step: i32, ph0: u32, n: u64, cs: *mut f32) -> c_int;
+    pub fn p25fe_afc_design(d: i32, cutoff_hz: f64, t: i32, taps: *mut f32, cap: usize) -> c_int;
+    pub fn p25fe_afc_create(h: *mut Handle, d: i32, t: i32, taps: *const f32, k: i32, out: *mut *mut Afc) -> c_int;
+    pub fn p25fe_afc_destroy(afc: *mut Afc);
+    pub fn p25fe_afc_measure_dev(afc: *mut Afc, d_rows: *const f32, row_stride: usize, n_hist: usize, n: usize, abs_first: u64,
+                                 shift: i32, d_acc: *mut AfcAcc, stream: *mut c_void) -> c_int;
+    pub fn p25fe_afc_hz(acc: *const AfcAcc, d: i32, hz: *mut f64, coherence: *mut f64) -> c_int;
     pub fn p25fe_n_baseband(abs0: u64, n: usize) -> usize;
     pub fn p25fe_slice_dev(h: *mut Handle, d_bb: *const f32, bb_stride: usize, n_hist_bb: usize, n_bb: usize, abs_bb0: u64,
                            d_anchor_in: *const Anchor, d_dibits: *mut u8, dibit_stride: usize, d_sync_pos: *mut i64,

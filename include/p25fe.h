@@ -479,6 +479,72 @@ int p25fe_nco_factor(int32_t step, uint64_t n, float cs[2]);
 int p25fe_nco_create(p25fe_t *h, int32_t L, int32_t M, int32_t T, const float *taps,
                            int32_t n_out_channels, const int32_t *step, p25fe_tuner_t **out);
 
+/* ---- AFC, part 1: an NCO channel's phase offset, and changing its step in a stream (docs/SPEC.md 3.0e) ---------------------------
+ * Every NCO channel has a phase offset ph0_k besides its step: ph = (ph0_k + step_k * n) mod 2^32, everything after ph as in 3.0d.
+ * p25fe_nco_create makes ph0 = 0 (3.0d, bit for bit); the product is skipped only when step == 0 && ph0 == 0. */
+
+/* ph0_k <- ph0_k + (step_k - step) * abs_at (mod 2^32), then step_k <- step: the mixer's factor at index abs_at is the same bits
+ * before and after, so a stream retuned at abs_at has no phase jump there.  Applies to the p25fe_tune_dev / p25fe_tune calls
+ * issued after it on `stream`; the channel's device record is rewritten in stream order, so a launch issued before it never sees the
+ * new numbers.  A null stream is the handle's, the one p25fe_tune uses, and the update is then also ordered against the default
+ * stream, where p25fe_tune_dev with a null stream enqueues.  A call mixes its WHOLE window, the T - 1 history samples
+ * included, with the current (step, ph0): the first T - 1 taps after a change see history mixed at a frequency that is off by the
+ * change (100 Hz over 84 samples at 2.5 Msps: 0.0034 cycles).  p25fe_tuner_reset leaves steps and offsets alone.
+ * P25FE_ERR_ARG: a null or rational tuner, k outside [0, n_out_channels), abs_at >= 2^62. */
+int p25fe_afc_set_step(p25fe_tuner_t *tn, int32_t k, int32_t step, uint64_t abs_at, void *stream);
+/* channel k's current step and phase offset, as the host holds them; no device is touched.  P25FE_ERR_ARG: a null or rational
+ * tuner, k outside the range, a null pointer. */
+int p25fe_afc_get_step(const p25fe_tuner_t *tn, int32_t k, int32_t *step, uint32_t *ph0);
+/* (c, s) of 3.0e for a step, a phase offset and an absolute index, with exactly the kernel's operations (ph0 = 0:
+ * p25fe_nco_factor); no device needed.  P25FE_ERR_ARG: a null pointer. */
+int p25fe_afc_factor(int32_t step, uint32_t ph0, uint64_t n, float cs[2]);
+
+/* ---- AFC, part 2: frequency measure (docs/SPEC.md 3.0f) ----------------------------------------------------------------------------
+ * Input: K rows of 240 ksps cf32, the tuner's output rows.  A channel-selective real FIR g[0 .. T) decimating by D (the tuner's
+ * own table cuts off at 60 kHz and lets the neighbours 12.5 kHz away through), then the lag-1 product at 240000 / D sps, quantised
+ * and summed as integers.  With absolute indices and x[n] = 0 for n < 0:
+ *     w[m]  = the resampler's y[m] with L = 1, M = D, T, taps = g            (n_m = m D + D - 1;  w[-1] = 0)
+ *     p.re  = fma( w[m].im, w[m-1].im, w[m].re * w[m-1].re)                  (= w[m] conj(w[m-1]))
+ *     p.im  = fma(-w[m].re, w[m-1].im, w[m].im * w[m-1].re)
+ *     e     = fma( w[m].im, w[m].im,   w[m].re * w[m].re)
+ *     Q(v)  = (int32) rintf(clamp(v * 2^shift, -2147483520, 2147483520)),  NaN -> 0
+ *     acc.re += Q(p.re);  acc.im += Q(p.im);  acc.pow += Q(e);  acc.n += 1    (64-bit, wrapping)
+ * A range owns the m whose n_m lies in it (p25fe_n_resample(1, D, abs_first, n) of them).  Integer sums commute: any split of a
+ * stream into ranges with enough history gives the same 32 bytes per channel as one range. */
+#define P25FE_AFC_MIN_D 2
+#define P25FE_AFC_MAX_D 64
+#define P25FE_AFC_MAX_T 512
+#define P25FE_AFC_MAX_CH 256
+#define P25FE_AFC_MAX_SHIFT 40
+typedef struct p25fe_afc p25fe_afc_t;
+typedef struct p25fe_afc_acc {
+    int64_t re, im;      /* sum of Q(p.re), Q(p.im) */
+    int64_t pow;         /* sum of Q(e) */
+    uint64_t n;          /* products summed */
+} p25fe_afc_acc_t;       /* 32 bytes */
+
+/* The recommended prefilter is D = 10, T = 240, cutoff 7000 Hz.  taps[0 .. T): a Kaiser(beta = 7.0)-windowed sinc of T points with
+ * its cutoff at cutoff_hz (at 240 ksps), scaled to sum 1, evaluated in double and rounded once -- p25fe_resampler_design's rule; no
+ * device needed.  P25FE_ERR_ARG: D or T outside the limits, a cutoff that is not finite or not in (0, 120000];
+ * P25FE_ERR_CAPACITY: cap < T (taps may then be null). */
+int p25fe_afc_design(int32_t D, double cutoff_hz, int32_t T, float *taps, size_t cap);
+/* A measuring object on h's device for K rows; h must outlive every USE of it (p25fe_afc_destroy alone is safe after
+ * p25fe_destroy(h)).  Every argument is checked before any device is touched: P25FE_ERR_ARG unless 2 <= D <= 64, 1 <= T <= 512,
+ * 1 <= K <= 256 and the taps are finite. */
+int p25fe_afc_create(p25fe_t *h, int32_t D, int32_t T, const float *taps, int32_t K, p25fe_afc_t **out);
+void p25fe_afc_destroy(p25fe_afc_t *afc);
+/* One range of the K rows d_rows + k * row_stride (complex samples; 8-byte aligned), conventions as p25fe_resample_dev: d_rows
+ * points at owned sample 0, n_hist valid samples precede it (n_hist >= T - 1 + D: exact continuation; what is missing reads as
+ * zero), abs_first matters modulo D.  ADDS into the caller's d_acc[K] (device, 8-byte aligned): zero the records to open a window.
+ * Enqueues on `stream`, synchronises nothing.  P25FE_ERR_ARG: a null or misaligned pointer, shift outside [0, 40],
+ * abs_first >= 2^62. */
+int p25fe_afc_measure_dev(p25fe_afc_t *afc, const float *d_rows, size_t row_stride, size_t n_hist, size_t n, uint64_t abs_first,
+                          int32_t shift, p25fe_afc_acc_t *d_acc, void *stream);
+/* A record the caller has copied back -> hz = atan2(im, re) / (2 pi) * 240000 / D (unambiguous to +-120000 / D) and coherence =
+ * hypot(re, im) / pow (1: one clean carrier; near 0: noise); both 0 when pow <= 0.  Host only.  P25FE_ERR_ARG: a null pointer, D
+ * outside the limits. */
+int p25fe_afc_hz(const p25fe_afc_acc_t *acc, int32_t D, double *hz, double *coherence);
+
 /* stages 6-7 on device baseband.  d_bb points at the first owned sample; n_hist_bb valid
  * samples precede it; abs_bb0 is its absolute index; d_anchor_in (nullable = no lock) is the
  * carry-in per channel.  d_result[c] is filled per channel.

@@ -17,6 +17,7 @@ S16_SCALE = 2.0 ** -15                    # P25FE_S16_SCALE: an int16 v is the s
 MAX_POSITION = 1 << 62                   # P25FE_MAX_POSITION: abs0 / abs_bb0 from here on are P25FE_ERR_ARG
 RS_MAX_L, RS_MAX_M, RS_MAX_T, RS_MAX_TABLE = 32, 1024, 1024, 4096   # P25FE_RS_MAX_*: limits of the rational resampler
 TUNE_MAX_CH, TUNE_MAX_DEN = 256, 8192    # P25FE_TUNE_MAX_*: limits of the tuner
+AFC_MIN_D, AFC_MAX_D, AFC_MAX_T, AFC_MAX_CH, AFC_MAX_SHIFT = 2, 64, 512, 256, 40   # P25FE_AFC_*: limits of the frequency measure
 
 OK, ERR_ARG, ERR_NO_DEVICE, ERR_HIP, ERR_CAPACITY, ERR_FORMAT, ERR_NOMEM, ERR_JIT, ERR_TIMEOUT = 0, -1, -2, -3, -4, -5, -6, -7, -8
 CLOCK_FIXED, CLOCK_TRACKING, CLOCK_TRACKING_RESLICE, CLOCK_CAUSAL_OK = 0, 1, 2, 0x100
@@ -63,6 +64,8 @@ CHAN_STATS_DTYPE = np.dtype([("sig_power_dbm", "<f4"), ("locked", "<i4"), ("n_di
                              ("last_sync_pos", "<i8"), ("bch", CODE_STATS_DTYPE)])
 assert CHAN_STATS_DTYPE.itemsize == 64
 assert ANCHOR_DTYPE.itemsize == C.sizeof(Anchor) and RESULT_DTYPE.itemsize == C.sizeof(Result)
+AFC_ACC_DTYPE = np.dtype([("re", "<i8"), ("im", "<i8"), ("pow", "<i8"), ("n", "<u8")])      # p25fe_afc_acc_t
+assert AFC_ACC_DTYPE.itemsize == 32
 
 # every symbol include/p25fe.h declares (tests check the library exports exactly these)
 SYMBOLS = [
@@ -83,6 +86,8 @@ SYMBOLS = [
     "p25fe_tuner_freq", "p25fe_tuner_rotator", "p25fe_tuner_create", "p25fe_tuner_destroy", "p25fe_tuner_reset", "p25fe_tune_dev",
     "p25fe_tune",
     "p25fe_nco_step", "p25fe_nco_factor", "p25fe_nco_create",
+    "p25fe_afc_set_step", "p25fe_afc_get_step", "p25fe_afc_factor", "p25fe_afc_design", "p25fe_afc_create", "p25fe_afc_destroy",
+    "p25fe_afc_measure_dev", "p25fe_afc_hz",
 ]
 
 
@@ -198,6 +203,15 @@ def load():
     L.p25fe_nco_step.argtypes = [C.c_uint32, C.c_double, pi32]
     L.p25fe_nco_factor.argtypes = [C.c_int32, u64, vp]
     L.p25fe_nco_create.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, vp, C.c_int32, vp, C.POINTER(vp)]
+    L.p25fe_afc_set_step.argtypes = [vp, C.c_int32, C.c_int32, u64, vp]
+    L.p25fe_afc_get_step.argtypes = [vp, C.c_int32, pi32, C.POINTER(C.c_uint32)]
+    L.p25fe_afc_factor.argtypes = [C.c_int32, C.c_uint32, u64, vp]
+    L.p25fe_afc_design.argtypes = [C.c_int32, C.c_double, C.c_int32, vp, sz]
+    L.p25fe_afc_create.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, C.POINTER(vp)]
+    L.p25fe_afc_destroy.argtypes = [vp]
+    L.p25fe_afc_destroy.restype = None
+    L.p25fe_afc_measure_dev.argtypes = [vp, vp, sz, sz, sz, u64, C.c_int32, vp, vp]
+    L.p25fe_afc_hz.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.p25fe_n_predecim.argtypes = [u64, sz]
     L.p25fe_n_predecim.restype = sz
     L.p25fe_n_baseband.argtypes = [u64, sz]

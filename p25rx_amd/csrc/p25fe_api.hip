@@ -1341,6 +1341,8 @@ static int launch_k6(p25fe_t* h, const void* d_iq, int fmt, size_t n_hist, size_
 // is C input rows to C output rows; the tuner is ONE input row to K output rows, plus the channels' frequencies: one rotator table per
 // distinct denominator and the per-channel numbers (TuneCh) in device memory.  A tuner of NCO channels (SPEC 3.0d; kernel:
 // k_tune_nco) is the same object with another kind: ONE rotator table, of denominator 256, and a step per channel in TuneCh.
+// An NCO channel also has a phase offset (SPEC 3.0e): the host keeps (step, ph0) per channel, p25fe_afc_set_step rewrites a
+// channel's record in stream order, and a launch goes to k_tune_nco_ph while any offset is not zero.
 // --------------------------------------------------------------------------------------------
 struct RsCore {
     p25fe_t* h = nullptr;
@@ -1360,7 +1362,23 @@ struct p25fe_tuner : RsCore {
     int rot_off = 0;                       // floats of dynamic LDS in front of the rotator's copy
     size_t lds = 0;                        // dynamic LDS of a launch: the table, and the largest rotator that is copied there
     DevBuf d_rot, d_ch;
+    std::vector<int32_t> step;             // NCO channels: the current step ...
+    std::vector<uint32_t> ph0;             // ... and phase offset of every channel, as the launches issued from now on see them
+    bool has_ph0() const { return std::any_of(ph0.begin(), ph0.end(), [](uint32_t v) { return v != 0; }); }
+    hipEvent_t ev = nullptr;               // orders a record's update between the handle's stream and the default stream (made on first use)
+    ~p25fe_tuner() { if (ev) (void)hipEventDestroy(ev); }
 };
+// The frequency measure of SPEC 3.0f (kernel: k_afc_measure): the prefilter's taps on the device and the shape
+struct p25fe_afc {
+    p25fe_t* h = nullptr;
+    int device = 0;
+    int D = 0, T = 0, K = 0;
+    DevBuf d_taps;
+};
+static bool afc_shape_ok(int64_t D, int64_t T)
+{
+    return D >= P25FE_AFC_MIN_D && D <= P25FE_AFC_MAX_D && T >= 1 && T <= P25FE_AFC_MAX_T;
+}
 
 static uint64_t gcd_u64(uint64_t a, uint64_t b) { while (b) { const uint64_t t = a % b; a = b; b = t; } return a; }
 static bool rs_ratio_ok(int64_t L, int64_t M)
@@ -1452,6 +1470,12 @@ static void rs_launch_as(dim3 grid, size_t lds, hipStream_t st, const TuneArgs& 
     hipLaunchKernelGGL((k_tune<FMT, LUTM>), grid, dim3(WV), lds, st, a, cv);
 }
 struct NcoArgs : TuneArgs {};              // the tuner's arguments on their way to k_tune_nco
+struct NcoPhArgs : NcoArgs {};             // ... and to k_tune_nco_ph
+template <int FMT, bool LUTM>
+static void rs_launch_as(dim3 grid, size_t lds, hipStream_t st, const NcoPhArgs& a, const WideConv& cv)
+{
+    hipLaunchKernelGGL((k_tune_nco_ph<FMT, LUTM>), grid, dim3(WV), lds, st, static_cast<const TuneArgs&>(a), cv);
+}
 template <int FMT, bool LUTM>
 static void rs_launch_as(dim3 grid, size_t lds, hipStream_t st, const NcoArgs& a, const WideConv& cv)
 {
@@ -1467,7 +1491,8 @@ static void rs_dispatch(int fmt, dim3 grid, size_t lds, hipStream_t st, const Ar
     else rs_launch_as<P25FE_FMT_U8, false>(grid, lds, st, a, cv);
 }
 
-// One range through k_resample (tn null: o->rows_in rows in and out) or k_tune / k_tune_nco (tn is o: one row in, tn->K rows out).
+// One range through k_resample (tn null: o->rows_in rows in and out) or k_tune / k_tune_nco / k_tune_nco_ph (tn is o: one row in,
+// tn->K rows out).
 static int rs_launch(RsCore* o, const p25fe_tuner* tn, const void* d_iq, int fmt, size_t ch_stride, size_t n_hist, size_t n,
                      uint64_t abs_first, float* d_out, size_t out_stride, hipStream_t st)
 {
@@ -1477,7 +1502,7 @@ static int rs_launch(RsCore* o, const p25fe_tuner* tn, const void* d_iq, int fmt
     if (out_stride < n_out) return P25FE_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (n_out == 0) return P25FE_OK;
-    NcoArgs ta;
+    NcoPhArgs ta;
     rs_fill_args(o, ta.r, d_iq, ch_stride, n_hist, n, abs_first, d_out, out_stride, n_out);
     const size_t per_wg = (size_t)ta.r.tile * RS_SUBS, groups = (n_out + per_wg - 1) / per_wg;
     dim3 grid((unsigned)groups, (unsigned)o->rows_in);
@@ -1490,7 +1515,8 @@ static int rs_launch(RsCore* o, const p25fe_tuner* tn, const void* d_iq, int fmt
     }
     const WideConv cv = wide_conv_of(h);
     (void)hipGetLastError();                                        // the check below is for THIS launch: drop what an earlier call of the thread left behind
-    if (tn && tn->nco) rs_dispatch(fmt, grid, tn->lds, st, ta, cv);
+    if (tn && tn->nco && tn->has_ph0()) rs_dispatch(fmt, grid, tn->lds, st, ta, cv);
+    else if (tn && tn->nco) rs_dispatch(fmt, grid, tn->lds, st, static_cast<const NcoArgs&>(ta), cv);
     else if (tn) rs_dispatch(fmt, grid, tn->lds, st, static_cast<const TuneArgs&>(ta), cv);
     else rs_dispatch(fmt, grid, sizeof(float) * (size_t)o->L * (size_t)o->TP, st, ta.r, cv);
     HIPCHK(h, hipGetLastError());
@@ -1694,16 +1720,15 @@ int p25fe_nco_step(uint32_t fs_in_hz, double offset_hz, int32_t* step)
     return P25FE_OK;
 }
 
-int p25fe_nco_factor(int32_t step, uint64_t n, float cs[2])
+// (c, s) of a 32-bit phase: SPEC 3.0d from `ph` on
+static void nco_factor_host(uint32_t ph, float cs[2])
 {
-    if (!cs) return P25FE_ERR_ARG;
     static const std::vector<float> rot = [] {
         std::vector<float> r(2 * (size_t)TN_NCO_DEN);
         (void)p25fe_tuner_rotator(TN_NCO_DEN, r.data(), r.size());
         return r;
     }();
     // SPEC 3.0d, the operations the kernel's nco_factor does, in its order (this file is compiled without contraction)
-    const uint32_t ph = (uint32_t)step * (uint32_t)n;
     const uint32_t ia = (ph + (1u << 23)) >> 24;
     const int32_t r = (int32_t)(ph - (ia << 24));
     const float t = (float)r * (float)(6.283185307179586476925 / 4294967296.0);
@@ -1713,6 +1738,12 @@ int p25fe_nco_factor(int32_t step, uint64_t n, float cs[2])
     const float C = rot[ia], S = rot[TN_NCO_DEN + ia];
     cs[0] = fmaf(-S, sf, C * cf);
     cs[1] = fmaf(C, sf, S * cf);
+}
+
+int p25fe_nco_factor(int32_t step, uint64_t n, float cs[2])
+{
+    if (!cs) return P25FE_ERR_ARG;
+    nco_factor_host((uint32_t)step * (uint32_t)n, cs);
     return P25FE_OK;
 }
 
@@ -1725,6 +1756,8 @@ int p25fe_nco_create(p25fe_t* h, int32_t L, int32_t M, int32_t T, const float* t
     if (int rc = rs_create(&tn, h, L, M, T, taps, 1)) return rc;    // (the handle is looked at last)
     const int K = tn->K = n_out_channels;
     tn->nco = true;
+    tn->step.assign(step, step + K);
+    tn->ph0.assign((size_t)K, 0u);
     std::vector<float> cs(2 * (size_t)TN_NCO_DEN), rot;
     (void)p25fe_tuner_rotator(TN_NCO_DEN, cs.data(), cs.size());
     for (int i = 0; i < TN_NCO_DEN; ++i) { rot.push_back(cs[i]); rot.push_back(cs[TN_NCO_DEN + i]); }
@@ -1758,6 +1791,133 @@ int p25fe_tune_dev(p25fe_tuner_t* tn, const void* d_iq, int fmt, size_t n_hist, 
 int p25fe_tune(p25fe_tuner_t* tn, const void* iq, int fmt, size_t n, float* out, size_t cap, size_t* n_out)
 {
     return rs_stream(tn, tn, iq, fmt, n, out, cap, n_out);
+}
+
+// --------------------------------------------------------------------------------------------
+// AFC (SPEC 3.0e, 3.0f): a channel's step changed in a stream, and the frequency measure
+// --------------------------------------------------------------------------------------------
+int p25fe_afc_factor(int32_t step, uint32_t ph0, uint64_t n, float cs[2])
+{
+    if (!cs) return P25FE_ERR_ARG;
+    nco_factor_host(ph0 + (uint32_t)step * (uint32_t)n, cs);
+    return P25FE_OK;
+}
+
+int p25fe_afc_set_step(p25fe_tuner_t* tn, int32_t k, int32_t step, uint64_t abs_at, void* stream)
+{
+    if (!tn || !tn->h || !tn->nco || k < 0 || k >= tn->K || position_refused(abs_at)) return P25FE_ERR_ARG;
+    p25fe_t* h = tn->h;
+    // the phase at abs_at stays: ph0 + step_old abs_at = ph0' + step abs_at (mod 2^32)
+    const uint32_t ph0 = tn->ph0[(size_t)k] + ((uint32_t)tn->step[(size_t)k] - (uint32_t)step) * (uint32_t)abs_at;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    (void)hipGetLastError();
+    // A null stream is the handle's (p25fe_tune's).  p25fe_tune_dev with a null stream enqueues on the default stream, which the
+    // handle's non-blocking stream is not ordered against: the update waits for what the default stream holds, and the default
+    // stream's later work waits for the update.
+    const hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    if (!stream) {
+        if (!tn->ev) HIPCHK(h, hipEventCreateWithFlags(&tn->ev, hipEventDisableTiming));
+        HIPCHK(h, hipEventRecord(tn->ev, nullptr));
+        HIPCHK(h, hipStreamWaitEvent(st, tn->ev, 0));
+    }
+    // by value through a one-thread kernel: ordered on the stream behind every launch issued before it, no host buffer to keep alive
+    hipLaunchKernelGGL(k_afc_set_ch, dim3(1), dim3(1), 0, st, tn->d_ch.as<TuneCh>() + k, (int)step, (unsigned)ph0);
+    HIPCHK(h, hipGetLastError());
+    if (!stream) {
+        HIPCHK(h, hipEventRecord(tn->ev, st));
+        HIPCHK(h, hipStreamWaitEvent(nullptr, tn->ev, 0));
+    }
+    tn->step[(size_t)k] = step; tn->ph0[(size_t)k] = ph0;
+    return P25FE_OK;
+}
+
+int p25fe_afc_get_step(const p25fe_tuner_t* tn, int32_t k, int32_t* step, uint32_t* ph0)
+{
+    if (!tn || !tn->nco || k < 0 || k >= tn->K || !step || !ph0) return P25FE_ERR_ARG;
+    *step = tn->step[(size_t)k]; *ph0 = tn->ph0[(size_t)k];
+    return P25FE_OK;
+}
+
+int p25fe_afc_design(int32_t D, double cutoff_hz, int32_t T, float* taps, size_t cap)
+{
+    if (!afc_shape_ok(D, T) || !(cutoff_hz - cutoff_hz == 0.0) || !(cutoff_hz > 0.0) || cutoff_hz > 120000.0) return P25FE_ERR_ARG;
+    const size_t N = (size_t)T;
+    if (cap < N || !taps) return P25FE_ERR_CAPACITY;
+    // p25fe_resampler_design's rule with L = 1 at 240 ksps and the caller's cutoff
+    const double pi = 3.14159265358979323846;
+    const double fc = cutoff_hz / (double)P25FE_RS_RATE_OUT_HZ;
+    const double mid = ((double)N - 1.0) / 2.0, den = rs_i0(7.0);
+    std::vector<double> hd(N);
+    double sum = 0.0;
+    for (size_t k = 0; k < N; ++k) {
+        const double x = (double)k - mid, arg = 2.0 * fc * x;
+        const double sinc = arg == 0.0 ? 1.0 : sin(pi * arg) / (pi * arg);
+        const double r = N > 1 ? x / mid : 0.0;
+        const double w = rs_i0(7.0 * sqrt(r * r < 1.0 ? 1.0 - r * r : 0.0)) / den;
+        hd[k] = sinc * w;                                           // (the prototype's gain 2 fc cancels in the scaling to sum 1)
+        sum += hd[k];
+    }
+    for (size_t k = 0; k < N; ++k) taps[k] = (float)(hd[k] / sum);
+    return P25FE_OK;
+}
+
+int p25fe_afc_create(p25fe_t* h, int32_t D, int32_t T, const float* taps, int32_t K, p25fe_afc_t** out)
+{
+    if (out) *out = nullptr;
+    if (!out || !afc_shape_ok(D, T) || K < 1 || K > P25FE_AFC_MAX_CH || !taps) return P25FE_ERR_ARG;
+    for (int k = 0; k < T; ++k) if (!finite_f(taps[k])) return P25FE_ERR_ARG;
+    if (!h) return P25FE_ERR_ARG;                                   // (the handle is looked at last)
+    p25fe_afc* o = new (std::nothrow) p25fe_afc;
+    if (!o) return P25FE_ERR_NOMEM;
+    o->h = h; o->device = h->cfg.device; o->D = D; o->T = T; o->K = K;
+    if (hipSetDevice(h->cfg.device) != hipSuccess || o->d_taps.ensure((size_t)T * sizeof(float)) != hipSuccess ||
+        hipMemcpy(o->d_taps.p, taps, (size_t)T * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        h->last_hip = (int)hipGetLastError(); delete o; return P25FE_ERR_HIP;
+    }
+    *out = o;
+    return P25FE_OK;
+}
+
+void p25fe_afc_destroy(p25fe_afc_t* afc) { rs_destroy(afc); }
+
+int p25fe_afc_measure_dev(p25fe_afc_t* afc, const float* d_rows, size_t row_stride, size_t n_hist, size_t n, uint64_t abs_first,
+                          int32_t shift, p25fe_afc_acc_t* d_acc, void* stream)
+{
+    if (!afc || !afc->h || !d_rows || !d_acc || position_refused(abs_first) || n >= P25FE_MAX_POSITION ||
+        row_stride >= P25FE_MAX_POSITION) return P25FE_ERR_ARG;
+    if (shift < 0 || shift > P25FE_AFC_MAX_SHIFT) return P25FE_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(d_rows) & 7u) != 0 || (reinterpret_cast<uintptr_t>(d_acc) & 7u) != 0) return P25FE_ERR_ARG;
+    p25fe_t* h = afc->h;
+    const int D = afc->D, T = afc->T;
+    const size_t n_out = p25fe_n_resample(1, D, abs_first, n);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (n_out == 0) return P25FE_OK;
+    AfcArgs a;
+    a.x = reinterpret_cast<const float2*>(d_rows); a.row_stride = (long)row_stride;
+    a.n_hist = (long)std::min(n_hist, (size_t)(T - 1 + D));        // nothing before that is ever read
+    a.n_new = (long)n; a.n_out = (long)n_out;
+    a.taps = afc->d_taps.as<float>(); a.D = D; a.T = T;
+    a.d0 = D - 1 - (int)(abs_first % (uint64_t)D);                  // owned w 0 is the first m with n_m = m D + D - 1 >= abs_first
+    a.tw = std::min(WV * RS_R, 1 + (RS_NIN - T) / D);
+    a.scale = ldexpf(1.0f, shift);
+    a.acc = d_acc;
+    const size_t per = (size_t)a.tw - 1, tiles = (n_out + per - 1) / per;
+    if (tiles > (size_t)0x7fffffffu) return P25FE_ERR_ARG;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(k_afc_measure, dim3((unsigned)tiles, (unsigned)afc->K), dim3(WV), 0, (hipStream_t)stream, a);
+    HIPCHK(h, hipGetLastError());
+    return P25FE_OK;
+}
+
+int p25fe_afc_hz(const p25fe_afc_acc_t* acc, int32_t D, double* hz, double* coherence)
+{
+    if (!acc || !hz || !coherence || D < P25FE_AFC_MIN_D || D > P25FE_AFC_MAX_D) return P25FE_ERR_ARG;
+    *hz = 0.0; *coherence = 0.0;
+    if (acc->pow <= 0) return P25FE_OK;
+    const double re = (double)acc->re, im = (double)acc->im;
+    *hz = atan2(im, re) / (2.0 * 3.14159265358979323846) * (double)P25FE_RS_RATE_OUT_HZ / (double)D;
+    *coherence = hypot(re, im) / (double)acc->pow;
+    return P25FE_OK;
 }
 
 // --------------------------------------------------------------------------------------------

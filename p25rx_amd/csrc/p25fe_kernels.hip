@@ -1577,15 +1577,20 @@ struct RsArgs {
 // denominator 256, which every channel copies to LDS; the signed residual below them turns that entry by a third-order sine and a
 // second-order cosine.  The phase is linear in n with no modulus but the register's own: a workgroup multiplies once, a lane adds
 // step per element and step SPV 64 per vector.  A channel with step = 0 skips the product.
+// A phase offset (SPEC 3.0e, k_tune_nco_ph) is the fourth value of MIX: ph = ph0 + step * n, ph0 per channel in TuneCh::D (which the
+// NCO path never reads).  It is what lets a channel's step change in a stream without a phase jump (p25fe_afc_set_step); the one
+// addition sits where the workgroup forms its first phase, and a channel skips the product only when step and ph0 are both 0.  An
+// object whose offsets are all zero launches k_tune_nco.
 // ------------------------------------------------------------------------------------------
 constexpr int TN_ROT_LDS_DEN = 512;          // largest denominator whose rotator goes to LDS (8 bytes per entry: 4 KB)
 constexpr int TN_NCO_DEN = 256;              // the NCO's coarse table: 2^32 / 256 = 2^24 phase units per entry
-constexpr int MIX_NONE = 0, MIX_RATIONAL = 1, MIX_NCO = 2;
+constexpr int MIX_NONE = 0, MIX_RATIONAL = 1, MIX_NCO = 2, MIX_NCO_PH = 3;
 
 struct TuneCh {
     const float2* rot;      // (C_D[i], S_D[i]), i < D, device
     int D, nm;              // denominator; num mod D in [0, D) (0: the capture's centre, no product)
                             // an NCO channel: D = TN_NCO_DEN, nm = step (any value; 0: no product)
+                            // ... as k_tune_nco_ph reads it: D = ph0, the phase offset (any value), nm = step
 };
 struct TuneArgs {
     RsArgs r;               // the resampler's, for ONE input row (ch_stride unused); y_stride = distance of the K output rows
@@ -1713,9 +1718,10 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
             for (unsigned k = tid; k < D; k += WV) rot[k] = c.rot[k];
         ROT = rot;
     }
-    if constexpr (MIX == MIX_NCO) {
+    if constexpr (MIX == MIX_NCO || MIX == MIX_NCO_PH) {
         float2* const rot = reinterpret_cast<float2*>(RS_HT + ta->rot_off);
-        mode = nm == 0 ? 0 : 3;
+        if constexpr (MIX == MIX_NCO_PH) mode = (nm | D) == 0 ? 0 : 3;   // (D is ph0 here)
+        else mode = nm == 0 ? 0 : 3;
         if (mode == 3)
             for (int k = tid; k < TN_NCO_DEN; k += WV) rot[k] = c.rot[k];
         ROT = rot;
@@ -1736,9 +1742,10 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
         il = (nm * (unsigned)(SPV * tid)) % D;                      // this lane's index offset inside a vector row
         sv = (nm * (unsigned)(SPV * WV)) % D;                       // ... and from one of its vectors to the next
     }
-    if constexpr (MIX == MIX_NCO) {
+    if constexpr (MIX == MIX_NCO || MIX == MIX_NCO_PH) {
         // rb is the PHASE of the window's first sample, step * position mod 2^32: the one product; it follows the window by adds
         rb = nm * (unsigned)((long)ta->abs_first + (nt - (T - 1)));
+        if constexpr (MIX == MIX_NCO_PH) rb += D;                   // ... plus the channel's offset ph0
         il = nm * (unsigned)(SPV * tid);
         sv = nm * (unsigned)(SPV * WV);
     }
@@ -1763,7 +1770,8 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
     // MODE: 0 no product (the resampler, and a channel at the capture's centre) / 1 rotator in LDS / 2 rotator gathered / 3 NCO
     auto stage = [&](long base, auto mc) {
         constexpr int MODE = decltype(mc)::value;
-        static_assert(MODE == 0 || (MIX == MIX_RATIONAL && MODE <= 2) || (MIX == MIX_NCO && MODE == 3), "only the tuner mixes");
+        static_assert(MODE == 0 || (MIX == MIX_RATIONAL && MODE <= 2) || ((MIX == MIX_NCO || MIX == MIX_NCO_PH) && MODE == 3),
+                      "only the tuner mixes");
         const long v0 = base >> LS;
         const int sh = (int)(base - (v0 << LS));                    // 0 .. SPV - 1
         const bool interior = (v0 << LS) >= -a.n_hist && (v0 << LS) + (long)SPV * NV * WV <= a.n_new;   // uniform
@@ -1830,7 +1838,7 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
         if (m0 >= a.n_out) break;                                   // uniform
         if constexpr (MIX == MIX_NONE) stage(nt - (T - 1), icst<0>{});
         else if (mode == 0) stage(nt - (T - 1), icst<0>{});
-        else if constexpr (MIX == MIX_NCO) stage(nt - (T - 1), icst<3>{});
+        else if constexpr (MIX == MIX_NCO || MIX == MIX_NCO_PH) stage(nt - (T - 1), icst<3>{});
         else if (mode == 1) stage(nt - (T - 1), icst<1>{});
         else stage(nt - (T - 1), icst<2>{});
         phase_sync();
@@ -1858,7 +1866,7 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
         out_m0 = m0;
         nt = nt_next; pt = pt_next;
         if constexpr (MIX == MIX_RATIONAL) rb = (rb + dn % D) % D;
-        if constexpr (MIX == MIX_NCO) rb += nm * dn;
+        if constexpr (MIX == MIX_NCO || MIX == MIX_NCO_PH) rb += nm * dn;
         phase_sync();                                               // every lane's window reads precede the next staging
     }
     flush();
@@ -1869,6 +1877,114 @@ template <int FMT, bool LUTM>
 __global__ __launch_bounds__(WV, RS_WPS) void k_tune(TuneArgs ta, WideConv cv) { resample_body<FMT, LUTM, MIX_RATIONAL>(ta.r, &ta, cv); }
 template <int FMT, bool LUTM>
 __global__ __launch_bounds__(WV, RS_WPS) void k_tune_nco(TuneArgs ta, WideConv cv) { resample_body<FMT, LUTM, MIX_NCO>(ta.r, &ta, cv); }
+template <int FMT, bool LUTM>
+__global__ __launch_bounds__(WV, RS_WPS) void k_tune_nco_ph(TuneArgs ta, WideConv cv) { resample_body<FMT, LUTM, MIX_NCO_PH>(ta.r, &ta, cv); }
+// One NCO channel's record (step, ph0) rewritten in stream order: launches issued before it on the stream have read the old one,
+// launches after it read the new one (p25fe_afc_set_step)
+__global__ void k_afc_set_ch(TuneCh* ch, int step, unsigned ph0)
+{
+    if (threadIdx.x == 0 && blockIdx.x == 0) { ch->nm = step; ch->D = (int)ph0; }
+}
+
+// ------------------------------------------------------------------------------------------
+// K0d: frequency measure (SPEC 3.0f): K rows at 240 ksps -> per row the integer sums of w[m] conj(w[m-1]) and |w[m]|^2 over a
+// range, w = the row through a caller-supplied real FIR decimated by D (the L = 1 case of 3.0b: the channel-selective filter
+// the tuner's 60 kHz table is not).  One wave per workgroup, grid (tiles, K).  A tile stages its cf32 window and the taps in LDS
+// and runs rs_fir with the resampler's lane-owns-outputs mapping (lane t computes w's t + 64 r of the tile); it computes ONE
+// extra leading w, so every product of the tile has its predecessor in the tile.  The w's go through LDS to the lane that owns
+// the product; products are quantised to integers (Q of 3.0f) and summed per lane in 64 bits, across the wave by shuffles, and
+// lane 0 adds the four sums to the caller's record with 64-bit integer global atomics: integer sums commute, so the order in
+// which workgroups arrive does not matter and any split of a stream gives the same record.
+// The window is linear as in K0b, RS_NIN positions: a tile holds tw = min(64 RS_R, 1 + (RS_NIN - T) / D) w's (>= 24 at the
+// limits D = 64, T = 512).
+// ------------------------------------------------------------------------------------------
+struct AfcArgs {
+    const float2* x;        // owned sample 0 of row 0, 8-B aligned
+    long row_stride;        // samples
+    long n_hist, n_new;
+    long n_out;             // w's the range owns (= products)
+    const float* taps;      // device, T floats
+    int D, T;
+    int d0;                 // input index of owned w 0 relative to owned sample 0 (0 .. D - 1)
+    int tw;                 // w's per tile, the leading one included
+    float scale;            // 2^shift
+    p25fe_afc_acc_t* acc;   // [K]
+};
+
+// Q of SPEC 3.0f: v 2^shift (exact), NaN -> 0, clamped to +-(2^31 - 128), rounded to nearest even
+__device__ __forceinline__ long afc_q(float v, float scale)
+{
+    float s = v * scale;
+    s = s != s ? 0.0f : s;
+    s = s < -2147483520.0f ? -2147483520.0f : (s > 2147483520.0f ? 2147483520.0f : s);
+    return (long)(int)__builtin_rintf(s);
+}
+__device__ __forceinline__ long afc_wave_sum(long v)
+{
+#pragma unroll
+    for (int d = 1; d < WV; d <<= 1) {
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)(unsigned long)v, d, WV);
+        const unsigned hi = (unsigned)__shfl_xor((int)(unsigned)((unsigned long)v >> 32), d, WV);
+        v = (long)((unsigned long)v + (((unsigned long)hi << 32) | lo));
+    }
+    return v;
+}
+
+__global__ __launch_bounds__(WV) void k_afc_measure(AfcArgs a)
+{
+    constexpr int TW = WV * RS_R;
+    __shared__ float2 X[RS_NIN];
+    __shared__ float G[P25FE_AFC_MAX_T];
+    __shared__ float2 W[TW];
+    const int tid = threadIdx.x;
+    const int T = a.T, D = a.D, P = a.tw - 1;                       // P products per tile
+    const long o0 = (long)blockIdx.x * P;                           // the tile's first owned w
+    const long left = a.n_out - o0;
+    if (left <= 0) return;                                          // uniform (the host launches no such tile)
+    const int nw = (left < (long)P ? (int)left : P) + 1;            // w's of this tile: 2 .. tw
+    const float2* xr = a.x + (size_t)blockIdx.y * a.row_stride;
+    for (int k = tid; k < T; k += WV) G[k] = a.taps[k];
+    // window: X[k] = x[base + k]; w j of the tile (w o0 - 1 + j of the range) ends at X[j D + T - 1]
+    const long base = (long)a.d0 + (o0 - 1) * D - (T - 1);
+    const int need = (nw - 1) * D + T;                              // <= RS_NIN
+    for (int k = tid; k < need; k += WV) {
+        const long i = base + k;
+        X[k] = (i >= -a.n_hist && i < a.n_new) ? xr[i] : make_float2(0.f, 0.f);
+    }
+    phase_sync();
+    const float2* xp[RS_R];
+    v2f acc[RS_R];
+#pragma unroll
+    for (int r = 0; r < RS_R; ++r) {
+        const int j = tid + WV * r;
+        xp[r] = X + (j < nw ? j * D : 0) + (T - 1);                 // idle slots walk the window's first T positions
+        acc[r] = v2f{0.f, 0.f};
+    }
+    rs_fir(xp, G, T, acc);
+#pragma unroll
+    for (int r = 0; r < RS_R; ++r) W[tid + WV * r] = make_float2(acc[r].x, acc[r].y);
+    phase_sync();
+    long sre = 0, sim = 0, spw = 0, sn = 0;
+#pragma unroll
+    for (int r = 0; r < RS_R; ++r) {
+        const int j = tid + WV * r;
+        if (j >= 1 && j < nw) {
+            const float2 w = make_float2(acc[r].x, acc[r].y), q = W[j - 1];
+            sre += afc_q(__builtin_fmaf(w.y, q.y, w.x * q.x), a.scale);
+            sim += afc_q(__builtin_fmaf(-w.x, q.y, w.y * q.x), a.scale);
+            spw += afc_q(__builtin_fmaf(w.y, w.y, w.x * w.x), a.scale);
+            sn += 1;
+        }
+    }
+    sre = afc_wave_sum(sre); sim = afc_wave_sum(sim); spw = afc_wave_sum(spw); sn = afc_wave_sum(sn);
+    if (tid == 0) {
+        unsigned long long* rec = reinterpret_cast<unsigned long long*>(a.acc + blockIdx.y);
+        atomicAdd(rec + 0, (unsigned long long)sre);
+        atomicAdd(rec + 1, (unsigned long long)sim);
+        atomicAdd(rec + 2, (unsigned long long)spw);
+        atomicAdd(rec + 3, (unsigned long long)sn);
+    }
+}
 #endif
 
 // ------------------------------------------------------------------------------------------

@@ -699,6 +699,18 @@ class Tuner:
     def reset(self):
         _lib.check(self.lib, self.fe.h, self.lib.p25fe_tuner_reset(self.tn))
 
+    def set_step(self, k, step, abs_at):
+        """NCO channel k goes on at `step` from the absolute index abs_at with no phase jump there (p25fe_afc_set_step, SPEC 3.0e);
+        applies to the tune_dev calls issued after it on the current stream, and to tune"""
+        _lib.check(self.lib, self.fe.h, self.lib.p25fe_afc_set_step(self.tn, int(k), int(step), int(abs_at), self.fe._stream()))
+        self.steps[int(k)] = int(step)
+
+    def get_step(self, k):
+        """(step, ph0) of NCO channel k as the launches issued from now on see them (p25fe_afc_get_step)"""
+        step, ph0 = C.c_int32(0), C.c_uint32(0)
+        _lib.check(self.lib, self.fe.h, self.lib.p25fe_afc_get_step(self.tn, int(k), C.byref(step), C.byref(ph0)))
+        return step.value, ph0.value
+
     def tune_dev(self, iq, n_hist=0, abs0=0, offset=0, out=None):
         """cf32, int16 or uint8 [n, 2] on the device -> (cf32 [K, n_out (padded), 2], n_out); `offset` = index of the first owned
         sample inside `iq` (>= n_hist), abs0 its position in the stream.  The rows feed a K-channel FrontEnd's run_dev / demod_dev."""
@@ -732,3 +744,78 @@ class Tuner:
         no = C.c_size_t(0)
         _lib.check(self.lib, self.fe.h, self.lib.p25fe_tune(self.tn, _p(iq), fmt, n, _p(out), cap, C.byref(no)))
         return out[:, :no.value].copy()
+
+
+class Afc:
+    """The frequency measure of docs/SPEC.md 3.0f (p25fe_afc_t): per row of 240 ksps cf32 -- a tuner's output rows -- the integer sums
+    of w[m] conj(w[m-1]) and |w[m]|^2, w = the row through a real low-pass (taps, T of them) decimated by D.  Made for one FrontEnd
+    (its device), which must outlive it; K rows."""
+
+    DEFAULT = (10, 240, 7000.0)                                      # D, T, cutoff in Hz: the recommended prefilter
+
+    @staticmethod
+    def design(D=10, T=240, cutoff_hz=7000.0):
+        """the prefilter's taps, float32 [T] (p25fe_afc_design; needs no device)"""
+        L_ = _lib.load()
+        taps = np.empty(max(int(T), 0), dtype=np.float32)
+        _lib.check(L_, None, L_.p25fe_afc_design(int(D), float(cutoff_hz), int(T), _p(taps), taps.size))
+        return taps
+
+    @staticmethod
+    def factor(step, ph0, n):
+        """(c, s) of SPEC 3.0e for a step, a phase offset and an absolute index (p25fe_afc_factor)"""
+        L_ = _lib.load()
+        cs = np.empty(2, dtype=np.float32)
+        _lib.check(L_, None, L_.p25fe_afc_factor(int(step), int(ph0), int(n), _p(cs)))
+        return cs[0], cs[1]
+
+    @staticmethod
+    def hz(acc, D):
+        """one record (an element of an AFC_ACC_DTYPE array) -> (hz, coherence) (p25fe_afc_hz; host only)"""
+        L_ = _lib.load()
+        rec = np.zeros(1, dtype=_lib.AFC_ACC_DTYPE)
+        rec[0] = acc
+        hz, coh = C.c_double(0.0), C.c_double(0.0)
+        _lib.check(L_, None, L_.p25fe_afc_hz(_p(rec), int(D), C.byref(hz), C.byref(coh)))
+        return hz.value, coh.value
+
+    def __init__(self, fe, K, D=10, T=240, taps=None, cutoff_hz=7000.0):
+        self.fe, self.lib = fe, fe.L
+        self.K, self.D, self.T = int(K), int(D), int(T)
+        taps = Afc.design(D, T, cutoff_hz) if taps is None else np.ascontiguousarray(taps, dtype=np.float32)
+        if taps.size != self.T:
+            raise _lib.P25feError(_lib.ERR_ARG, "the prefilter holds T taps")
+        self.afc = C.c_void_p()
+        _lib.check(self.lib, fe.h, self.lib.p25fe_afc_create(fe.h, self.D, self.T, _p(taps), self.K, C.byref(self.afc)))
+
+    def close(self):
+        if getattr(self, "afc", None):
+            self.lib.p25fe_afc_destroy(self.afc)
+            self.afc = None
+
+    __del__ = close
+
+    def new_acc(self):
+        """K zeroed records on the device (uint8 [K, 32]): an open window"""
+        import torch
+        return torch.zeros((self.K, 32), dtype=torch.uint8, device="cuda:%d" % self.fe.device)
+
+    def measure(self, rows, n_hist=0, abs0=0, offset=0, n=None, shift=24, acc=None):
+        """rows: cf32 [K, cols, 2] on the device (a tuner's output); the range is samples [offset, offset + n) of every row, abs0 the
+        position of its first sample, n_hist valid samples before it.  ADDS into acc (new_acc() when None) and returns it."""
+        assert rows.is_cuda and rows.dim() == 3 and rows.shape[0] == self.K and rows.shape[2] == 2 and rows.stride(2) == 1
+        assert rows.stride(1) == 2 and rows.stride(0) % 2 == 0
+        if n is None:
+            n = rows.shape[1] - offset
+        assert 0 <= n_hist <= offset and offset + n <= rows.shape[1]
+        if acc is None:
+            acc = self.new_acc()
+        _lib.check(self.lib, self.fe.h,
+                   self.lib.p25fe_afc_measure_dev(self.afc, C.c_void_p(rows.data_ptr() + 8 * offset), rows.stride(0) // 2, n_hist, n, abs0,
+                                                  int(shift), C.c_void_p(acc.data_ptr()), self.fe._stream()))
+        return acc
+
+    @staticmethod
+    def records(acc):
+        """the device records -> NumPy structured array [K] (syncs the stream)"""
+        return np.frombuffer(acc.cpu().numpy().tobytes(), dtype=_lib.AFC_ACC_DTYPE).copy()

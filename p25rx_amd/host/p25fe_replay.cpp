@@ -1,7 +1,7 @@
 // p25fe_replay -- file-in / file-out driver in the role of the reference's command line for this path
 // (src/main.rs:95-102, 162-175, 278-283 and src/replay.rs:26-57): a deterministic harness for the hot path.
 //
-//   p25fe_replay [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] [-r RATE_HZ [-f OFFSET_HZ | -F OFFSET_HZ]] u8|s16|cf32|bb <in> <dibits.out>
+//   p25fe_replay [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] [-r RATE_HZ [-f OFFSET_HZ | -F OFFSET_HZ [-a MS]]] u8|s16|cf32|bb <in> <dibits.out>
 //   p25fe_replay -W WINDOW_BYTES u8|s16|cf32 <in> <dibits.out>
 //
 //     u8    RTL-SDR style interleaved u8 I/Q, the reference's live input (src/consts.rs:6: 32768-byte chunks)
@@ -33,6 +33,11 @@
 //     -F HZ     with -r, instead of -f: the offset as a decimal that may be fractional, at any value up to half the rate -- a channel
 //               off the raster, or on it with the crystal's ppm error taken out.  The chunks go through the tuner's NCO channel
 //               (docs/SPEC.md 3.0d, p25fe_nco_create) at the step p25fe_nco_step gives: the nearest multiple of RATE_HZ / 2^32.
+//
+//     -a MS     with -F: automatic frequency correction.  The first MS ms of the capture are tuned at -F's offset while the GPU
+//               measures the tuned row's frequency error (docs/SPEC.md 3.0f, p25fe_afc_measure_dev, the recommended prefilter);
+//               then the channel's step is corrected ONCE by the estimate, without a phase jump (3.0e, p25fe_afc_set_step), and
+//               the stream carries on.  The estimate is printed, and goes to the -j events as {"event":"afc", ...}.
 //
 //     -W BYTES  bulk mode for long captures (p25fe_run_host_windows): a READER THREAD fills pinned blocks of eight windows
 //               from the file while the library pipelines the previous block -- window k + 1 on its way to the GPU,
@@ -107,7 +112,7 @@ struct Sink {
 
 static int usage(const char* argv0)
 {
-    std::fprintf(stderr, "usage: %s [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] [-r RATE_HZ [-f OFFSET_HZ | -F OFFSET_HZ]] u8|s16|cf32|bb <in> <dibits.out>\n"
+    std::fprintf(stderr, "usage: %s [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] [-r RATE_HZ [-f OFFSET_HZ | -F OFFSET_HZ [-a MS]]] u8|s16|cf32|bb <in> <dibits.out>\n"
                          "       %s -W WINDOW_BYTES u8|s16|cf32 <in> <dibits.out>\n", argv0, argv0);
     return 2;
 }
@@ -191,6 +196,7 @@ int main(int argc, char** argv)
     unsigned long rate_hz = 0;
     long long offset_hz = 0;
     double offset_nco_hz = 0.0;
+    double afc_ms = 0.0;                                              // -a: measure the first MS ms at -F's offset, correct once
     bool tune = false, nco = false;
     int a = 1;
     for (; a < argc && argv[a][0] == '-' && argv[a][1] != '\0'; a += 2) {
@@ -209,6 +215,11 @@ int main(int argc, char** argv)
             if (end == argv[a + 1] || *end != '\0') return usage(argv[0]);
             tune = nco = true;
         }
+        else if (!std::strcmp(argv[a], "-a")) {
+            char* end = nullptr;
+            afc_ms = std::strtod(argv[a + 1], &end);
+            if (end == argv[a + 1] || *end != '\0' || !(afc_ms > 0.0) || afc_ms > 60000.0) return usage(argv[0]);
+        }
         else if (!std::strcmp(argv[a], "-W")) {
             char* end = nullptr;
             window_bytes = (size_t)std::strtoull(argv[a + 1], &end, 10);
@@ -219,13 +230,13 @@ int main(int argc, char** argv)
     }
     bool rational = false;                                            // -f and -F exclude each other
     for (int k = 1; k < a; k += 2) rational = rational || !std::strcmp(argv[k], "-f");
-    if (argc - a != 3 || batch == 0 || (tune && !rate_hz) || (nco && rational)) return usage(argv[0]);
+    if (argc - a != 3 || batch == 0 || (tune && !rate_hz) || (nco && rational) || (afc_ms > 0.0 && !nco)) return usage(argv[0]);
     const std::string mode = argv[a];
     std::ifstream in(argv[a + 1], std::ios::binary);
     if (!in) { std::fprintf(stderr, "unable to open %s\n", argv[a + 1]); return 1; }
     Handle h(0, 1);
     if (window_bytes) {
-        if (wpath || jpath || rate_hz || tune || (mode != "u8" && mode != "s16" && mode != "cf32")) return usage(argv[0]);
+        if (wpath || jpath || rate_hz || tune || afc_ms > 0.0 || (mode != "u8" && mode != "s16" && mode != "cf32")) return usage(argv[0]);
         return bulk(h, mode, in, argv[a + 2], window_bytes);
     }
     Chan<std::vector<uint8_t>> reader;
@@ -260,8 +271,8 @@ int main(int argc, char** argv)
         expect(p25fe_resampler_design((uint32_t)rate_hz, &L, &M, &T, taps.data(), taps.size()), "unable to design the resampler");
         p25fe_resampler_t* rs = nullptr;
         p25fe_tuner_t* tn = nullptr;
+        int32_t step = 0;
         if (nco) {
-            int32_t step = 0;
             if (p25fe_nco_step((uint32_t)rate_hz, offset_nco_hz, &step) != P25FE_OK) {
                 std::fprintf(stderr, "no tuner for %g Hz at %lu Hz (beyond half the rate)\n", offset_nco_hz, rate_hz);
                 return 1;
@@ -282,11 +293,69 @@ int main(int argc, char** argv)
         std::vector<char> buf(n_chunk * bps);
         std::vector<float> x240(2 * (n_chunk * (size_t)L / (size_t)M + 2)), bb(x240.size() / 10 + 2);
         unsigned notifier = 0;
-        while (in.read(buf.data(), (std::streamsize)buf.size()) || in.gcount() > 0) {
+        // -a MS: the frequency measure (docs/SPEC.md 3.0f, the recommended prefilter) runs on the tuned row while the first MS ms of
+        // the capture go by; then the channel's step is corrected ONCE, without a phase jump (3.0e), and the stream carries on
+        size_t meas_left = afc_ms > 0.0 ? std::max<size_t>(1, (size_t)((double)rate_hz * afc_ms / 1000.0)) : 0;   // input samples still to measure
+        const int32_t afc_d = 10, afc_t = 240;
+        const size_t afc_keep = (size_t)(afc_t - 1 + afc_d);
+        p25fe_afc_t* afc = nullptr;
+        float* d_row = nullptr;
+        p25fe_afc_acc_t* d_acc = nullptr;
+        std::vector<float> row;                                       // [history | the chunk's tuned samples], as it goes to the device
+        std::vector<float> tail;                                      // the last afc_keep tuned samples (fewer at the start)
+        uint64_t consumed = 0, pos240 = 0;
+        if (meas_left) {
+            std::vector<float> g((size_t)afc_t);
+            expect(p25fe_afc_design(afc_d, 7000.0, afc_t, g.data(), g.size()), "unable to design the measure's prefilter");
+            expect(p25fe_afc_create(h.get(), afc_d, afc_t, g.data(), 1, &afc), "unable to create the frequency measure");
+            const p25fe_afc_acc_t zero = {0, 0, 0, 0};
+            if (hipMalloc(reinterpret_cast<void**>(&d_row), (afc_keep + x240.size() / 2) * 2 * sizeof(float)) != hipSuccess ||
+                hipMalloc(reinterpret_cast<void**>(&d_acc), sizeof zero) != hipSuccess ||
+                hipMemcpy(d_acc, &zero, sizeof zero, hipMemcpyHostToDevice) != hipSuccess) {
+                std::fprintf(stderr, "p25fe_replay: no device memory for the frequency measure\n");
+                return 1;
+            }
+        }
+        for (;;) {
+            const size_t want_n = meas_left ? std::min(n_chunk, meas_left) : n_chunk;
+            if (!(in.read(buf.data(), (std::streamsize)(want_n * bps)) || in.gcount() > 0)) break;
             const size_t n = (size_t)in.gcount() / bps;
             size_t n240 = 0, n_out = 0;
             if (tn) expect(p25fe_tune(tn, buf.data(), fmt, n, x240.data(), x240.size() / 2, &n240), "unable to tune");
             else expect(p25fe_resample(rs, buf.data(), fmt, n, x240.data(), x240.size() / 2, &n240), "unable to resample");
+            consumed += n;
+            if (meas_left) {
+                const size_t nh = tail.size() / 2;
+                row.assign(tail.begin(), tail.end());
+                row.insert(row.end(), x240.begin(), x240.begin() + (long)(2 * n240));
+                if (hipMemcpy(d_row, row.data(), row.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+                    std::fprintf(stderr, "p25fe_replay: unable to copy the tuned row to the device\n");
+                    return 1;
+                }
+                expect(p25fe_afc_measure_dev(afc, d_row + 2 * nh, 0, nh, n240, pos240, 24, d_acc, nullptr), "unable to measure the frequency");
+                tail.assign(row.end() - (long)(2 * std::min(afc_keep, row.size() / 2)), row.end());
+                meas_left = n < want_n ? 0 : meas_left - n;           // (a capture shorter than MS ms: what there is)
+                if (!meas_left) {
+                    p25fe_afc_acc_t acc;
+                    if (hipMemcpy(&acc, d_acc, sizeof acc, hipMemcpyDeviceToHost) != hipSuccess) {
+                        std::fprintf(stderr, "p25fe_replay: unable to read the frequency measure\n");
+                        return 1;
+                    }
+                    double hz = 0.0, coherence = 0.0;
+                    int32_t dstep = 0;
+                    expect(p25fe_afc_hz(&acc, afc_d, &hz, &coherence), "unable to evaluate the frequency measure");
+                    expect(p25fe_nco_step((uint32_t)rate_hz, hz, &dstep), "unable to turn the estimate into a step");
+                    const int32_t new_step = (int32_t)((uint32_t)step + (uint32_t)dstep);
+                    expect(p25fe_afc_set_step(tn, 0, new_step, consumed, nullptr), "unable to retune");
+                    std::fprintf(stderr, "p25fe_replay: afc: %.1f Hz off (coherence %.3f, %" PRIu64 " products); step %d -> %d at sample %" PRIu64 "\n",
+                                 hz, coherence, acc.n, step, new_step, consumed);
+                    if (hub.js)
+                        std::fprintf(hub.js, "{\"event\":\"afc\",\"hz\":%.3f,\"coherence\":%.6f,\"products\":%" PRIu64 ",\"step\":%d,\"at\":%" PRIu64 "}\n",
+                                     hz, coherence, acc.n, new_step, consumed);
+                    step = new_step;
+                }
+            }
+            pos240 += n240;
             float power = 0.f;
             const bool want = (++notifier % 4) == 0;
             expect(p25fe_demod_cf32(h.get(), x240.data(), n240, bb.data(), bb.size(), &n_out, want ? &power : nullptr),
@@ -295,6 +364,9 @@ int main(int argc, char** argv)
             chan.send(Baseband{std::vector<float>(bb.begin(), bb.begin() + (long)n_out)});
             recv.run(dump, hub);
         }
+        p25fe_afc_destroy(afc);
+        (void)hipFree(d_row);
+        (void)hipFree(d_acc);
         p25fe_resampler_destroy(rs);
         p25fe_tuner_destroy(tn);
     } else if (mode == "u8") {
