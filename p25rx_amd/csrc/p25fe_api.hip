@@ -1340,9 +1340,8 @@ static int launch_k6(p25fe_t* h, const void* d_iq, int fmt, size_t n_hist, size_
 // and the state of the host streaming form (position, format, the last T - 1 samples per input row as they came in).  The resampler
 // is C input rows to C output rows; the tuner is ONE input row to K output rows, plus the channels' frequencies: one rotator table per
 // distinct denominator and the per-channel numbers (TuneCh) in device memory.  A tuner of NCO channels (SPEC 3.0d; kernel:
-// k_tune_nco) is the same object with another kind: ONE rotator table, of denominator 256, and a step per channel in TuneCh.
-// An NCO channel also has a phase offset (SPEC 3.0e): the host keeps (step, ph0) per channel, p25fe_afc_set_step rewrites a
-// channel's record in stream order, and a launch goes to k_tune_nco_ph while any offset is not zero.
+// k_tune_nco) is the same object with another kind: ONE rotator table, of denominator 256, and a step and a phase offset per channel
+// in TuneCh (SPEC 3.0e): the host keeps (step, ph0) per channel, and p25fe_afc_set_step rewrites a channel's record in stream order.
 // --------------------------------------------------------------------------------------------
 struct RsCore {
     p25fe_t* h = nullptr;
@@ -1358,13 +1357,12 @@ struct RsCore {
 struct p25fe_resampler : RsCore {};
 struct p25fe_tuner : RsCore {
     int K = 0;
-    bool nco = false;                      // the kind: rational channels (k_tune) or NCO channels (k_tune_nco)
+    int mix = MIX_RATIONAL;                // the kind, as the kernel's MIX: rational channels (k_tune) or NCO channels (k_tune_nco)
     int rot_off = 0;                       // floats of dynamic LDS in front of the rotator's copy
     size_t lds = 0;                        // dynamic LDS of a launch: the table, and the largest rotator that is copied there
     DevBuf d_rot, d_ch;
     std::vector<int32_t> step;             // NCO channels: the current step ...
     std::vector<uint32_t> ph0;             // ... and phase offset of every channel, as the launches issued from now on see them
-    bool has_ph0() const { return std::any_of(ph0.begin(), ph0.end(), [](uint32_t v) { return v != 0; }); }
     hipEvent_t ev = nullptr;               // orders a record's update between the handle's stream and the default stream (made on first use)
     ~p25fe_tuner() { if (ev) (void)hipEventDestroy(ev); }
 };
@@ -1399,12 +1397,50 @@ static double rs_i0(double x)
     for (int k = 1; k < 64; ++k) { t *= (x / (2.0 * k)) * (x / (2.0 * k)); s += t; if (t < 1e-18 * s) break; }
     return s;
 }
+// The Kaiser-windowed sinc (beta = 7) of both design calls: N taps of cutoff fc (cycles per sample), hd[k] = g sinc w, scaled to sum s
+static void rs_kaiser_sinc(size_t N, double fc, double g, double s, float* taps)
+{
+    const double pi = 3.14159265358979323846;
+    const double mid = ((double)N - 1.0) / 2.0, den = rs_i0(7.0);
+    std::vector<double> hd(N);
+    double sum = 0.0;
+    for (size_t k = 0; k < N; ++k) {
+        const double x = (double)k - mid, arg = 2.0 * fc * x;
+        const double sinc = arg == 0.0 ? 1.0 : sin(pi * arg) / (pi * arg);
+        const double r = N > 1 ? x / mid : 0.0;
+        const double w = rs_i0(7.0 * sqrt(r * r < 1.0 ? 1.0 - r * r : 0.0)) / den;
+        hd[k] = g * sinc * w;
+        sum += hd[k];
+    }
+    for (size_t k = 0; k < N; ++k) taps[k] = (float)(hd[k] * s / sum);
+}
 // num / den in lowest terms inside the tuner's limits (0 / 1 is the centre)
 static bool tn_freq_ok(int64_t num, int64_t den)
 {
     if (den < 1 || den > P25FE_TUNE_MAX_DEN) return false;
     const int64_t an = num < 0 ? -num : num;
     return 2 * an <= den && gcd_u64((uint64_t)an, (uint64_t)den) == 1;
+}
+
+// The end of both tuner constructors: the rotators' host image (interleaved (cos, sin) pairs) and the channels' records to the
+// device, and the dynamic LDS of a launch (lds_den: the largest denominator whose rotator is copied there).  ch[k] comes with
+// everything but its rotator's address, which is pair at[k] of the image.  On failure tn is gone.
+static int tn_finish(p25fe_tuner* tn, const std::vector<float>& rot, std::vector<TuneCh>& ch, const std::vector<long>& at, int lds_den,
+                     p25fe_tuner_t** out)
+{
+    tn->rot_off = (int)round_up((size_t)tn->L * tn->TP, 2);
+    tn->lds = sizeof(float) * ((size_t)tn->rot_off + 2 * (size_t)lds_den);
+    if (tn->d_rot.ensure(rot.size() * sizeof(float)) == hipSuccess && tn->d_ch.ensure(ch.size() * sizeof(TuneCh)) == hipSuccess) {
+        for (size_t k = 0; k < ch.size(); ++k) ch[k].rot = tn->d_rot.as<float2>() + at[k];
+        if (hipMemcpy(tn->d_rot.p, rot.data(), rot.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
+            hipMemcpy(tn->d_ch.p, ch.data(), ch.size() * sizeof(TuneCh), hipMemcpyHostToDevice) == hipSuccess) {
+            *out = tn;
+            return P25FE_OK;
+        }
+    }
+    tn->h->last_hip = (int)hipGetLastError();
+    delete tn;
+    return P25FE_ERR_HIP;
 }
 
 // A new object of either kind: the shape and the table are checked first (they need no handle, and no device is touched before
@@ -1459,40 +1495,25 @@ static bool rs_pointers_refused(const RsCore* o, const void* d_iq, int fmt, size
            (o->rows_in > 1 && ch_stride % fmt_stride_unit(fmt) != 0);
 }
 
-template <int FMT, bool LUTM>
-static void rs_launch_as(dim3 grid, size_t lds, hipStream_t st, const RsArgs& a, const WideConv& cv)
+// the kernel of a MIX value (the resampler takes the tuner's arguments' first part)
+template <int MIX, int FMT, bool LUTM>
+static void rs_launch_as(dim3 grid, size_t lds, hipStream_t st, const TuneArgs& ta, const WideConv& cv)
 {
-    hipLaunchKernelGGL((k_resample<FMT, LUTM>), grid, dim3(WV), lds, st, a, cv);
+    if constexpr (MIX == MIX_NONE) hipLaunchKernelGGL((k_resample<FMT, LUTM>), grid, dim3(WV), lds, st, ta.r, cv);
+    else if constexpr (MIX == MIX_RATIONAL) hipLaunchKernelGGL((k_tune<FMT, LUTM>), grid, dim3(WV), lds, st, ta, cv);
+    else hipLaunchKernelGGL((k_tune_nco<FMT, LUTM>), grid, dim3(WV), lds, st, ta, cv);
 }
-template <int FMT, bool LUTM>
-static void rs_launch_as(dim3 grid, size_t lds, hipStream_t st, const TuneArgs& a, const WideConv& cv)
+// ... and its instance for a format: cf32, s16, u8 with the table as arithmetic or looked up
+template <int MIX>
+static void rs_dispatch(int fmt, dim3 grid, size_t lds, hipStream_t st, const TuneArgs& ta, const WideConv& cv)
 {
-    hipLaunchKernelGGL((k_tune<FMT, LUTM>), grid, dim3(WV), lds, st, a, cv);
-}
-struct NcoArgs : TuneArgs {};              // the tuner's arguments on their way to k_tune_nco
-struct NcoPhArgs : NcoArgs {};             // ... and to k_tune_nco_ph
-template <int FMT, bool LUTM>
-static void rs_launch_as(dim3 grid, size_t lds, hipStream_t st, const NcoPhArgs& a, const WideConv& cv)
-{
-    hipLaunchKernelGGL((k_tune_nco_ph<FMT, LUTM>), grid, dim3(WV), lds, st, static_cast<const TuneArgs&>(a), cv);
-}
-template <int FMT, bool LUTM>
-static void rs_launch_as(dim3 grid, size_t lds, hipStream_t st, const NcoArgs& a, const WideConv& cv)
-{
-    hipLaunchKernelGGL((k_tune_nco<FMT, LUTM>), grid, dim3(WV), lds, st, static_cast<const TuneArgs&>(a), cv);
-}
-// the instance of a kernel for a format: cf32, s16, u8 with the table as arithmetic or looked up
-template <class Args>
-static void rs_dispatch(int fmt, dim3 grid, size_t lds, hipStream_t st, const Args& a, const WideConv& cv)
-{
-    if (fmt == P25FE_FMT_CF32) rs_launch_as<P25FE_FMT_CF32, false>(grid, lds, st, a, cv);
-    else if (fmt == P25FE_FMT_S16) rs_launch_as<P25FE_FMT_S16, false>(grid, lds, st, a, cv);
-    else if (cv.lut) rs_launch_as<P25FE_FMT_U8, true>(grid, lds, st, a, cv);
-    else rs_launch_as<P25FE_FMT_U8, false>(grid, lds, st, a, cv);
+    if (fmt == P25FE_FMT_CF32) rs_launch_as<MIX, P25FE_FMT_CF32, false>(grid, lds, st, ta, cv);
+    else if (fmt == P25FE_FMT_S16) rs_launch_as<MIX, P25FE_FMT_S16, false>(grid, lds, st, ta, cv);
+    else if (cv.lut) rs_launch_as<MIX, P25FE_FMT_U8, true>(grid, lds, st, ta, cv);
+    else rs_launch_as<MIX, P25FE_FMT_U8, false>(grid, lds, st, ta, cv);
 }
 
-// One range through k_resample (tn null: o->rows_in rows in and out) or k_tune / k_tune_nco / k_tune_nco_ph (tn is o: one row in,
-// tn->K rows out).
+// One range through k_resample (tn null: o->rows_in rows in and out) or k_tune / k_tune_nco (tn is o: one row in, tn->K rows out).
 static int rs_launch(RsCore* o, const p25fe_tuner* tn, const void* d_iq, int fmt, size_t ch_stride, size_t n_hist, size_t n,
                      uint64_t abs_first, float* d_out, size_t out_stride, hipStream_t st)
 {
@@ -1502,7 +1523,7 @@ static int rs_launch(RsCore* o, const p25fe_tuner* tn, const void* d_iq, int fmt
     if (out_stride < n_out) return P25FE_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (n_out == 0) return P25FE_OK;
-    NcoPhArgs ta;
+    TuneArgs ta;
     rs_fill_args(o, ta.r, d_iq, ch_stride, n_hist, n, abs_first, d_out, out_stride, n_out);
     const size_t per_wg = (size_t)ta.r.tile * RS_SUBS, groups = (n_out + per_wg - 1) / per_wg;
     dim3 grid((unsigned)groups, (unsigned)o->rows_in);
@@ -1515,10 +1536,9 @@ static int rs_launch(RsCore* o, const p25fe_tuner* tn, const void* d_iq, int fmt
     }
     const WideConv cv = wide_conv_of(h);
     (void)hipGetLastError();                                        // the check below is for THIS launch: drop what an earlier call of the thread left behind
-    if (tn && tn->nco && tn->has_ph0()) rs_dispatch(fmt, grid, tn->lds, st, ta, cv);
-    else if (tn && tn->nco) rs_dispatch(fmt, grid, tn->lds, st, static_cast<const NcoArgs&>(ta), cv);
-    else if (tn) rs_dispatch(fmt, grid, tn->lds, st, static_cast<const TuneArgs&>(ta), cv);
-    else rs_dispatch(fmt, grid, sizeof(float) * (size_t)o->L * (size_t)o->TP, st, ta.r, cv);
+    if (!tn) rs_dispatch<MIX_NONE>(fmt, grid, sizeof(float) * (size_t)o->L * (size_t)o->TP, st, ta, cv);
+    else if (tn->mix == MIX_RATIONAL) rs_dispatch<MIX_RATIONAL>(fmt, grid, tn->lds, st, ta, cv);
+    else rs_dispatch<MIX_NCO>(fmt, grid, tn->lds, st, ta, cv);
     HIPCHK(h, hipGetLastError());
     return P25FE_OK;
 }
@@ -1594,20 +1614,8 @@ int p25fe_resampler_design(uint32_t fs_in_hz, int32_t* L, int32_t* M, int32_t* T
     *L = (int32_t)l; *M = (int32_t)m; *T = (int32_t)t;
     const size_t N = (size_t)(l * t);
     if (cap < N || !taps) return P25FE_ERR_CAPACITY;
-    const double pi = 3.14159265358979323846;
     const double fc = 60000.0 / ((double)l * (double)fs_in_hz);       // cutoff in cycles per sample of the prototype's rate
-    const double mid = ((double)N - 1.0) / 2.0, den = rs_i0(7.0);
-    std::vector<double> hd(N);
-    double sum = 0.0;
-    for (size_t k = 0; k < N; ++k) {
-        const double x = (double)k - mid, arg = 2.0 * fc * x;
-        const double sinc = arg == 0.0 ? 1.0 : sin(pi * arg) / (pi * arg);
-        const double r = N > 1 ? x / mid : 0.0;
-        const double w = rs_i0(7.0 * sqrt(r * r < 1.0 ? 1.0 - r * r : 0.0)) / den;
-        hd[k] = 2.0 * fc * sinc * w;
-        sum += hd[k];
-    }
-    for (size_t k = 0; k < N; ++k) taps[k] = (float)(hd[k] * (double)l / sum);
+    rs_kaiser_sinc(N, fc, 2.0 * fc, (double)l, taps);                 // the prototype's gain 2 fc, every phase's taps sum to 1
     return P25FE_OK;
 }
 
@@ -1679,36 +1687,24 @@ int p25fe_tuner_create(p25fe_t* h, int32_t L, int32_t M, int32_t T, const float*
     if (int rc = rs_create(&tn, h, L, M, T, taps, 1)) return rc;    // (the handle is looked at last)
     const int K = tn->K = n_out_channels;
     // one rotator per distinct denominator, (cos, sin) interleaved, one after the other in one buffer
-    std::vector<long> at(P25FE_TUNE_MAX_DEN + 1, -1);
+    std::vector<long> at_den(P25FE_TUNE_MAX_DEN + 1, -1), at((size_t)K);
     std::vector<float> rot, cs;
+    std::vector<TuneCh> ch((size_t)K);
     int lds_den = 0;
     for (int k = 0; k < K; ++k) {
         const int D = den[k];
         if (num[k] != 0 && D <= TN_ROT_LDS_DEN && D > lds_den) lds_den = D;
-        if (at[D] >= 0) continue;
-        at[D] = (long)(rot.size() / 2);
-        cs.resize(2 * (size_t)D);
-        (void)p25fe_tuner_rotator(D, cs.data(), cs.size());
-        for (int i = 0; i < D; ++i) { rot.push_back(cs[i]); rot.push_back(cs[D + i]); }
-    }
-    tn->rot_off = (int)round_up((size_t)L * tn->TP, 2);
-    tn->lds = sizeof(float) * ((size_t)tn->rot_off + 2 * (size_t)lds_den);
-    std::vector<TuneCh> ch((size_t)K);
-    if (tn->d_rot.ensure(rot.size() * sizeof(float)) == hipSuccess && tn->d_ch.ensure((size_t)K * sizeof(TuneCh)) == hipSuccess) {
-        for (int k = 0; k < K; ++k) {
-            ch[k].rot = tn->d_rot.as<float2>() + at[den[k]];
-            ch[k].D = den[k];
-            ch[k].nm = (int)(((int64_t)num[k] % den[k] + den[k]) % den[k]);
+        if (at_den[D] < 0) {
+            at_den[D] = (long)(rot.size() / 2);
+            cs.resize(2 * (size_t)D);
+            (void)p25fe_tuner_rotator(D, cs.data(), cs.size());
+            for (int i = 0; i < D; ++i) { rot.push_back(cs[i]); rot.push_back(cs[D + i]); }
         }
-        if (hipMemcpy(tn->d_rot.p, rot.data(), rot.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(tn->d_ch.p, ch.data(), ch.size() * sizeof(TuneCh), hipMemcpyHostToDevice) == hipSuccess) {
-            *out = tn;
-            return P25FE_OK;
-        }
+        at[(size_t)k] = at_den[D];
+        ch[(size_t)k].D = D;
+        ch[(size_t)k].nm = (int)(((int64_t)num[k] % D + D) % D);
     }
-    h->last_hip = (int)hipGetLastError();
-    delete tn;
-    return P25FE_ERR_HIP;
+    return tn_finish(tn, rot, ch, at, lds_den, out);
 }
 
 int p25fe_nco_step(uint32_t fs_in_hz, double offset_hz, int32_t* step)
@@ -1755,26 +1751,15 @@ int p25fe_nco_create(p25fe_t* h, int32_t L, int32_t M, int32_t T, const float* t
     p25fe_tuner* tn = nullptr;
     if (int rc = rs_create(&tn, h, L, M, T, taps, 1)) return rc;    // (the handle is looked at last)
     const int K = tn->K = n_out_channels;
-    tn->nco = true;
+    tn->mix = MIX_NCO;
     tn->step.assign(step, step + K);
     tn->ph0.assign((size_t)K, 0u);
     std::vector<float> cs(2 * (size_t)TN_NCO_DEN), rot;
     (void)p25fe_tuner_rotator(TN_NCO_DEN, cs.data(), cs.size());
     for (int i = 0; i < TN_NCO_DEN; ++i) { rot.push_back(cs[i]); rot.push_back(cs[TN_NCO_DEN + i]); }
-    tn->rot_off = (int)round_up((size_t)L * tn->TP, 2);
-    tn->lds = sizeof(float) * ((size_t)tn->rot_off + 2 * (size_t)TN_NCO_DEN);
     std::vector<TuneCh> ch((size_t)K);
-    if (tn->d_rot.ensure(rot.size() * sizeof(float)) == hipSuccess && tn->d_ch.ensure((size_t)K * sizeof(TuneCh)) == hipSuccess) {
-        for (int k = 0; k < K; ++k) { ch[k].rot = tn->d_rot.as<float2>(); ch[k].D = TN_NCO_DEN; ch[k].nm = step[k]; }
-        if (hipMemcpy(tn->d_rot.p, rot.data(), rot.size() * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(tn->d_ch.p, ch.data(), ch.size() * sizeof(TuneCh), hipMemcpyHostToDevice) == hipSuccess) {
-            *out = tn;
-            return P25FE_OK;
-        }
-    }
-    h->last_hip = (int)hipGetLastError();
-    delete tn;
-    return P25FE_ERR_HIP;
+    for (int k = 0; k < K; ++k) { ch[(size_t)k].ph0 = 0u; ch[(size_t)k].step = step[k]; }
+    return tn_finish(tn, rot, ch, std::vector<long>((size_t)K, 0), TN_NCO_DEN, out);   // every channel has the one table
 }
 
 void p25fe_tuner_destroy(p25fe_tuner_t* tn) { rs_destroy(tn); }
@@ -1805,7 +1790,7 @@ int p25fe_afc_factor(int32_t step, uint32_t ph0, uint64_t n, float cs[2])
 
 int p25fe_afc_set_step(p25fe_tuner_t* tn, int32_t k, int32_t step, uint64_t abs_at, void* stream)
 {
-    if (!tn || !tn->h || !tn->nco || k < 0 || k >= tn->K || position_refused(abs_at)) return P25FE_ERR_ARG;
+    if (!tn || !tn->h || tn->mix != MIX_NCO || k < 0 || k >= tn->K || position_refused(abs_at)) return P25FE_ERR_ARG;
     p25fe_t* h = tn->h;
     // the phase at abs_at stays: ph0 + step_old abs_at = ph0' + step abs_at (mod 2^32)
     const uint32_t ph0 = tn->ph0[(size_t)k] + ((uint32_t)tn->step[(size_t)k] - (uint32_t)step) * (uint32_t)abs_at;
@@ -1833,7 +1818,7 @@ int p25fe_afc_set_step(p25fe_tuner_t* tn, int32_t k, int32_t step, uint64_t abs_
 
 int p25fe_afc_get_step(const p25fe_tuner_t* tn, int32_t k, int32_t* step, uint32_t* ph0)
 {
-    if (!tn || !tn->nco || k < 0 || k >= tn->K || !step || !ph0) return P25FE_ERR_ARG;
+    if (!tn || tn->mix != MIX_NCO || k < 0 || k >= tn->K || !step || !ph0) return P25FE_ERR_ARG;
     *step = tn->step[(size_t)k]; *ph0 = tn->ph0[(size_t)k];
     return P25FE_OK;
 }
@@ -1843,21 +1828,8 @@ int p25fe_afc_design(int32_t D, double cutoff_hz, int32_t T, float* taps, size_t
     if (!afc_shape_ok(D, T) || !(cutoff_hz - cutoff_hz == 0.0) || !(cutoff_hz > 0.0) || cutoff_hz > 120000.0) return P25FE_ERR_ARG;
     const size_t N = (size_t)T;
     if (cap < N || !taps) return P25FE_ERR_CAPACITY;
-    // p25fe_resampler_design's rule with L = 1 at 240 ksps and the caller's cutoff
-    const double pi = 3.14159265358979323846;
-    const double fc = cutoff_hz / (double)P25FE_RS_RATE_OUT_HZ;
-    const double mid = ((double)N - 1.0) / 2.0, den = rs_i0(7.0);
-    std::vector<double> hd(N);
-    double sum = 0.0;
-    for (size_t k = 0; k < N; ++k) {
-        const double x = (double)k - mid, arg = 2.0 * fc * x;
-        const double sinc = arg == 0.0 ? 1.0 : sin(pi * arg) / (pi * arg);
-        const double r = N > 1 ? x / mid : 0.0;
-        const double w = rs_i0(7.0 * sqrt(r * r < 1.0 ? 1.0 - r * r : 0.0)) / den;
-        hd[k] = sinc * w;                                           // (the prototype's gain 2 fc cancels in the scaling to sum 1)
-        sum += hd[k];
-    }
-    for (size_t k = 0; k < N; ++k) taps[k] = (float)(hd[k] / sum);
+    // p25fe_resampler_design's rule with L = 1 at 240 ksps and the caller's cutoff (the prototype's gain cancels in the scaling to sum 1)
+    rs_kaiser_sinc(N, cutoff_hz / (double)P25FE_RS_RATE_OUT_HZ, 1.0, 1.0, taps);
     return P25FE_OK;
 }
 

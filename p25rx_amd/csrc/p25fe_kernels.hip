@@ -1572,26 +1572,26 @@ struct RsArgs {
 //   * the rotator table (interleaved (cos, sin) pairs) is copied to dynamic LDS behind the taps when den <= TN_ROT_LDS_DEN and
 //     gathered from global memory (L2-resident: at most 64 KB) otherwise -- the same numbers either way;
 //   * the per-channel numbers sit in device memory (TuneCh), read with scalar loads.
-// NCO channels (SPEC 3.0d, k_tune_nco) are the third value of MIX: a channel's frequency is step / 2^32 cycles per sample, its phase
-// the wrapping 32-bit product step * n.  The top eight bits of the phase (rounded) pick an entry of the ONE rotator table of
-// denominator 256, which every channel copies to LDS; the signed residual below them turns that entry by a third-order sine and a
-// second-order cosine.  The phase is linear in n with no modulus but the register's own: a workgroup multiplies once, a lane adds
-// step per element and step SPV 64 per vector.  A channel with step = 0 skips the product.
-// A phase offset (SPEC 3.0e, k_tune_nco_ph) is the fourth value of MIX: ph = ph0 + step * n, ph0 per channel in TuneCh::D (which the
-// NCO path never reads).  It is what lets a channel's step change in a stream without a phase jump (p25fe_afc_set_step); the one
-// addition sits where the workgroup forms its first phase, and a channel skips the product only when step and ph0 are both 0.  An
-// object whose offsets are all zero launches k_tune_nco.
+// NCO channels (SPEC 3.0e, k_tune_nco) are the third value of MIX: a channel's frequency is step / 2^32 cycles per sample, its phase
+// the wrapping 32-bit sum ph0 + step * n, (step, ph0) per channel in TuneCh.  The top eight bits of the phase (rounded) pick an entry
+// of the ONE rotator table of denominator 256, which every channel copies to LDS; the signed residual below them turns that entry by
+// a third-order sine and a second-order cosine.  The phase is linear in n with no modulus but the register's own: a workgroup
+// multiplies and adds ph0 once, a lane adds step per element and step SPV 64 per vector.  A channel with step = 0 and ph0 = 0 skips
+// the product.  ph0 is what lets a channel's step change in a stream without a phase jump (p25fe_afc_set_step); SPEC 3.0d is the
+// ph0 = 0 case, which is every channel of a new object.
 // ------------------------------------------------------------------------------------------
 constexpr int TN_ROT_LDS_DEN = 512;          // largest denominator whose rotator goes to LDS (8 bytes per entry: 4 KB)
 constexpr int TN_NCO_DEN = 256;              // the NCO's coarse table: 2^32 / 256 = 2^24 phase units per entry
-constexpr int MIX_NONE = 0, MIX_RATIONAL = 1, MIX_NCO = 2, MIX_NCO_PH = 3;
+constexpr int MIX_NONE = 0, MIX_RATIONAL = 1, MIX_NCO = 2;
 
 struct TuneCh {
     const float2* rot;      // (C_D[i], S_D[i]), i < D, device
-    int D, nm;              // denominator; num mod D in [0, D) (0: the capture's centre, no product)
-                            // an NCO channel: D = TN_NCO_DEN, nm = step (any value; 0: no product)
-                            // ... as k_tune_nco_ph reads it: D = ph0, the phase offset (any value), nm = step
+    union {                 // the same 8 bytes under the names of the channel's kind:
+        struct { int D, nm; };              // rational: denominator; num mod D in [0, D) (0: the capture's centre, no product)
+        struct { unsigned ph0; int step; }; // NCO: phase offset and step, any values (both 0: no product)
+    };
 };
+static_assert(sizeof(TuneCh) == 16, "the record is 16 bytes for either kind");
 struct TuneArgs {
     RsArgs r;               // the resampler's, for ONE input row (ch_stride unused); y_stride = distance of the K output rows
     const TuneCh* ch;       // [K]
@@ -1701,7 +1701,10 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
         xb = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(a.x) + (size_t)fmt_bps(FMT) * row * a.ch_stride);
     }
     float2* yb = reinterpret_cast<float2*>(a.y) + (size_t)row * a.y_stride;
-    const unsigned D = (unsigned)c.D, nm = (unsigned)c.nm;          // (MIX only, as everything that names them)
+    // D: the denominator (MIX_RATIONAL only); inc: what a sample adds to the rotator's index (num mod D) or to the phase (step)
+    unsigned D = 0, inc = 0, ph0 = 0;
+    if constexpr (MIX == MIX_RATIONAL) { D = (unsigned)c.D; inc = (unsigned)c.nm; }
+    if constexpr (MIX == MIX_NCO) { ph0 = c.ph0; inc = (unsigned)c.step; }
     const float* lut = nullptr;
     if constexpr (LUTM) {
         __shared__ float LUT[256];
@@ -1713,15 +1716,14 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
     int mode = 0;                                                   // uniform: no product / table in LDS / table gathered / NCO
     if constexpr (MIX == MIX_RATIONAL) {
         float2* const rot = reinterpret_cast<float2*>(RS_HT + ta->rot_off);
-        mode = nm == 0 ? 0 : (D <= (unsigned)TN_ROT_LDS_DEN ? 1 : 2);
+        mode = inc == 0 ? 0 : (D <= (unsigned)TN_ROT_LDS_DEN ? 1 : 2);
         if (mode == 1)
             for (unsigned k = tid; k < D; k += WV) rot[k] = c.rot[k];
         ROT = rot;
     }
-    if constexpr (MIX == MIX_NCO || MIX == MIX_NCO_PH) {
+    if constexpr (MIX == MIX_NCO) {
         float2* const rot = reinterpret_cast<float2*>(RS_HT + ta->rot_off);
-        if constexpr (MIX == MIX_NCO_PH) mode = (nm | D) == 0 ? 0 : 3;   // (D is ph0 here)
-        else mode = nm == 0 ? 0 : 3;
+        mode = (inc | ph0) == 0 ? 0 : 3;
         if (mode == 3)
             for (int k = tid; k < TN_NCO_DEN; k += WV) rot[k] = c.rot[k];
         ROT = rot;
@@ -1739,15 +1741,14 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
         // (position of the window's first sample) mod D: the one 64-bit reduction; it follows the window in 32 bits
         const long rb64 = ((long)ta->abs_first + (nt - (T - 1))) % (long)D;
         rb = (unsigned)(rb64 < 0 ? rb64 + (long)D : rb64);
-        il = (nm * (unsigned)(SPV * tid)) % D;                      // this lane's index offset inside a vector row
-        sv = (nm * (unsigned)(SPV * WV)) % D;                       // ... and from one of its vectors to the next
+        il = (inc * (unsigned)(SPV * tid)) % D;                     // this lane's index offset inside a vector row
+        sv = (inc * (unsigned)(SPV * WV)) % D;                      // ... and from one of its vectors to the next
     }
-    if constexpr (MIX == MIX_NCO || MIX == MIX_NCO_PH) {
-        // rb is the PHASE of the window's first sample, step * position mod 2^32: the one product; it follows the window by adds
-        rb = nm * (unsigned)((long)ta->abs_first + (nt - (T - 1)));
-        if constexpr (MIX == MIX_NCO_PH) rb += D;                   // ... plus the channel's offset ph0
-        il = nm * (unsigned)(SPV * tid);
-        sv = nm * (unsigned)(SPV * WV);
+    if constexpr (MIX == MIX_NCO) {
+        // rb is the PHASE of the window's first sample, ph0 + step * position mod 2^32: the one product; it follows the window by adds
+        rb = ph0 + inc * (unsigned)((long)ta->abs_first + (nt - (T - 1)));
+        il = inc * (unsigned)(SPV * tid);
+        sv = inc * (unsigned)(SPV * WV);
     }
 
     uint4 v[NV];
@@ -1770,18 +1771,18 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
     // MODE: 0 no product (the resampler, and a channel at the capture's centre) / 1 rotator in LDS / 2 rotator gathered / 3 NCO
     auto stage = [&](long base, auto mc) {
         constexpr int MODE = decltype(mc)::value;
-        static_assert(MODE == 0 || (MIX == MIX_RATIONAL && MODE <= 2) || ((MIX == MIX_NCO || MIX == MIX_NCO_PH) && MODE == 3),
+        static_assert(MODE == 0 || (MIX == MIX_RATIONAL && MODE <= 2) || (MIX == MIX_NCO && MODE == 3),
                       "only the tuner mixes");
         const long v0 = base >> LS;
         const int sh = (int)(base - (v0 << LS));                    // 0 .. SPV - 1
         const bool interior = (v0 << LS) >= -a.n_hist && (v0 << LS) + (long)SPV * NV * WV <= a.n_new;   // uniform
         unsigned iv = 0;
-        if constexpr (MODE == 3) iv = rb - nm * (unsigned)sh + il;  // phase of this lane's first element (it sits sh before the window)
+        if constexpr (MODE == 3) iv = rb - inc * (unsigned)sh + il; // phase of this lane's first element (it sits sh before the window)
         else if constexpr (MODE != 0) {
             // rotator index of this lane's first element: sample (v0 << LS) + SPV tid sits at position rb - sh (mod D; D may be below sh)
             const unsigned shd = (unsigned)sh % D;
             const unsigned r0 = rb >= shd ? rb - shd : rb + D - shd;
-            iv = (nm * r0) % D + il;
+            iv = (inc * r0) % D + il;
             iv = iv >= D ? iv - D : iv;
         }
 #pragma unroll
@@ -1794,11 +1795,11 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
                 if constexpr (MODE == 3) {
                     const float2 cs = nco_factor(ie, ROT);
                     s2 = make_float2(__builtin_fmaf(s2.y, cs.y, s2.x * cs.x), __builtin_fmaf(-s2.x, cs.y, s2.y * cs.x));
-                    ie += nm;
+                    ie += inc;
                 } else if constexpr (MODE != 0) {
                     const float2 cs = MODE == 1 ? ROT[ie] : c.rot[ie];
                     s2 = make_float2(__builtin_fmaf(s2.y, cs.y, s2.x * cs.x), __builtin_fmaf(-s2.x, cs.y, s2.y * cs.x));
-                    ie += nm;
+                    ie += inc;
                     ie = ie >= D ? ie - D : ie;
                 }
                 if (!interior) {
@@ -1838,7 +1839,7 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
         if (m0 >= a.n_out) break;                                   // uniform
         if constexpr (MIX == MIX_NONE) stage(nt - (T - 1), icst<0>{});
         else if (mode == 0) stage(nt - (T - 1), icst<0>{});
-        else if constexpr (MIX == MIX_NCO || MIX == MIX_NCO_PH) stage(nt - (T - 1), icst<3>{});
+        else if constexpr (MIX == MIX_NCO) stage(nt - (T - 1), icst<3>{});
         else if (mode == 1) stage(nt - (T - 1), icst<1>{});
         else stage(nt - (T - 1), icst<2>{});
         phase_sync();
@@ -1866,7 +1867,7 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
         out_m0 = m0;
         nt = nt_next; pt = pt_next;
         if constexpr (MIX == MIX_RATIONAL) rb = (rb + dn % D) % D;
-        if constexpr (MIX == MIX_NCO || MIX == MIX_NCO_PH) rb += nm * dn;
+        if constexpr (MIX == MIX_NCO) rb += inc * dn;
         phase_sync();                                               // every lane's window reads precede the next staging
     }
     flush();
@@ -1877,13 +1878,11 @@ template <int FMT, bool LUTM>
 __global__ __launch_bounds__(WV, RS_WPS) void k_tune(TuneArgs ta, WideConv cv) { resample_body<FMT, LUTM, MIX_RATIONAL>(ta.r, &ta, cv); }
 template <int FMT, bool LUTM>
 __global__ __launch_bounds__(WV, RS_WPS) void k_tune_nco(TuneArgs ta, WideConv cv) { resample_body<FMT, LUTM, MIX_NCO>(ta.r, &ta, cv); }
-template <int FMT, bool LUTM>
-__global__ __launch_bounds__(WV, RS_WPS) void k_tune_nco_ph(TuneArgs ta, WideConv cv) { resample_body<FMT, LUTM, MIX_NCO_PH>(ta.r, &ta, cv); }
 // One NCO channel's record (step, ph0) rewritten in stream order: launches issued before it on the stream have read the old one,
 // launches after it read the new one (p25fe_afc_set_step)
 __global__ void k_afc_set_ch(TuneCh* ch, int step, unsigned ph0)
 {
-    if (threadIdx.x == 0 && blockIdx.x == 0) { ch->nm = step; ch->D = (int)ph0; }
+    if (threadIdx.x == 0 && blockIdx.x == 0) { ch->step = step; ch->ph0 = ph0; }
 }
 
 // ------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""AFC on the GPU (docs/SPEC.md 3.0e: k_tune_nco_ph and p25fe_afc_set_step; 3.0f: k_afc_measure), through the C ABI, bit for bit
+"""AFC on the GPU (docs/SPEC.md 3.0e: k_tune_nco's ph0 and p25fe_afc_set_step; 3.0f: k_afc_measure), through the C ABI, bit for bit
 against tests/afc_model.py.
 
 Retune: a fresh object IS 3.0d; after p25fe_afc_set_step every range equals the model with the channel's new (step, ph0), the
@@ -76,7 +76,7 @@ def test_retune(mods, rot, ratio, fmt):
         tn = TN.nco(fe, L, M, T, taps, STEPS)
         params = [(st, 0) for st in STEPS]
         assert [tn.get_step(k) for k in range(K)] == params
-        # a fresh object is 3.0d (it launches k_tune_nco)
+        # a fresh object is 3.0d (every ph0 is 0)
         y, no = tn.tune_dev(tx[:hist + n1], n_hist=hist, abs0=P - n1, offset=hist)
         ref = model_range(rot, x[:hist + n1], hist, P - n1, L, M, T, taps, params)
         check_rows(y, no, ref, ("fresh", P))
@@ -118,6 +118,55 @@ def test_retune(mods, rot, ratio, fmt):
         g, no = tn.tune_dev(tx[:o2 + n_small], n_hist=T - 1, abs0=P, offset=o2)
         check_rows(g, no, model_range(rot, x[o2 - (T - 1):o2 + n_small], T - 1, P, L, M, T, taps, [(st, 0) for st in STEPS]), ("back", P))
         tn.close()
+
+
+def test_retune_one_channel_of_several(mods, rot):
+    """p25fe_afc_set_step on ONE channel leaves the others as p25fe_nco_create made them, ph0 = 0 on the device as on the host.
+    24/25 with T = 9, K = 3 at steps (232387521, -3527459, 0), cf32, P = 5000 and 2^32 + 77: range 1 = [P - 104, P) on a fresh
+    object, set_step(1, 1234567, P) alone, range 2 = 880 samples from P with n_hist = T - 1 into rows with guard bands.  Channel 1
+    equals the model with its new (step, ph0), channels 0 and 2 the model with (step, 0), channel 2 the resampler's output of the
+    same range, all bit for bit, and get_step says the same.  Then the host form: p25fe_tune with K = 2, p25fe_afc_set_step with a
+    null stream on channel 0, channel 1 (step 0) untouched."""
+    import torch
+    from p25rx_amd.frontend import Resampler
+    _lib, FE, TN, _ = mods
+    L, M, T, n1, n2 = 24, 25, 9, 104, 880
+    steps, hist, sentinel = (OFF_A, OFF_B, 0), 96, -123456.75
+    K, o2 = len(steps), hist + n1
+    rng = np.random.default_rng(47)
+    taps, x = rand_taps(rng, L, T), cnoise(rng, o2 + n2)
+    tx = dev(x)
+    fe = FE()
+    rs = Resampler(fe, L, M, T, taps)
+    for P in (5000, (1 << 32) + 77):
+        tn = TN.nco(fe, L, M, T, taps, steps)
+        params = [(st, 0) for st in steps]
+        y, no = tn.tune_dev(tx[:o2], n_hist=hist, abs0=P - n1, offset=hist)
+        check_rows(y, no, model_range(rot, x[:o2], hist, P - n1, L, M, T, taps, params), ("fresh", P))
+        tn.set_step(1, 1234567, P)
+        params[1] = AM.set_step(*params[1], 1234567, P)
+        assert params[1][1] != 0 and [tn.get_step(k) for k in range(K)] == params
+        cnt = RM.n_resample(L, M, P, n2)
+        out = torch.full((K, cnt + 38, 2), sentinel, device="cuda")
+        g, no = tn.tune_dev(tx, n_hist=T - 1, abs0=P, offset=o2, out=out)
+        assert no == cnt and cnt > 800 and bool((out[:, cnt:] == sentinel).all()), P
+        check_rows(out, cnt, model_range(rot, x[o2 - (T - 1):], T - 1, P, L, M, T, taps, params), ("one retuned", P))
+        r, nr = rs.resample_dev(tx, n_hist=T - 1, abs0=P, offset=o2)
+        assert nr == cnt and np.array_equal(bits(host(out, cnt, 2)), bits(host(r, nr, 0))), P
+        tn.close()
+    # the host form, from position 0: the chunks are [0, n1) and [n1, n1 + n2)
+    xs = x[:n1 + n2]
+    tn = TN.nco(fe, L, M, T, taps, [OFF_A, 0])
+    a = tn.tune(xs[:n1])
+    assert np.array_equal(bits(a), bits(model_range(rot, xs[:n1], 0, 0, L, M, T, taps, [(OFF_A, 0), (0, 0)])))
+    assert fe.L.p25fe_afc_set_step(tn.tn, 0, 1234567, n1, None) == _lib.OK
+    params = [AM.set_step(OFF_A, 0, 1234567, n1), (0, 0)]
+    assert params[0][1] != 0 and [tn.get_step(k) for k in range(2)] == params
+    b = tn.tune(xs[n1:])
+    assert b.shape[1] == RM.n_resample(L, M, n1, n2)
+    assert np.array_equal(bits(b), bits(model_range(rot, xs[n1 - (T - 1):], T - 1, n1, L, M, T, taps, params)))
+    rs.resample(xs[:n1])
+    assert np.array_equal(bits(b[1]), bits(rs.resample(xs[n1:])))
 
 
 def test_retune_host_streaming_and_refusals(mods, rot):
