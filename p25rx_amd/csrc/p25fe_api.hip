@@ -12,6 +12,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <new>
 #include <utility>
@@ -95,6 +96,7 @@ struct Arena {
         off += round_up(count * sizeof(T), 64);
         return r;
     }
+    template <class T> T* take(size_t count) { T* dev; return take<T>(count, &dev); }     // ... for what only the host side names
 };
 
 // Kernel launch with optional events ATTACHED TO THE DISPATCH (hipExtLaunchKernelGGL): the start / stop events are
@@ -196,6 +198,10 @@ struct StreamState {
     }
     bool format_refused(int fmt) const { return fmt_locked >= 0 && fmt_locked != fmt && abs_iq > 0; }
     size_t n_hist() const { return abs_iq < SHARD_HALO ? (size_t)abs_iq : SHARD_HALO; }   // valid samples of the history
+    void stage_hist(int fmt, char* rows, size_t row_bytes) const     // the history in front of staged input: channel c's to rows + c * row_bytes
+    {
+        for (size_t c = 0; c < anchor.size(); ++c) memcpy(rows + c * row_bytes, hist_iq.data() + c * SHARD_HALO * 8, SHARD_HALO * fmt_bytes(fmt));
+    }
     // n new samples per channel have been consumed (channel c's at fresh + c * row_bytes): the last SHARD_HALO samples of
     // [history | new] become the history
     void commit_iq(size_t C, int fmt, size_t n, const char* fresh, size_t row_bytes)
@@ -208,6 +214,12 @@ struct StreamState {
             else { memmove(hist, hist + n * eb, (SHARD_HALO - n) * eb); memcpy(hist + (SHARD_HALO - n) * eb, src, n * eb); }
         }
         fmt_locked = fmt; abs_iq += n;
+    }
+    // the receiver has consumed n_bb baseband samples: channel c stands at res[c].anchor_out and gave n_dibits[c] dibits (null: res[c].n_dibits)
+    void commit_recv(const p25fe_result_t* res, const uint64_t* n_dibits, size_t n_bb)
+    {
+        for (size_t c = 0; c < anchor.size(); ++c) { anchor[c] = res[c].anchor_out; total_dibits[c] += n_dibits ? n_dibits[c] : res[c].n_dibits; }
+        abs_bb += n_bb;
     }
     // Channel c's baseband tail for a later p25fe_slice after a call that produced nb samples: the newest BBPAD.  `fresh` [TAILN] is what
     // k_tail_extract read from the planes, which hold HIST_BB + look samples in front of the call's first; what is older (a very short chunk)
@@ -294,18 +306,26 @@ struct Prof {
     }
 };
 
-// p25fe_run_host_windows: two device windows, dibit rows and result records in a ring, the copy streams and their events
+// p25fe_run_host_windows: window k uses device window and dibit rows k % WIN_PARITY, result records and events k % WIN_RING
+constexpr size_t WIN_PARITY = 2, WIN_RING = 4;
+struct WinSlot {                           // what window k's events mark, each on the stream that records it
+    hipEvent_t h2d_begin = nullptr, h2d_end = nullptr;     // copy stream: around the window's host-to-device copy
+    hipEvent_t comp_begin = nullptr, comp_end = nullptr;   // compute stream: around its kernels
+    hipEvent_t on_host = nullptr;                          // result stream: its records and dibit rows are in pinned memory
+    std::array<hipEvent_t*, 5> all() { return {&h2d_begin, &h2d_end, &comp_begin, &comp_end, &on_host}; }
+};
 struct Windows {
-    DevBuf buf[2], dib[2], res, anc;
-    PinBuf stage[2], out;
-    hipStream_t cs = nullptr, os = nullptr;
-    hipEvent_t ev[4][5] = {};              // per ring slot: H2D begin / end, compute begin / end, results on the host
+    DevBuf buf[WIN_PARITY], dib[WIN_PARITY], res, anc;
+    PinBuf stage[WIN_PARITY], out;
+    hipStream_t cs = nullptr, os = nullptr;                // the copy stream, the result stream (compute: the handle's)
+    WinSlot slot[WIN_RING];
+    WinSlot& of(size_t k) { return slot[k % WIN_RING]; }
     hipError_t ensure()                    // the streams and events, once
     {
         if (cs) return hipSuccess;
         hipError_t e = hipStreamCreateWithFlags(&cs, hipStreamNonBlocking);
         if (e == hipSuccess) e = hipStreamCreateWithFlags(&os, hipStreamNonBlocking);
-        for (auto& slot : ev) for (hipEvent_t& x : slot) if (e == hipSuccess) e = hipEventCreate(&x);
+        for (WinSlot& s : slot) for (hipEvent_t* x : s.all()) if (e == hipSuccess) e = hipEventCreate(x);
         return e;
     }
 };
@@ -790,7 +810,7 @@ void p25fe_destroy(p25fe_t* h)
     for (hipStream_t st : {h->stream, h->rx_stream, h->win.cs, h->win.os})
         if (st) { (void)hipStreamSynchronize(st); (void)hipStreamDestroy(st); }
     if (h->jit_mod) (void)hipModuleUnload(h->jit_mod);
-    for (auto& slot : h->win.ev) for (hipEvent_t e : slot) if (e) (void)hipEventDestroy(e);
+    for (WinSlot& s : h->win.slot) for (hipEvent_t* e : s.all()) if (*e) (void)hipEventDestroy(*e);
     for (Lane& l : h->lanes)
         for (hipEvent_t e : {l.ev_k1, l.ev_rx}) if (e) (void)hipEventDestroy(e);
     for (auto& e : h->prof.ev) if (e) (void)hipEventDestroy(e);
@@ -2385,34 +2405,21 @@ int p25fe_shard_compact_from_dev(p25fe_t* h, const uint8_t* d_gathered, size_t c
 // launches + ONE synchronisation, and for a chunk of at most one tile (the reference's 16 384-sample buffer gives
 // 3 276 / 3 277 baseband samples) ONE launch: k_chunk / k_recv_chunk.
 // --------------------------------------------------------------------------------------------
-// [history | new] per channel in h->hin; returns the staging geometry
-struct Staged { size_t stride, n_hist; char* host; const char* dev; };
+// [history | new] per channel in h->hin: the host view of the new samples (rows row_bytes apart), K1 on them from the stream's position on
+struct Staged { char* fresh; size_t row_bytes; K1Launch k1; };
 static int stage_iq(p25fe_t* h, const void* iq, int fmt, size_t n, Staged* s)
 {
     if (h->state.format_refused(fmt)) return P25FE_ERR_FORMAT;
     const size_t C = (size_t)h->C, eb = fmt_bytes(fmt);
-    s->stride = SHARD_HALO + round_up(n, 8) + 8;                     // samples, multiple of 8: owned sample 0 stays 16-B aligned
-    HIPCHK(h, h->hin.ensure(C * s->stride * eb));
-    s->host = static_cast<char*>(h->hin.p);
-    s->dev = static_cast<const char*>(h->hin.dp);
-    s->n_hist = h->state.n_hist();
-    for (size_t c = 0; c < C; ++c) {
-        char* row = s->host + c * s->stride * eb;
-        memcpy(row, h->state.hist_iq.data() + c * SHARD_HALO * 8, SHARD_HALO * eb);
-        if (n) memcpy(row + SHARD_HALO * eb, static_cast<const char*>(iq) + c * n * eb, n * eb);
-    }
+    const size_t stride = SHARD_HALO + round_up(n, 8) + 8;           // samples, multiple of 8: owned sample 0 stays 16-B aligned
+    HIPCHK(h, h->hin.ensure(C * stride * eb));
+    s->fresh = static_cast<char*>(h->hin.p) + SHARD_HALO * eb; s->row_bytes = stride * eb;
+    h->state.stage_hist(fmt, static_cast<char*>(h->hin.p), s->row_bytes);
+    for (size_t c = 0; c < C && n; ++c) memcpy(s->fresh + c * s->row_bytes, static_cast<const char*>(iq) + c * n * eb, n * eb);
+    K1Launch& k = s->k1;
+    k.src = static_cast<const char*>(h->hin.dp) + SHARD_HALO * eb; k.fmt = fmt; k.ch_stride = stride; k.n_hist = h->state.n_hist(); k.n = n;
+    k.abs0 = h->state.abs_iq; k.stream = h->stream;
     return P25FE_OK;
-}
-// the call succeeded: the stream moves on behind the staged samples
-static void commit_iq(p25fe_t* h, int fmt, size_t n, const Staged& s) { h->state.commit_iq((size_t)h->C, fmt, n, s.host + SHARD_HALO * fmt_bytes(fmt), s.stride * fmt_bytes(fmt)); }
-
-// K1 on the staged chunk, from the stream's position on
-static K1Launch staged_k1(const p25fe_t* h, int fmt, size_t n, const Staged& s)
-{
-    K1Launch k;
-    k.src = s.dev + SHARD_HALO * fmt_bytes(fmt); k.fmt = fmt; k.ch_stride = s.stride; k.n_hist = s.n_hist; k.n = n; k.abs0 = h->state.abs_iq;
-    k.stream = h->stream;
-    return k;
 }
 
 static int demod_host(p25fe_t* h, const void* iq, int fmt, size_t n, float* bb, size_t bb_cap, size_t* n_out,
@@ -2425,22 +2432,20 @@ static int demod_host(p25fe_t* h, const void* iq, int fmt, size_t n, float* bb, 
     if (nb > bb_cap) return P25FE_ERR_CAPACITY;
     const size_t C = (size_t)h->C;
     Staged sg;
-    int rc = stage_iq(h, iq, fmt, n, &sg);
-    if (rc) return rc;
+    if (int rc = stage_iq(h, iq, fmt, n, &sg)) return rc;
     const size_t bb_stride = round_up(nb + 4, 4);
     HIPCHK(h, h->hout.ensure(C * bb_stride * sizeof(float) + 64 * (C + 2)));
     Arena ar(h->hout);
     float *d_bb, *d_pw;
     float* h_bb = ar.take<float>(C * bb_stride, &d_bb);
     float* h_pw = ar.take<float>(C, &d_pw);
-    K1Launch k = staged_k1(h, fmt, n, sg);
+    K1Launch k = sg.k1;
     k.bb = d_bb; k.bb_stride = bb_stride; k.power_dbm = power_dbm ? d_pw : nullptr;
-    rc = launch_k1(h, k);
-    if (rc) return rc;
+    if (int rc = launch_k1(h, k)) return rc;
     HIPCHK(h, hipStreamSynchronize(h->stream));
     for (size_t c = 0; c < C; ++c) memcpy(bb + c * bb_cap, h_bb + c * bb_stride, nb * sizeof(float));
     if (power_dbm) memcpy(power_dbm, h_pw, sizeof(float) * C);
-    commit_iq(h, fmt, n, sg);
+    h->state.commit_iq(C, fmt, n, sg.fresh, sg.row_bytes);           // the call succeeded: the stream moves on behind the staged samples
     *n_out = nb;
     return P25FE_OK;
 }
@@ -2464,6 +2469,8 @@ int p25fe_demod_s16(p25fe_t* h, const int16_t* iq, size_t n_samples, float* bb, 
     return demod_host(h, iq, P25FE_FMT_S16, n_samples, bb, bb_cap, n_out, power_dbm);
 }
 
+// hard ceiling of the dibits of n_bb baseband samples, as a row size: detections, hence re-anchors, are at least W + 1 samples apart
+static inline size_t dibit_row(size_t n_bb, size_t align) { return round_up(n_bb / (W + 1) + 2, align); }
 // Pinned outputs of one receiver call: per channel a result record, the carry-in anchor, a dibit row and (optionally) the
 // sync event rows; plus the baseband tail the fused path hands back.
 struct RecvOut {
@@ -2479,8 +2486,7 @@ struct RecvOut {
 static int recv_out(p25fe_t* h, size_t n_bb, size_t sync_cap, RecvOut* o)
 {
     const size_t C = (size_t)h->C;
-    o->dstride = round_up(n_bb / (W + 1) + 2, 16);                   // hard ceiling: detections, hence re-anchors, are at least W + 1 samples apart
-    o->sstride = sync_cap;
+    o->dstride = dibit_row(n_bb, 16); o->sstride = sync_cap;
     const size_t bytes = C * (sizeof(p25fe_result_t) + sizeof(p25fe_anchor_t) + o->dstride + 16 * sync_cap + TAILN * sizeof(float) + 4) + 64 * 8;
     HIPCHK(h, h->hout.ensure(bytes));
     Arena ar(h->hout);
@@ -2492,31 +2498,8 @@ static int recv_out(p25fe_t* h, size_t n_bb, size_t sync_cap, RecvOut* o)
     o->tail = ar.take<float>(C * TAILN, &o->d_tail);
     o->done = ar.take<unsigned>(C, &o->d_done);
     memcpy(o->anc, h->state.anchor.data(), sizeof(p25fe_anchor_t) * C);
-    return P25FE_OK;
+    return ensure_slice_scratch(h, n_bb);                           // ... and the scratch set the call's kernels work in
 }
-// after the synchronisation: capacity check, copy-out, receiver state
-static int recv_finish(p25fe_t* h, const RecvOut& o, size_t n_bb, uint8_t* dibits, size_t cap, size_t* n_dibits, int64_t* sync_pos,
-                       uint64_t* sync_dibit, size_t sync_cap, size_t* n_sync)
-{
-    const size_t C = (size_t)h->C;
-    for (size_t c = 0; c < C; ++c)
-        if (o.res[c].n_dibits > cap) return P25FE_ERR_CAPACITY;      // before any state moves: the call can be repeated with more room
-    for (size_t c = 0; c < C; ++c) {
-        const p25fe_result_t& r = o.res[c];
-        memcpy(dibits + c * cap, o.dib + c * o.dstride, (size_t)r.n_dibits);
-        const size_t ns = r.n_sync < sync_cap ? (size_t)r.n_sync : sync_cap;
-        if (ns && sync_pos) memcpy(sync_pos + c * sync_cap, o.spos + c * o.sstride, ns * sizeof(int64_t));
-        if (sync_dibit)
-            for (size_t k = 0; k < ns; ++k) sync_dibit[c * sync_cap + k] = o.sdib[c * o.sstride + k] + h->state.total_dibits[c];
-        n_dibits[c] = (size_t)r.n_dibits;
-        if (n_sync) n_sync[c] = (size_t)r.n_sync;
-        h->state.anchor[c] = r.anchor_out;
-        h->state.total_dibits[c] += r.n_dibits;
-    }
-    h->state.abs_bb += n_bb;
-    return P25FE_OK;
-}
-
 // the receive side of a host-buffer call: n_bb samples behind the stream's position, the pinned outputs
 static RecvCall host_recv_call(const p25fe_t* h, const RecvOut& o, size_t n_bb, bool want_sync)
 {
@@ -2563,6 +2546,39 @@ static int chunk_wait(p25fe_t* h, const RecvOut& o, const ChunkRecvArgs& c)
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return P25FE_OK;
 }
+// the end of a call whose kernels are out (`polled`: the arguments they got): wait, capacity check, copy-out, receiver state
+static int recv_finish(p25fe_t* h, const RecvOut& o, const ChunkRecvArgs& polled, size_t n_bb, uint8_t* dibits, size_t cap, size_t* n_dibits,
+                       int64_t* sync_pos, uint64_t* sync_dibit, size_t sync_cap, size_t* n_sync)
+{
+    const size_t C = (size_t)h->C;
+    if (int rc = chunk_wait(h, o, polled)) return rc;
+    for (size_t c = 0; c < C; ++c)
+        if (o.res[c].n_dibits > cap) return P25FE_ERR_CAPACITY;      // before any state moves: the call can be repeated with more room
+    for (size_t c = 0; c < C; ++c) {
+        const p25fe_result_t& r = o.res[c];
+        memcpy(dibits + c * cap, o.dib + c * o.dstride, (size_t)r.n_dibits);
+        const size_t ns = r.n_sync < sync_cap ? (size_t)r.n_sync : sync_cap;
+        if (ns && sync_pos) memcpy(sync_pos + c * sync_cap, o.spos + c * o.sstride, ns * sizeof(int64_t));
+        if (sync_dibit)
+            for (size_t k = 0; k < ns; ++k) sync_dibit[c * sync_cap + k] = o.sdib[c * o.sstride + k] + h->state.total_dibits[c];
+        n_dibits[c] = (size_t)r.n_dibits;
+        if (n_sync) n_sync[c] = (size_t)r.n_sync;
+    }
+    h->state.commit_recv(o.res, nullptr, n_bb);
+    return P25FE_OK;
+}
+
+// p25fe_slice, p25fe_run_* and p25fe_run_host_windows each keep their own checks in front (arguments, format, device, capacity, the empty
+// call) in their own order: which refusal wins is part of the interface.  Once none applies, the call takes the scratch set:
+static int recv_begin(p25fe_t* h) { h->sh.invalidate(); return pipe_join(h, h->stream); }
+// ... and an IQ call that succeeded consumes the lock-drop list, moves the stream behind the n samples per channel at `fresh` (rows
+// row_bytes apart) and keeps the tail of its last n_bb baseband samples (`tail` [C][TAILN], from k_tail_extract)
+static void run_commit(p25fe_t* h, int fmt, size_t n, const char* fresh, size_t row_bytes, size_t n_bb, const float* tail)
+{
+    h->rs_n = 0;
+    h->state.commit_iq((size_t)h->C, fmt, n, fresh, row_bytes);
+    for (size_t c = 0; c < (size_t)h->C; ++c) h->state.merge_tail(c, n_bb, h->look, tail + c * TAILN);
+}
 
 int p25fe_slice(p25fe_t* h, const float* bb, size_t n, uint8_t* dibits, size_t cap, size_t* n_dibits, int64_t* sync_pos,
                 uint64_t* sync_dibit, size_t sync_cap, size_t* n_sync)
@@ -2574,8 +2590,7 @@ int p25fe_slice(p25fe_t* h, const float* bb, size_t n, uint8_t* dibits, size_t c
     const size_t C = (size_t)h->C;
     if (n == 0) { for (size_t c = 0; c < C; ++c) { n_dibits[c] = 0; if (n_sync) n_sync[c] = 0; } return P25FE_OK; }
     if (cap < n / SPS + 1) return P25FE_ERR_CAPACITY;               // worst case of an undisturbed lock, checked before any state moves
-    h->sh.invalidate();
-    if (int jrc = pipe_join(h, h->stream)) return jrc;
+    if (int jrc = recv_begin(h)) return jrc;
     // stage [tail | new] per channel
     const size_t bb_stride = round_up(BBPAD + n + 4, 4);
     HIPCHK(h, h->hbb.ensure(C * bb_stride * sizeof(float)));
@@ -2586,34 +2601,25 @@ int p25fe_slice(p25fe_t* h, const float* bb, size_t n, uint8_t* dibits, size_t c
         memcpy(hb + c * bb_stride + BBPAD, bb + c * n, n * sizeof(float));
     }
     RecvOut o;
-    int rc = recv_out(h, n, sync_cap, &o);
-    if (rc) return rc;
-    rc = ensure_slice_scratch(h, n);
-    if (rc) return rc;
-    ChunkRecvArgs polled;
-    polled.done = nullptr; polled.seq = 0u;
+    if (int rc = recv_out(h, n, sync_cap, &o)) return rc;
     const size_t hist = h->state.abs_bb < BBPAD ? (size_t)h->state.abs_bb : BBPAD;
     const RecvCall rcall = host_recv_call(h, o, n, sync_cap != 0);
+    RecvChunkArgs a;
+    chunk_recv_args(h, rcall, nullptr, &a.r);                       // (not polled unless armed below)
     if (!rcall.gen && n <= (size_t)TS) {
-        RecvChunkArgs a;
-        chunk_recv_args(h, rcall, nullptr, &a.r);
         chunk_poll_arm(h, o, &a.r);
-        polled = a.r;
         const PlanarGeo g(n);
         a.bb = db + BBPAD; a.bb_stride = (long)bb_stride; a.n_hist = (long)hist;
         a.f = h->rx().pl_f.get(); a.bits = h->rx().pl_bits.get(); a.n_blocks = (long)g.n_blocks;
         hipLaunchKernelGGL(k_recv_chunk, dim3((unsigned)C), dim3(WV), 0, h->stream, a);
         HIPCHK(h, hipGetLastError());
     } else {
-        rc = launch_planarize(h, db + BBPAD, bb_stride, hist, n, h->stream);
+        int rc = launch_planarize(h, db + BBPAD, bb_stride, hist, n, h->stream);
         if (!rc) rc = launch_recv(h, rcall);
         if (rc) return rc;
     }
-    rc = chunk_wait(h, o, polled);
-    if (rc) return rc;
-    rc = recv_finish(h, o, n, dibits, cap, n_dibits, sync_pos, sync_dibit, sync_cap, n_sync);
-    if (rc) return rc;                                               // (P25FE_ERR_CAPACITY: nothing has moved, the lock-drop list included -- repeat the call)
-    h->rs_n = 0;
+    if (int rc = recv_finish(h, o, a.r, n, dibits, cap, n_dibits, sync_pos, sync_dibit, sync_cap, n_sync)) return rc;
+    h->rs_n = 0;                                                     // (after P25FE_ERR_CAPACITY nothing has moved, this list included -- repeat the call)
     for (size_t c = 0; c < C; ++c)                                   // the tail: last BBPAD samples of [tail | new]
         memcpy(h->state.tail_bb.data() + c * BBPAD, hb + c * bb_stride + n, BBPAD * sizeof(float));
     return P25FE_OK;
@@ -2627,45 +2633,33 @@ static int run_host(p25fe_t* h, const void* iq, int fmt, size_t n, uint8_t* dibi
     const size_t C = (size_t)h->C;
     const size_t nb = p25fe_n_baseband_h(h, h->state.abs_iq, n);
     if (cap < nb / SPS + 1) return P25FE_ERR_CAPACITY;              // worst case of an undisturbed lock, checked before any state moves
-    h->sh.invalidate();
-    if (int jrc = pipe_join(h, h->stream)) return jrc;
+    if (int jrc = recv_begin(h)) return jrc;
     Staged sg;
-    int rc = stage_iq(h, iq, fmt, n, &sg);
-    if (rc) return rc;
+    if (int rc = stage_iq(h, iq, fmt, n, &sg)) return rc;
     if (nb == 0) {                                                  // fewer than five new samples: only the filters' history moves
-        commit_iq(h, fmt, n, sg);
+        h->state.commit_iq(C, fmt, n, sg.fresh, sg.row_bytes);
         for (size_t c = 0; c < C; ++c) n_dibits[c] = 0;
         return P25FE_OK;
     }
     RecvOut o;
-    rc = recv_out(h, nb, 0, &o);
-    if (rc) return rc;
-    rc = ensure_slice_scratch(h, nb);
-    if (rc) return rc;
+    if (int rc = recv_out(h, nb, 0, &o)) return rc;
     const RecvCall rcall = host_recv_call(h, o, nb, false);
     ChunkRecvArgs cr;
     chunk_recv_args(h, rcall, o.d_tail, &cr);
-    K1Launch k = staged_k1(h, fmt, n, sg);
+    K1Launch k = sg.k1;
     if (!rcall.gen && nb <= (size_t)TS) {
         // ONE launch: K1 (planar) + the receiver, run by each channel's last workgroup
         chunk_poll_arm(h, o, &cr);
         k.planar = true; k.chunk = &cr;
-        rc = launch_k1(h, k);
-        if (rc) return rc;
+        if (int rc = launch_k1(h, k)) return rc;
     } else {
         // the baseband stays in HBM; the receiver's history is recomputed from the IQ history, like a shard's from its halo
-        rc = launch_planar_recv(h, k, rcall);
-        if (rc) return rc;
+        if (int rc = launch_planar_recv(h, k, rcall)) return rc;
         hipLaunchKernelGGL(k_tail_extract, dim3((unsigned)C), dim3(WV), 0, h->stream, cr);
         HIPCHK(h, hipGetLastError());
     }
-    rc = chunk_wait(h, o, cr);
-    if (rc) return rc;
-    rc = recv_finish(h, o, nb, dibits, cap, n_dibits, nullptr, nullptr, 0, nullptr);
-    if (rc) return rc;
-    h->rs_n = 0;                                                     // the lock-drop list is consumed by a call that succeeded
-    commit_iq(h, fmt, n, sg);
-    for (size_t c = 0; c < C; ++c) h->state.merge_tail(c, nb, h->look, o.tail + c * TAILN);
+    if (int rc = recv_finish(h, o, cr, nb, dibits, cap, n_dibits, nullptr, nullptr, 0, nullptr)) return rc;
+    run_commit(h, fmt, n, sg.fresh, sg.row_bytes, nb, o.tail);
     return P25FE_OK;
 }
 
@@ -2688,183 +2682,189 @@ int p25fe_run_s16(p25fe_t* h, const int16_t* iq, size_t n_samples, uint8_t* dibi
 // --------------------------------------------------------------------------------------------
 // a long host capture as a pipeline of windows: H2D copy | K1..K4 | dibits D2H, each on its own stream
 // --------------------------------------------------------------------------------------------
+// The windows of one call.  A remainder of fewer than 8 samples (it may not even yield a baseband sample) rides with the window in front
+// of it: every window then produces baseband, and the tail handed to a later p25fe_slice is always the last window's.  That window is
+// up to window + 7 samples long: the + 8 of the row stride and of the worst cases.
+struct WinPlan {
+    size_t C, eb, n, window, n_win;        // channels, bytes per sample; samples of the capture and of a window (clamped); windows
+    size_t stride, nb_win, dstride;        // samples per channel row of a device window, [halo | window (+ < 8)]; worst case of a window's baseband, its dibit row
+    int fmt, phase; uint64_t abs_iq;       // (abs_iq: where the stream stands before the call)
+    WinPlan(size_t n_, size_t win, int fmt_, size_t C_, uint64_t abs_, int ph) : C(C_), eb(fmt_bytes(fmt_)), n(n_), fmt(fmt_), phase(ph), abs_iq(abs_)
+    {
+        window = (win ? win : (size_t)(64u << 20) / eb) & ~(size_t)7;    // every window's first sample stays 16-byte aligned
+        if (window < 8192) window = 8192;
+        n_win = (n + window - 1) / window;
+        if (n_win >= 2 && n - (n_win - 1) * window < 8) --n_win;
+        stride = SHARD_HALO + window + 8; nb_win = (window + 8) / DEC + 2; dstride = dibit_row(nb_win, 64);
+    }
+    size_t first(size_t k) const { return k * window; }
+    size_t len(size_t k) const { return k + 1 == n_win ? n - first(k) : window; }
+    size_t n_bb(size_t k) const { return n_baseband_ph(phase, abs_iq + first(k), len(k)); }
+    size_t n_bb_before(size_t k) const { return n_baseband_ph(phase, abs_iq, first(k)); }    // ... of all windows in front of k
+};
+// The pinned block of a call: per ring slot the result records, per parity a dibit row block, the baseband tail (the last window's
+// k_tail_extract writes it in place) and what window 0 starts from -- the carry-in anchors and the IQ history.  win_alloc carves and fills it.
+struct WinPin { p25fe_result_t* res[WIN_RING]; uint8_t* dib[WIN_PARITY]; float *tail, *d_tail; p25fe_anchor_t* anc; char* hist; };
+static int win_alloc(p25fe_t* h, const WinPlan& p, bool staged, WinPin* o)
+{
+    Windows& w = h->win;
+    const size_t C = p.C;
+    HIPCHK(h, w.ensure());
+    if (int rc = ensure_slice_scratch(h, p.nb_win)) return rc;
+    for (DevBuf& d : w.buf) HIPCHK(h, d.ensure(C * p.stride * p.eb));
+    for (DevBuf& d : w.dib) HIPCHK(h, d.ensure(C * p.dstride));
+    HIPCHK(h, w.res.ensure(WIN_RING * C * sizeof(p25fe_result_t)));
+    HIPCHK(h, w.anc.ensure(WIN_PARITY * C * sizeof(p25fe_anchor_t)));
+    HIPCHK(h, w.out.ensure(WIN_RING * round_up(C * sizeof(p25fe_result_t), 64) + WIN_PARITY * round_up(C * p.dstride, 64) +
+                           round_up(C * TAILN * sizeof(float), 64) + round_up(C * sizeof(p25fe_anchor_t), 64) + round_up(C * SHARD_HALO * p.eb, 64)));
+    Arena ar(w.out);
+    for (p25fe_result_t*& r : o->res) r = ar.take<p25fe_result_t>(C);
+    for (uint8_t*& d : o->dib) d = ar.take<uint8_t>(C * p.dstride);
+    o->tail = ar.take<float>(C * TAILN, &o->d_tail);
+    o->anc = ar.take<p25fe_anchor_t>(C);
+    o->hist = ar.take<char>(C * SHARD_HALO * p.eb);
+    if (staged) for (PinBuf& s : w.stage) HIPCHK(h, s.ensure(C * p.stride * p.eb));
+    memcpy(o->anc, h->state.anchor.data(), C * sizeof(p25fe_anchor_t));
+    h->state.stage_hist(p.fmt, o->hist, SHARD_HALO * p.eb);
+    return P25FE_OK;
+}
+// Window k on its three streams; a stage returns at its first error.  Copy stream: [halo | window] in ONE copy.  The halo of window
+// k >= 1 is simply the SHARD_HALO samples in front of it in the caller's capture (16 KB more per window); only window 0 takes it from the
+// handle's history.  (A device-to-device copy of the previous window's tail put a second operation between every two H2D copies: 7 - 9 %.)
+static int win_copy_in(p25fe_t* h, const WinPlan& p, const WinPin& o, const char* iq, bool pinned, size_t k)
+{
+    Windows& w = h->win;
+    const size_t b = k % WIN_PARITY, eb = p.eb;
+    const size_t lead = k == 0 ? 0 : SHARD_HALO;                    // samples in front of the window that travel with it
+    const size_t row = (lead + p.len(k)) * eb;
+    char* dst = w.buf[b].as<char>() + (SHARD_HALO - lead) * eb;
+    if (k >= WIN_PARITY) HIPCHK(h, hipStreamWaitEvent(w.cs, w.of(k - WIN_PARITY).comp_end, 0));       // the kernels of window k - 2 have read this device window
+    if (k == 0) HIPCHK(h, hipMemcpy2DAsync(dst - SHARD_HALO * eb, p.stride * eb, o.hist, SHARD_HALO * eb, SHARD_HALO * eb, p.C, hipMemcpyHostToDevice, w.cs));
+    const char* src = iq + (p.first(k) - lead) * eb;
+    size_t spitch = p.n * eb;
+    if (!pinned) {                                                   // pageable memory: this thread stages the rows
+        if (k >= WIN_PARITY) HIPCHK(h, hipEventSynchronize(w.of(k - WIN_PARITY).h2d_end));            // the copy engine is done with this staging window
+        char* sg = static_cast<char*>(w.stage[b].p);
+        for (size_t c = 0; c < p.C; ++c) memcpy(sg + c * row, src + c * p.n * eb, row);
+        src = sg; spitch = row;
+    }
+    HIPCHK(h, hipEventRecord(w.of(k).h2d_begin, w.cs));
+    if (p.C == 1) HIPCHK(h, hipMemcpyAsync(dst, src, row, hipMemcpyHostToDevice, w.cs));
+    else HIPCHK(h, hipMemcpy2DAsync(dst, p.stride * eb, src, spitch, row, p.C, hipMemcpyHostToDevice, w.cs));
+    HIPCHK(h, hipEventRecord(w.of(k).h2d_end, w.cs));
+    return P25FE_OK;
+}
+// Compute stream (the handle's): K1 .. K4 on the device window, the next window's carry-in anchors, behind the last window the baseband tail
+static int win_compute(p25fe_t* h, const WinPlan& p, const WinPin& o, size_t k)
+{
+    Windows& w = h->win;
+    hipStream_t st = h->stream;
+    const size_t b = k % WIN_PARITY, C = p.C;
+    p25fe_anchor_t* d_anc = w.anc.as<p25fe_anchor_t>();             // [WIN_PARITY][C]: window k finds its carry-in in row b and leaves window k + 1's in the other
+    p25fe_result_t* d_res = w.res.as<p25fe_result_t>() + k % WIN_RING * C;
+    HIPCHK(h, hipStreamWaitEvent(st, w.of(k).h2d_end, 0));
+    if (k >= WIN_PARITY) HIPCHK(h, hipStreamWaitEvent(st, w.of(k - WIN_PARITY).on_host, 0));          // window k - 2's dibit rows have left this device row block
+    if (k == 0) HIPCHK(h, hipMemcpyAsync(d_anc, o.anc, C * sizeof(p25fe_anchor_t), hipMemcpyHostToDevice, st));
+    HIPCHK(h, hipEventRecord(w.of(k).comp_begin, st));
+    K1Launch k1;
+    k1.src = w.buf[b].as<char>() + SHARD_HALO * p.eb; k1.fmt = p.fmt; k1.ch_stride = p.stride; k1.n_hist = k == 0 ? h->state.n_hist() : SHARD_HALO;
+    k1.n = p.len(k); k1.abs0 = p.abs_iq + p.first(k); k1.stream = st;
+    RecvCall rc = recv_call(h);                                      // (a pending lock-drop list holds absolute indices: every window sees it)
+    rc.range.n_bb = p.n_bb(k); rc.range.abs_bb0 = (long)(h->state.abs_bb + p.n_bb_before(k)) - h->look; rc.range.anchor_in = d_anc + b * C;
+    rc.dest.dibits = w.dib[b].as<uint8_t>(); rc.dest.dibit_stride = p.dstride; rc.dest.result = d_res; rc.stream = st;
+    if (int lrc = launch_planar_recv(h, k1, rc)) return lrc;
+    hipLaunchKernelGGL(k_anchors_from_results, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, st, d_res, d_anc + (k + 1) % WIN_PARITY * C, (int)C);
+    if (k + 1 == p.n_win) {                                          // the baseband tail for a later p25fe_slice on this handle
+        ChunkRecvArgs cr;
+        chunk_recv_args(h, rc, o.d_tail, &cr);
+        hipLaunchKernelGGL(k_tail_extract, dim3((unsigned)C), dim3(WV), 0, st, cr);
+    }
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(w.of(k).comp_end, st));
+    return P25FE_OK;
+}
+// Result stream: the window's result records and dibit rows leave for pinned memory
+static int win_copy_out(p25fe_t* h, const WinPlan& p, const WinPin& o, size_t k)
+{
+    Windows& w = h->win;
+    const size_t b = k % WIN_PARITY, q = k % WIN_RING;
+    HIPCHK(h, hipStreamWaitEvent(w.os, w.of(k).comp_end, 0));
+    HIPCHK(h, hipMemcpyAsync(o.res[q], w.res.as<p25fe_result_t>() + q * p.C, p.C * sizeof(p25fe_result_t), hipMemcpyDeviceToHost, w.os));
+    HIPCHK(h, hipMemcpyAsync(o.dib[b], w.dib[b].as<uint8_t>(), p.C * p.dstride, hipMemcpyDeviceToHost, w.os));
+    HIPCHK(h, hipEventRecord(w.of(k).on_host, w.os));
+    return P25FE_OK;
+}
+// This thread: window j's dibits are on the host, append them to the caller's rows (total: dibits per channel so far)
+static int win_drain(p25fe_t* h, const WinPlan& p, const WinPin& o, size_t j, uint8_t* dibits, size_t cap, uint64_t* total, p25fe_windows_stats_t* st)
+{
+    const WinSlot& s = h->win.of(j);
+    HIPCHK(h, hipEventSynchronize(s.on_host));
+    float t = 0.f;
+    if (hipEventElapsedTime(&t, s.h2d_begin, s.h2d_end) == hipSuccess) st->ms_h2d += t; else (void)hipGetLastError();
+    if (hipEventElapsedTime(&t, s.comp_begin, s.comp_end) == hipSuccess) st->ms_compute += t; else (void)hipGetLastError();
+    const p25fe_result_t* r = o.res[j % WIN_RING];
+    for (size_t c = 0; c < p.C; ++c) {
+        const uint64_t nd = r[c].n_dibits;
+        if (nd > p.dstride || total[c] + nd > cap) return P25FE_ERR_CAPACITY;
+        memcpy(dibits + c * cap + total[c], o.dib[j % WIN_PARITY] + c * p.dstride, (size_t)nd);
+        total[c] += nd;
+    }
+    return P25FE_OK;
+}
+
 int p25fe_run_host_windows(p25fe_t* h, const void* iq, int fmt, size_t n, size_t window, uint8_t* dibits, size_t cap,
                            size_t* n_dibits, p25fe_windows_stats_t* stats)
 {
+    // ---- guard
     if (!h || (!iq && n) || !dibits || !n_dibits || piecewise_refused(h)) return P25FE_ERR_ARG;
     if (int frc = format_unusable(h, fmt)) return frc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (h->state.format_refused(fmt)) return P25FE_ERR_FORMAT;
-    const size_t C = (size_t)h->C, eb = fmt_bytes(fmt);
-    if (window == 0) window = (size_t)(64u << 20) / eb;
-    window &= ~(size_t)7;                                           // every window's first sample stays 16-byte aligned
-    if (window < 8192) window = 8192;
-    const size_t nb_total = p25fe_n_baseband_h(h, h->state.abs_iq, n);
-    if (cap < nb_total / SPS + 1) return P25FE_ERR_CAPACITY;        // worst case of an undisturbed lock, before any state moves
+    const size_t C = (size_t)h->C;
+    const WinPlan p(n, window, fmt, C, h->state.abs_iq, h->phase);
+    const size_t nb_all = p25fe_n_baseband_h(h, h->state.abs_iq, n);
+    if (cap < nb_all / SPS + 1) return P25FE_ERR_CAPACITY;          // worst case of an undisturbed lock, before any state moves
     if (stats) memset(stats, 0, sizeof *stats);
     for (size_t c = 0; c < C; ++c) n_dibits[c] = 0;
     if (n == 0) return P25FE_OK;
-    if (n <= window && n <= (size_t)(1u << 20)) {                   // one small window: the streaming call does the same with less set-up
-        const int rc1 = run_host(h, iq, fmt, n, dibits, cap, n_dibits);
-        if (stats) { stats->n_windows = 1; }
-        return rc1;
+    if (n <= p.window && n <= (size_t)(1u << 20)) {                 // one small window: the streaming call does the same with less set-up
+        if (stats) stats->n_windows = 1;
+        return run_host(h, iq, fmt, n, dibits, cap, n_dibits);
     }
-    h->sh.invalidate();
-    if (int jrc = pipe_join(h, h->stream)) return jrc;
+    if (int jrc = recv_begin(h)) return jrc;
     const auto t_begin = std::chrono::steady_clock::now();
-    constexpr int R = 4;
-    HIPCHK(h, h->win.ensure());
-    hipStream_t st = h->stream, cs = h->win.cs, os = h->win.os;
-    // A remainder of fewer than 8 samples (it may not even yield a baseband sample) rides with the window in front of it -- every
-    // window of the pipeline then produces baseband, and the tail handed to a later p25fe_slice is always the last window's.
-    size_t n_win = (n + window - 1) / window;
-    const size_t rem = n - (n_win - 1) * window;                    // samples of the last window, 1 .. window
-    const bool fold = n_win >= 2 && rem < 8;
-    if (fold) --n_win;
-    // (the last window is then `window + rem` samples long: the + 8 of the strides below)
-    const size_t stride = SHARD_HALO + window + 8;                  // samples per channel row of a device window: [halo | window (+ < 8)]
-    const size_t nb_win = (window + 8) / DEC + 2;
-    const size_t dstride = round_up(nb_win / (W + 1) + 2, 64);      // hard ceiling of a window's dibits (p25fe_slice's rule)
-    int rc = ensure_slice_scratch(h, nb_win);
-    if (rc) return rc;
-    for (int b = 0; b < 2; ++b) {
-        HIPCHK(h, h->win.buf[b].ensure(C * stride * eb));
-        HIPCHK(h, h->win.dib[b].ensure(C * dstride));
-    }
-    HIPCHK(h, h->win.res.ensure((size_t)R * C * sizeof(p25fe_result_t)));
-    HIPCHK(h, h->win.anc.ensure(2 * C * sizeof(p25fe_anchor_t)));
-    // pinned: per ring slot the result records, per parity a dibit row block, the baseband tail, the carry-in anchors, the history
-    const size_t out_bytes = (size_t)R * round_up(C * sizeof(p25fe_result_t), 64) + 2 * round_up(C * dstride, 64) +
-                             round_up(C * TAILN * sizeof(float), 64) + round_up(C * sizeof(p25fe_anchor_t), 64) + round_up(C * SHARD_HALO * eb, 64);
-    HIPCHK(h, h->win.out.ensure(out_bytes));
-    Arena ar(h->win.out);
-    p25fe_result_t *h_res[R], *dv_unused_r;
-    for (int q = 0; q < R; ++q) h_res[q] = ar.take<p25fe_result_t>(C, &dv_unused_r);
-    uint8_t *h_dib[2], *dv_unused_b;
-    for (int b = 0; b < 2; ++b) h_dib[b] = ar.take<uint8_t>(C * dstride, &dv_unused_b);
-    float *d_tail, *h_tail = ar.take<float>(C * TAILN, &d_tail);
-    p25fe_anchor_t *dv_unused_a, *h_anc = ar.take<p25fe_anchor_t>(C, &dv_unused_a);
-    char *dv_unused_h, *h_hist = ar.take<char>(C * SHARD_HALO * eb, &dv_unused_h);
-    // is the caller's memory pinned?  (then the copy engine reads it directly; otherwise this thread stages it)
+    // ---- allocate.  Is the caller's memory pinned?  (then the copy engine reads it directly; otherwise this thread stages it)
     bool pinned = false;
-    {
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, iq) == hipSuccess) pinned = at.type == hipMemoryTypeHost;
-        else (void)hipGetLastError();
-    }
-    if (!pinned)
-        for (int b = 0; b < 2; ++b) HIPCHK(h, h->win.stage[b].ensure(C * (SHARD_HALO + window + 8) * eb));
-    memcpy(h_anc, h->state.anchor.data(), C * sizeof(p25fe_anchor_t));
-    for (size_t c = 0; c < C; ++c) memcpy(h_hist + c * SHARD_HALO * eb, h->state.hist_iq.data() + c * SHARD_HALO * 8, SHARD_HALO * eb);
-    p25fe_anchor_t* d_anc = h->win.anc.as<p25fe_anchor_t>();        // [2][C]: the carry-in of window k lives in half k & 1
-    RecvCall rcall = recv_call(h);                                   // (a pending lock-drop list holds absolute indices: every window sees it)
-    rcall.dest.dibit_stride = dstride; rcall.stream = st;
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, iq) == hipSuccess) pinned = at.type == hipMemoryTypeHost; else (void)hipGetLastError();
+    WinPin pin;
+    if (int arc = win_alloc(h, p, !pinned, &pin)) return arc;
     std::vector<uint64_t> total(C, 0);
-    double ms_h2d = 0.0, ms_comp = 0.0;
+    p25fe_windows_stats_t st = {};
+    // ---- the pipeline (an error must not return at once: copies that read the caller's capture are in flight)
     int status = P25FE_OK;
-    auto drain = [&](size_t j) -> int {                              // window j's dibits are on the host: append them
-        hipEvent_t* ev = h->win.ev[j % R];
-        HIPCHK(h, hipEventSynchronize(ev[4]));
-        float t = 0.f;
-        if (hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) ms_h2d += t; else (void)hipGetLastError();
-        if (hipEventElapsedTime(&t, ev[2], ev[3]) == hipSuccess) ms_comp += t; else (void)hipGetLastError();
-        const p25fe_result_t* r = h_res[j % R];
-        for (size_t c = 0; c < C; ++c) {
-            const uint64_t nd = r[c].n_dibits;
-            if (nd > dstride || total[c] + nd > cap) return P25FE_ERR_CAPACITY;
-            memcpy(dibits + c * cap + total[c], h_dib[j & 1] + c * dstride, (size_t)nd);
-            total[c] += nd;
-        }
-        return P25FE_OK;
-    };
-    size_t nb_done = 0;
-// (inside the window loop an error must not return at once: copies that read the caller's capture are in flight)
-#define WINCHK(expr) if (const hipError_t e__ = (expr); e__ != hipSuccess) { h->last_hip = (int)e__; status = P25FE_ERR_HIP; break; } else (void)0
-    for (size_t k = 0; k < n_win && status == P25FE_OK; ++k) {
-        const size_t off = k * window, wn = k + 1 == n_win ? n - off : window;
-        const uint64_t abs0 = h->state.abs_iq + off;
-        const size_t n_hist = k == 0 ? h->state.n_hist() : SHARD_HALO;
-        const int b = (int)(k & 1);
-        hipEvent_t* ev = h->win.ev[k % R];
-        char* dev = h->win.buf[b].as<char>();
-        // ---- copy stream: [halo | window] in ONE copy.  The halo of window k >= 1 is simply the SHARD_HALO samples in front of
-        // it in the caller's capture (16 KB more per window); only window 0 takes it from the handle's history.  (A device-to-
-        // device copy of the previous window's tail put a second operation between every two H2D copies: 7 - 9 % of the call.)
-        if (k >= 2) { WINCHK(hipStreamWaitEvent(cs, h->win.ev[(k - 2) % R][3], 0)); }      // the kernels of window k - 2 have read this buffer
-        const size_t lead = k == 0 ? 0 : SHARD_HALO;                // samples in front of the window that travel with it
-        if (k == 0) { WINCHK(hipMemcpy2DAsync(dev, stride * eb, h_hist, SHARD_HALO * eb, SHARD_HALO * eb, C, hipMemcpyHostToDevice, cs)); }
-        const char* src = static_cast<const char*>(iq) + (off - lead) * eb;
-        size_t spitch = n * eb;
-        if (!pinned) {
-            if (k >= 2) { WINCHK(hipEventSynchronize(h->win.ev[(k - 2) % R][1])); }       // the copy engine is done with this staging window
-            char* sg = static_cast<char*>(h->win.stage[b].p);
-            for (size_t c = 0; c < C; ++c) memcpy(sg + c * (lead + wn) * eb, src + c * n * eb, (lead + wn) * eb);
-            src = sg; spitch = (lead + wn) * eb;
-        }
-        char* dst = dev + (SHARD_HALO - lead) * eb;
-        WINCHK(hipEventRecord(ev[0], cs));
-        if (C == 1) { WINCHK(hipMemcpyAsync(dst, src, (lead + wn) * eb, hipMemcpyHostToDevice, cs)); }
-        else { WINCHK(hipMemcpy2DAsync(dst, stride * eb, src, spitch, (lead + wn) * eb, C, hipMemcpyHostToDevice, cs)); }
-        WINCHK(hipEventRecord(ev[1], cs));
-        // ---- compute stream
-        WINCHK(hipStreamWaitEvent(st, ev[1], 0));
-        if (k >= 2) { WINCHK(hipStreamWaitEvent(st, h->win.ev[(k - 2) % R][4], 0)); }      // window k - 2's dibit rows have left this device row block
-        if (k == 0) { WINCHK(hipMemcpyAsync(d_anc, h_anc, C * sizeof(p25fe_anchor_t), hipMemcpyHostToDevice, st)); }
-        WINCHK(hipEventRecord(ev[2], st));
-        const size_t nb = p25fe_n_baseband_h(h, abs0, wn);
-        p25fe_result_t* d_res = h->win.res.as<p25fe_result_t>() + (k % R) * C;
-        uint8_t* d_dib = h->win.dib[b].as<uint8_t>();
-        const PlanarGeo g(nb ? nb : 1);
-        K1Launch k1;
-        k1.src = dev + SHARD_HALO * eb; k1.fmt = fmt; k1.ch_stride = stride; k1.n_hist = n_hist; k1.n = wn; k1.abs0 = abs0; k1.stream = st;
-        rcall.range.n_bb = nb; rcall.range.abs_bb0 = (long)(h->state.abs_bb + nb_done) - h->look; rcall.range.anchor_in = d_anc + (size_t)b * C;
-        rcall.dest.dibits = d_dib; rcall.dest.result = d_res;
-        rc = launch_planar_recv(h, k1, rcall);
-        if (rc) { status = rc; break; }
-        hipLaunchKernelGGL(k_anchors_from_results, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, st, d_res, d_anc + (size_t)(b ^ 1) * C, (int)C);
-        if (k + 1 == n_win && nb) {                                  // the baseband tail for a later p25fe_slice on this handle
-            ChunkRecvArgs cr;
-            memset(&cr, 0, sizeof cr);
-            cr.pl = planar_view(h, g); cr.n = (long)nb; cr.look = (int)h->look; cr.tail = d_tail;
-            hipLaunchKernelGGL(k_tail_extract, dim3((unsigned)C), dim3(WV), 0, st, cr);
-        }
-        WINCHK(hipGetLastError());
-        WINCHK(hipEventRecord(ev[3], st));
-        // ---- results leave on their own stream
-        WINCHK(hipStreamWaitEvent(os, ev[3], 0));
-        WINCHK(hipMemcpyAsync(h_res[k % R], d_res, C * sizeof(p25fe_result_t), hipMemcpyDeviceToHost, os));
-        WINCHK(hipMemcpyAsync(h_dib[b], d_dib, C * dstride, hipMemcpyDeviceToHost, os));
-        WINCHK(hipEventRecord(ev[4], os));
-        nb_done += nb;
-        if (k >= 1) status = drain(k - 1);
+    for (size_t k = 0; k < p.n_win && status == P25FE_OK; ++k) {
+        status = win_copy_in(h, p, pin, static_cast<const char*>(iq), pinned, k);
+        if (status == P25FE_OK) status = win_compute(h, p, pin, k);
+        if (status == P25FE_OK) status = win_copy_out(h, p, pin, k);
+        if (status == P25FE_OK && k >= 1) status = win_drain(h, p, pin, k - 1, dibits, cap, total.data(), &st);
     }
-#undef WINCHK
-    if (status == P25FE_OK) status = drain(n_win - 1);
+    if (status == P25FE_OK) status = win_drain(h, p, pin, p.n_win - 1, dibits, cap, total.data(), &st);
     if (status != P25FE_OK) {
         // Nothing of the handle's STREAM STATE has moved (history, anchors, counters: the call can be repeated), and no copy or
         // kernel of this call is still in flight when it returns: they read the caller's capture and the handle's windows.
         // The caller's dibit buffer may already hold the dibits of earlier windows and n_dibits reads 0: treat both as undefined.
-        (void)hipStreamSynchronize(cs); (void)hipStreamSynchronize(st); (void)hipStreamSynchronize(os);
+        (void)hipStreamSynchronize(h->win.cs); (void)hipStreamSynchronize(h->stream); (void)hipStreamSynchronize(h->win.os);
         return status;
     }
-    HIPCHK(h, hipStreamSynchronize(st));
-    h->rs_n = 0;                                                     // a pending lock-drop list is consumed by a call that succeeded
-    // ---- the handle's stream state after the capture
-    const p25fe_result_t* last = h_res[(n_win - 1) % R];
-    const size_t nb_last = p25fe_n_baseband_h(h, h->state.abs_iq + (n_win - 1) * window, n - (n_win - 1) * window);   // (> 0: a window is at least 8 192 samples)
-    for (size_t c = 0; c < C; ++c) {
-        n_dibits[c] = (size_t)total[c];
-        h->state.anchor[c] = last[c].anchor_out;
-        h->state.total_dibits[c] += total[c];
-        if (nb_last) h->state.merge_tail(c, nb_last, h->look, h_tail + c * TAILN);
-    }
-    h->state.commit_iq(C, fmt, n, static_cast<const char*>(iq), n * eb);
-    h->state.abs_bb += nb_done;
-    if (stats) {
-        stats->n_windows = n_win;
-        stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
-        stats->ms_h2d = ms_h2d; stats->ms_compute = ms_comp; stats->pinned_input = pinned ? 1 : 0;
-    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    // ---- commit
+    for (size_t c = 0; c < C; ++c) n_dibits[c] = (size_t)total[c];
+    h->state.commit_recv(pin.res[(p.n_win - 1) % WIN_RING], total.data(), nb_all);
+    run_commit(h, fmt, n, static_cast<const char*>(iq), n * p.eb, p.n_bb(p.n_win - 1), pin.tail);
+    st.n_windows = p.n_win; st.pinned_input = pinned ? 1 : 0;
+    st.ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count();
+    if (stats) *stats = st;
     return P25FE_OK;
 }
 

@@ -749,3 +749,65 @@ def test_cpp_replay_bulk_mode_fails_cleanly(tmp_path):
     assert r.returncode == 1 and "write error" in r.stderr, (r.returncode, r.stderr[-500:])
     r = subprocess.run([exe, "-W", "256k", "cf32", str(src), str(tmp_path / "no_such_dir" / "x")], capture_output=True, text=True, timeout=100)
     assert r.returncode == 1 and "unable to open" in r.stderr, (r.returncode, r.stderr[-500:])
+
+
+# ---- p25fe_run_host_windows at the minimum window: nine windows, so the buffer parity is reused from window 2 on, the four-slot
+# event ring is gone round twice, and the 3-sample remainder rides with the last window
+RING_WINDOW = 8192
+RING_N = 9 * RING_WINDOW + 3
+_ring = {}
+
+
+def _ring_capture():
+    """two 0.4 s captures (seeds 61, 62) and the oracle's one pass over their first RING_N samples, cf32 and u8; computed once"""
+    if not _ring:
+        from oracle import oracle as O
+        from p25rx_amd import c4fm
+        full = np.stack([c4fm.synth(0.4, seed=s, snr_db=20.0, frame_dibits=600)[0] for s in (61, 62)])
+        x = np.ascontiguousarray(full[:, :RING_N])
+        u8 = np.stack([c4fm.to_u8(r) for r in x])
+        _ring.update(full=full, cf32=x, u8=u8, ref_cf32=[O.run_cf32(r) for r in x],
+                     ref_u8=[O.Recv().feed(O.Demod().feed_u8(r))[0] for r in u8], ref_full=O.run_cf32(full[0]))
+        assert [len(r) for r in _ring["ref_cf32"]] == [1444, 1444]
+    return _ring
+
+
+@pytest.mark.parametrize("fmt", ["cf32", "u8"])
+@pytest.mark.parametrize("pinned", [False, True])
+@pytest.mark.parametrize("n_ch", [1, 2])
+def test_host_windows_ring_corners(n_ch, pinned, fmt):
+    """nine windows of 8 192 samples: one and two channels, pageable (staged by the host thread) and pinned (read by the copy
+    engine) input, cf32 and u8 -- the dibits are the oracle's one pass, and the stats say what ran"""
+    import torch
+    from p25rx_amd.frontend import FrontEnd
+    cap = _ring_capture()
+    x = cap[fmt][:n_ch]
+    x = x.view(np.float32).reshape(n_ch, -1, 2) if fmt == "cf32" else x
+    fe = FrontEnd(n_channels=n_ch)
+    got, st = fe.run_host_windows(torch.from_numpy(x).pin_memory() if pinned else x, window=RING_WINDOW)
+    got = [got] if n_ch == 1 else got
+    for c in range(n_ch):
+        assert np.array_equal(got[c], cap["ref_" + fmt][c]), c
+    assert st["n_windows"] == 9 and st["pinned_input"] == pinned
+
+
+@pytest.mark.parametrize("n_ch", [1, 2])
+def test_host_windows_leave_the_stream_state_of_one_call(n_ch):
+    """whichever call consumed the capture -- nine windows or one p25fe_run_cf32 -- the handle's exported state is the same,
+    byte for byte: positions, IQ history, baseband tail, anchors, totals"""
+    from p25rx_amd.frontend import FrontEnd
+    x = _ring_capture()["cf32"][:n_ch]
+    a, b = FrontEnd(n_channels=n_ch), FrontEnd(n_channels=n_ch)
+    a.run_host_windows(x, window=RING_WINDOW)
+    b.run_cf32(x)
+    assert np.array_equal(a.state_export(), b.state_export())
+
+
+def test_host_windows_continue_after_the_fold():
+    """nine windows with the folded remainder, then the rest of the capture through p25fe_run_cf32: together the oracle's one pass"""
+    from p25rx_amd.frontend import FrontEnd
+    cap = _ring_capture()
+    fe = FrontEnd()
+    d1, st = fe.run_host_windows(cap["cf32"][0], window=RING_WINDOW)
+    d2 = fe.run_cf32(cap["full"][0, RING_N:])
+    assert st["n_windows"] == 9 and np.array_equal(np.concatenate([d1, d2]), cap["ref_full"])
