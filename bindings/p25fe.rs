@@ -275,6 +275,10 @@ extern "C" {
     pub fn p25fe_shard_pipe_end(h: *mut Handle, last_stream: *mut c_void) -> c_int;
     pub fn p25fe_rx_stream(h: *mut Handle, rx_stream: *mut *mut c_void) -> c_int;
     pub fn p25fe_shard_head_check(h: *mut Handle) -> c_int;
+    /// diagnostic: the planar baseband and sign words of the handle's most recent scratch-using call (include/p25fe.h)
+    pub fn p25fe_debug_planes_size(h: *const Handle, n_bb: usize, n_floats: *mut usize, n_words: *mut usize) -> c_int;
+    pub fn p25fe_debug_planes_dev(h: *mut Handle, n_bb: usize, d_f: *mut f32, f_stride: usize, d_bits: *mut u32, bits_stride: usize,
+                                  stream: *mut c_void) -> c_int;
     pub fn p25fe_shard_pass1_k1(h: *mut Handle, d_iq: *const c_void, fmt: c_int, ch_stride: usize, n_hist: usize, n: usize,
                                 abs0: u64, stream: *mut c_void) -> c_int;
     pub fn p25fe_streams_share_queue(h: *mut Handle, stream_a: *mut c_void, stream_b: *mut c_void, shared: *mut c_int) -> c_int;

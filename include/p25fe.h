@@ -631,6 +631,19 @@ int p25fe_shard_pipe_end(p25fe_t *h, void *last_stream);
  * (p25fe_streams_share_queue; libp25fe_rccl.so's p25fe_shard_create / p25fe_shard_prepare do) */
 int p25fe_rx_stream(p25fe_t *h, void **rx_stream);
 
+/* DIAGNOSTIC (tests/test_gpu_planes.py; no receiver needs it, additive: the ABI version stays): the blocked polyphase baseband and its
+ * sign words that the most recent scratch-using call on the handle wrote (K1 of the fused calls, the planarising kernels of
+ * p25fe_slice_dev / p25fe_slice) or read (a shard's later passes), copied device to device on `stream`, channel c's floats to
+ * d_f + c * f_stride and its words to d_bits + c * bits_stride.  The layout is the one described at PLPAD / planar_index in
+ * p25rx_amd/csrc/p25fe_kernels.hip: sample m of the call's range sits at position p = m + 320 + look (look: 0 with the fixed clock,
+ * P25FE_CLK_LOOKAHEAD with the tracking ones), plane p % 10, symbol i = p / 10; its float at (i / 32) * 320 + (p % 10) * 32 + i % 32,
+ * its raw sign bit at bit i % 32 of word (i / 32) * 10 + p % 10.  n_bb is the call's baseband length per channel (0 counts as 1); _size
+ * gives the floats and words per channel it stands for.  P25FE_ERR_ARG: null pointers, no such call yet, a length whose geometry is not
+ * the one that call sized the scratch for, strides below _size's figures.  The copy is ordered on `stream` only: give it the stream of
+ * the call (the host-pointer calls have finished when they return); which scratch set that call used is remembered by the handle. */
+int p25fe_debug_planes_size(const p25fe_t *h, size_t n_bb, size_t *n_floats, size_t *n_words);
+int p25fe_debug_planes_dev(p25fe_t *h, size_t n_bb, float *d_f, size_t f_stride, uint32_t *d_bits, size_t bits_stride, void *stream);
+
 /* Host-side combine: summaries[r] for r = 0..n_shards-1 in time order (one channel) ->
  * anchor_in[r] (n_shards entries) and dibit_offset[r] (n_shards + 1 entries: shard r's dibits occupy
  * [dibit_offset[r], dibit_offset[r + 1]) of the whole stream, the last entry is the total).

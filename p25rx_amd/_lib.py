@@ -88,6 +88,7 @@ SYMBOLS = [
     "p25fe_nco_step", "p25fe_nco_factor", "p25fe_nco_create",
     "p25fe_afc_set_step", "p25fe_afc_get_step", "p25fe_afc_factor", "p25fe_afc_design", "p25fe_afc_create", "p25fe_afc_destroy",
     "p25fe_afc_measure_dev", "p25fe_afc_hz",
+    "p25fe_debug_planes_size", "p25fe_debug_planes_dev",
 ]
 
 
@@ -164,6 +165,8 @@ def load():
     L.p25fe_shard_head_check.argtypes = [C.c_void_p]
     L.p25fe_rx_stream.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.p25fe_shard_pipe_end.argtypes = [vp, vp]
+    L.p25fe_debug_planes_size.argtypes = [vp, sz, psz, psz]
+    L.p25fe_debug_planes_dev.argtypes = [vp, sz, vp, sz, vp, sz, vp]
     L.p25fe_shard_pass1_k1.argtypes = [vp, vp, C.c_int, sz, sz, sz, u64, vp]
     L.p25fe_streams_share_queue.argtypes = [vp, vp, vp, C.POINTER(C.c_int)]
     L.p25fe_shard_pass2_dev.argtypes = [vp, vp, vp, vp, sz, sz, vp, vp, vp, sz, vp, vp, vp]

@@ -370,6 +370,7 @@ struct p25fe {
     const long* rs_idx = nullptr; size_t rs_n = 0, rs_stride = 0;    // lock drops for the next receiver-running call (p25fe_resync_at_dev); consumed by it
     Lane lanes[MAX_LANES];
     int cur = 0, lane_q[MAX_LANES - 1] = {1, 2, 3};    // the current set's id, the others' in the order they come up (rotate_lanes)
+    int pl_lane = -1; size_t pl_blocks = 0;            // the set whose planes the most recent call sized, and their blocks per channel (p25fe_debug_planes_dev)
     Lane& lane() { return lanes[cur]; }
     RxScratch& rx() { return lanes[cur].s; }
     const RxScratch& rx() const { return lanes[cur].s; }
@@ -1040,6 +1041,7 @@ static int ensure_slice_scratch(p25fe_t* h, size_t n_bb)
         HIPCHK(h, s.gsum.ensure(nt)); HIPCHK(h, s.gouts.ensure(nt)); HIPCHK(h, s.evg.ensure(nt * EVCAP));
         HIPCHK(h, s.gsg.ensure(ng)); HIPCHK(h, s.gpg.ensure(ng));
     }
+    h->pl_lane = h->cur; h->pl_blocks = g.n_blocks;                  // what p25fe_debug_planes_dev reads back
     return P25FE_OK;
 }
 
@@ -2007,6 +2009,34 @@ int p25fe_join_dev(p25fe_t* h, void* stream)
     if (!h) return P25FE_ERR_ARG;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     return pipe_join(h, (hipStream_t)stream);
+}
+
+int p25fe_debug_planes_size(const p25fe_t* h, size_t n_bb, size_t* n_floats, size_t* n_words)
+{
+    if (!h || !n_floats || !n_words || n_bb > MAX_RANGE_BB) return P25FE_ERR_ARG;
+    const PlanarGeo g(n_bb);
+    *n_floats = g.floats(); *n_words = g.words();
+    return P25FE_OK;
+}
+
+// The planes stay where they are: a device-to-device copy per channel out of the set the last call sized (which a pipelined call has
+// moved on to BEFORE it sized it; the set is remembered by id all the same, so that nothing here depends on when `cur` moves).
+int p25fe_debug_planes_dev(p25fe_t* h, size_t n_bb, float* d_f, size_t f_stride, uint32_t* d_bits, size_t bits_stride, void* stream)
+{
+    if (!h || !d_f || !d_bits || n_bb > MAX_RANGE_BB || h->pl_lane < 0) return P25FE_ERR_ARG;
+    const PlanarGeo g(n_bb);
+    const size_t C = (size_t)h->C;
+    const RxScratch& s = h->lanes[h->pl_lane].s;
+    if (g.n_blocks != h->pl_blocks || f_stride < g.floats() || bits_stride < g.words()) return P25FE_ERR_ARG;
+    if (!s.pl_f.get() || !s.pl_bits.get() || s.pl_f.buf.cap < C * g.floats() * sizeof(float) || s.pl_bits.buf.cap < C * g.words() * sizeof(uint32_t))
+        return P25FE_ERR_ARG;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t st = (hipStream_t)stream;
+    for (size_t c = 0; c < C; ++c) {
+        HIPCHK(h, hipMemcpyAsync(d_f + c * f_stride, s.pl_f.get() + c * g.floats(), g.floats() * sizeof(float), hipMemcpyDeviceToDevice, st));
+        HIPCHK(h, hipMemcpyAsync(d_bits + c * bits_stride, s.pl_bits.get() + c * g.words(), g.words() * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+    }
+    return P25FE_OK;
 }
 
 static int ensure_rx_stream(p25fe_t* h)

@@ -259,6 +259,20 @@ class FrontEnd:
         self._chk(self.L.p25fe_join_dev(self.h, self._stream()))
         self._inflight = ()
 
+    def debug_planes(self, n_bb):
+        """Diagnostic (p25fe_debug_planes_dev): the planar baseband and the sign words of the most recent scratch-using call, whose
+        baseband length per channel was n_bb -> (float32 [C, n_floats], int32 [C, n_words]: the words' bits) device tensors, copied
+        on the current stream.  Layout: PLPAD / planar_index in csrc/p25fe_kernels.hip."""
+        import torch
+        nf, nw = C.c_size_t(0), C.c_size_t(0)
+        self._chk(self.L.p25fe_debug_planes_size(self.h, int(n_bb), C.byref(nf), C.byref(nw)))
+        dev = "cuda:%d" % self.device
+        f = torch.empty((self.C, nf.value), dtype=torch.float32, device=dev)
+        w = torch.empty((self.C, nw.value), dtype=torch.int32, device=dev)
+        self._chk(self.L.p25fe_debug_planes_dev(self.h, int(n_bb), C.c_void_p(f.data_ptr()), f.stride(0), C.c_void_p(w.data_ptr()),
+                                                w.stride(0), self._stream()))
+        return f, w
+
     def demod_dev(self, iq, n_hist=0, abs0=0, bb=None, want_power=False, offset=0):
         """stages 1-5 on a device range; `offset` = index of the first owned sample inside `iq` (>= n_hist)."""
         import torch

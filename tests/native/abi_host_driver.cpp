@@ -72,6 +72,13 @@ int main()
     size_t nn = 0;
     EXPECT(p25fe_state_size(nullptr, &nn) == P25FE_ERR_ARG && p25fe_run_u8(nullptr, nullptr, 3, nullptr, 0, nullptr) == P25FE_ERR_ARG);
     EXPECT(p25fe_resync_at_dev(nullptr, nullptr, 0, 0) == P25FE_ERR_ARG && p25fe_join_dev(nullptr, nullptr) == P25FE_ERR_ARG);
+    {   // the diagnostic read-out of the planes: no handle, no copy, nothing written
+        size_t nf = 7, nw = 8;
+        float ff[4] = {1.f, 1.f, 1.f, 1.f};
+        uint32_t ww[4] = {1u, 1u, 1u, 1u};
+        EXPECT(p25fe_debug_planes_size(nullptr, 100, &nf, &nw) == P25FE_ERR_ARG && nf == 7 && nw == 8);
+        EXPECT(p25fe_debug_planes_dev(nullptr, 100, ff, 4, ww, 4, nullptr) == P25FE_ERR_ARG && ff[0] == 1.f && ww[3] == 1u);
+    }
     p25fe_destroy(nullptr);
     // shard resolve: pure host logic, both clocks
     {
