@@ -49,7 +49,66 @@ private:
     p25fe_t* h_ = nullptr;
 };
 
-// one chunk through stages 1-5, by the chunk's sample type: uint8_t pairs (the reference's reader) or int16_t pairs (P25FE_FMT_S16)
+// What an integrator creates from a handle, owned the same way: the C pointer, destroyed with the object, move-only, get().  An
+// empty owner (default-constructed or moved from) holds null, which every *_destroy accepts.  Declare them after their Handle:
+// they are used only while it lives.
+template <class T, void (*Destroy)(T*)> class Owned {
+public:
+    Owned() = default;
+    ~Owned() { Destroy(p_); }
+    Owned(Owned&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    Owned& operator=(Owned&& o) noexcept
+    {
+        if (this != &o) { Destroy(p_); p_ = o.p_; o.p_ = nullptr; }
+        return *this;
+    }
+    T* get() const { return p_; }
+
+protected:
+    T* p_ = nullptr;
+};
+
+// the rational resampler (p25fe_resampler_create)
+class Resampler : public Owned<p25fe_resampler_t, p25fe_resampler_destroy> {
+public:
+    Resampler() = default;
+    Resampler(Handle& h, int32_t L, int32_t M, int32_t T, const float* taps)
+    {
+        expect(p25fe_resampler_create(h.get(), L, M, T, taps, &p_), "unable to create the resampler");
+    }
+};
+
+// the tuner: one C type, made with rational channels (p25fe_tuner_create) or with NCO channels (p25fe_nco_create)
+class Tuner : public Owned<p25fe_tuner_t, p25fe_tuner_destroy> {
+public:
+    Tuner() = default;
+    static Tuner rational(Handle& h, int32_t L, int32_t M, int32_t T, const float* taps, int32_t n_out_channels, const int32_t* num,
+                          const int32_t* den)
+    {
+        Tuner t;
+        expect(p25fe_tuner_create(h.get(), L, M, T, taps, n_out_channels, num, den, &t.p_), "unable to create the tuner");
+        return t;
+    }
+    static Tuner nco(Handle& h, int32_t L, int32_t M, int32_t T, const float* taps, int32_t n_out_channels, const int32_t* step)
+    {
+        Tuner t;
+        expect(p25fe_nco_create(h.get(), L, M, T, taps, n_out_channels, step, &t.p_), "unable to create the tuner");
+        return t;
+    }
+};
+
+// the frequency measure (p25fe_afc_create)
+class FreqMeasure : public Owned<p25fe_afc_t, p25fe_afc_destroy> {
+public:
+    FreqMeasure() = default;
+    FreqMeasure(Handle& h, int32_t D, int32_t T, const float* taps, int32_t K)
+    {
+        expect(p25fe_afc_create(h.get(), D, T, taps, K, &p_), "unable to create the frequency measure");
+    }
+};
+
+// one chunk through stages 1-5, by the chunk's sample type: uint8_t pairs (the reference's reader), int16_t pairs (P25FE_FMT_S16)
+// or float pairs (cf32)
 inline int demod_chunk(p25fe_t* h, const std::vector<uint8_t>& iq, float* bb, size_t cap, size_t* n_out, float* power)
 {
     return p25fe_demod_u8(h, iq.data(), iq.size(), bb, cap, n_out, power);
@@ -58,12 +117,16 @@ inline int demod_chunk(p25fe_t* h, const std::vector<int16_t>& iq, float* bb, si
 {
     return p25fe_demod_s16(h, iq.data(), iq.size() / 2, bb, cap, n_out, power);
 }
+inline int demod_chunk(p25fe_t* h, const std::vector<float>& iq, float* bb, size_t cap, size_t* n_out, float* power)
+{
+    return p25fe_demod_cf32(h, iq.data(), iq.size() / 2, bb, cap, n_out, power);
+}
 
 struct HubEvent { float signal_power_dbm; };                         // HubEvent::UpdateSignalPower, src/hub.rs:455
 struct StatsEvent { uint64_t dibits, syncs; };                       // HubEvent::UpdateStats (src/recv.rs:162-165): what exists of Stats here
 struct Baseband { std::vector<float> samples; };                     // RecvEvent::Baseband, src/recv.rs:25
 
-// demod::DemodTask (src/demod.rs:25-120).  Sample: what the reader's chunks hold -- uint8_t (the reference) or int16_t.
+// demod::DemodTask (src/demod.rs:25-120).  Sample: what the reader's chunks hold -- uint8_t (the reference), int16_t or float.
 template <class Reader, class Hub, class Chan, class Sample = uint8_t> class DemodTask {
 public:
     DemodTask(Handle& h, Reader& reader, Hub& hub, Chan& chan) : h_(h), reader_(reader), hub_(hub), chan_(chan) {}

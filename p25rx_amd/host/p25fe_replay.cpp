@@ -49,10 +49,12 @@
 #include <chrono>
 #include <cinttypes>
 #include <condition_variable>
+#include <cstdarg>
 #include <cstring>
 #include <deque>
 #include <fstream>
 #include <mutex>
+#include <optional>
 #include <thread>
 
 #include <hip/hip_runtime_api.h>
@@ -78,6 +80,7 @@ struct Hub {
     FILE* js = nullptr;
     size_t n_power = 0;
     size_t n_stats = 0;
+    ~Hub() { if (js) std::fclose(js); }
     void send(HubEvent e)
     {
         ++n_power;
@@ -117,22 +120,83 @@ static int usage(const char* argv0)
     return 2;
 }
 
-// bulk mode: reader thread -> two pinned blocks -> p25fe_run_host_windows
-static int bulk(Handle& h, const std::string& mode, std::ifstream& in, const char* out_path, size_t window_bytes)
+// an error that ends the run with a message and status 1 (the library's own abort in `expect`): thrown, so that the owners let go
+struct Exit { int status; };
+[[noreturn]] __attribute__((format(printf, 1, 2))) static void fail(const char* fmt, ...)
 {
-    const int fmt = mode == "u8" ? P25FE_FMT_U8 : (mode == "s16" ? P25FE_FMT_S16 : P25FE_FMT_CF32);
-    const size_t eb = fmt == P25FE_FMT_U8 ? 2 : (fmt == P25FE_FMT_S16 ? 4 : 8);
-    const size_t window = window_bytes / eb / 8 * 8;
+    va_list ap;
+    va_start(ap, fmt); std::vfprintf(stderr, fmt, ap); va_end(ap);
+    throw Exit{1};
+}
+
+struct Options {
+    const char *in_path = nullptr, *out_path = nullptr, *wpath = nullptr, *jpath = nullptr;
+    size_t batch = 64, window_bytes = 0;                              // window_bytes != 0: bulk mode
+    unsigned long rate_hz = 0;                                        // -r; 0: the capture is at 240 ksps
+    struct { enum { NONE, RATIONAL, NCO } kind = NONE; long long hz = 0; double nco_hz = 0.0; } offset;   // -f: hz; -F: nco_hz
+    double afc_ms = 0.0;                                              // -a: measure the first MS ms at -F's offset, correct once
+    bool bb = false;                                                  // the mode: 48 kHz baseband, or ...
+    int fmt = 0; size_t bps = 0;                                      // ... IQ in this format (P25FE_FMT_*) of this many bytes per sample
+};
+
+// argv -> Options; false: a usage error (all of them are decided here, before anything is opened or created)
+static bool parse(int argc, char** argv, Options& o)
+{
+    bool f = false, F = false;                                        // -f and -F exclude each other
+    const auto number = [](const char* s, double& v) { char* end = nullptr; v = std::strtod(s, &end); return end != s && *end == '\0'; };
+    int a = 1;
+    for (; a < argc && argv[a][0] == '-' && argv[a][1] != '\0'; a += 2) {
+        if (a + 1 >= argc) return false;
+        const std::string opt = argv[a];
+        const char* val = argv[a + 1];
+        if (opt == "-w") o.wpath = val;
+        else if (opt == "-j") o.jpath = val;
+        else if (opt == "-b") o.batch = (size_t)std::strtoull(val, nullptr, 10);
+        else if (opt == "-r") { if ((o.rate_hz = std::strtoul(val, nullptr, 10)) == 0 || o.rate_hz > 0xfffffffful) return false; }
+        else if (opt == "-f") { o.offset.hz = std::strtoll(val, nullptr, 10); f = true; }
+        else if (opt == "-F") { if (!number(val, o.offset.nco_hz)) return false; F = true; }
+        else if (opt == "-a") { if (!number(val, o.afc_ms) || !(o.afc_ms > 0.0) || o.afc_ms > 60000.0) return false; }
+        else if (opt == "-W") {
+            char* end = nullptr;
+            o.window_bytes = (size_t)std::strtoull(val, &end, 10);
+            o.window_bytes <<= (*end == 'k' || *end == 'K') ? 10 : (*end == 'm' || *end == 'M') ? 20 : 0;
+        }
+        else return false;
+    }
+    if (argc - a != 3 || o.batch == 0 || (f && F) || ((f || F) && !o.rate_hz) || (o.afc_ms > 0.0 && !F)) return false;
+    o.offset.kind = F ? o.offset.NCO : (f ? o.offset.RATIONAL : o.offset.NONE);
+    const std::string mode = argv[a];
+    o.in_path = argv[a + 1]; o.out_path = argv[a + 2];
+    if (mode == "u8") { o.fmt = P25FE_FMT_U8; o.bps = 2; }
+    else if (mode == "s16") { o.fmt = P25FE_FMT_S16; o.bps = 4; }
+    else if (mode == "cf32") { o.fmt = P25FE_FMT_CF32; o.bps = 8; }
+    else if (mode == "bb") o.bb = true;
+    else return false;
+    if (o.bb && (o.rate_hz || o.window_bytes)) return false;         // the resampler, the tuner and the bulk mode take IQ
+    return !(o.window_bytes && (o.wpath || o.jpath || o.rate_hz || o.afc_ms > 0.0));
+}
+
+// device memory (hipMalloc) or pinned host memory (hipHostMalloc); p is null when there was none: the caller has the message
+struct HipMem {
+    void* p = nullptr;
+    const bool pinned;
+    HipMem(size_t bytes, bool pin) : pinned(pin) { if ((pin ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes)) != hipSuccess) p = nullptr; }
+    ~HipMem() { (void)(pinned ? hipHostFree(p) : hipFree(p)); }
+    HipMem(const HipMem&) = delete;
+};
+
+// bulk mode: reader thread -> two pinned blocks -> p25fe_run_host_windows
+static int bulk(Handle& h, const Options& o, std::ifstream& in)
+{
+    const size_t eb = o.bps;
+    const size_t window = o.window_bytes / eb / 8 * 8;
     if (window < 8192) { std::fprintf(stderr, "window too small\n"); return 2; }
     const size_t block = 8 * window;                                  // samples per pinned block: the reader fills one while the library pipelines the other
                                                                       // (measured on a 1.15 GB file from the page cache: 8 windows 78 ms, 2 windows 93 - 105 ms;
                                                                       // the single reader thread's ~15 GB/s is what bounds this mode, not the bus)
-    char* buf[2] = {nullptr, nullptr};
-    for (int b = 0; b < 2; ++b)
-        if (hipHostMalloc(reinterpret_cast<void**>(&buf[b]), block * eb, hipHostMallocDefault) != hipSuccess) {
-            std::fprintf(stderr, "unable to allocate pinned blocks\n");
-            return 1;
-        }
+    const HipMem pinned[2] = {HipMem(block * eb, true), HipMem(block * eb, true)};
+    char* const buf[2] = {static_cast<char*>(pinned[0].p), static_cast<char*>(pinned[1].p)};
+    if (!buf[0] || !buf[1]) { std::fprintf(stderr, "unable to allocate pinned blocks\n"); return 1; }
     std::mutex mu;
     std::condition_variable cv;
     size_t filled[2] = {0, 0};
@@ -152,26 +216,26 @@ static int bulk(Handle& h, const std::string& mode, std::ifstream& in, const cha
             if (got < block) return;
         }
     });
-    std::ofstream out(out_path, std::ios::binary);
+    std::ofstream out(o.out_path, std::ios::binary);
     std::vector<uint8_t> dib(block / 30 + 4);
     size_t total = 0, samples = 0, windows = 0;
     double ms_h2d = 0.0, ms_comp = 0.0;
     const auto t0 = std::chrono::steady_clock::now();
     int failed = 0;                                                  // an error ends the loop, never the process: the reader thread is joinable
-    if (!out) { std::fprintf(stderr, "unable to open %s\n", out_path); failed = 1; }
+    if (!out) { std::fprintf(stderr, "unable to open %s\n", o.out_path); failed = 1; }
     for (int b = 0; !failed; b ^= 1) {
         size_t n;
         { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return full[b]; }); n = filled[b]; }
         size_t nd = 0;
         p25fe_windows_stats_t st;
-        const int rc = p25fe_run_host_windows(h.get(), buf[b], fmt, n, window, dib.data(), dib.size(), &nd, &st);
+        const int rc = p25fe_run_host_windows(h.get(), buf[b], o.fmt, n, window, dib.data(), dib.size(), &nd, &st);
         if (rc != P25FE_OK) {
             std::fprintf(stderr, "p25fe_replay: unable to run the capture: %s (%d)\n", p25fe_strerror(rc), rc);
             failed = 1;
             break;
         }
         out.write(reinterpret_cast<const char*>(dib.data()), (std::streamsize)nd);
-        if (!out.good()) { std::fprintf(stderr, "p25fe_replay: write error on %s (disk full?)\n", out_path); failed = 1; break; }
+        if (!out.good()) { std::fprintf(stderr, "p25fe_replay: write error on %s (disk full?)\n", o.out_path); failed = 1; break; }
         total += nd; samples += n; windows += st.n_windows; ms_h2d += st.ms_h2d; ms_comp += st.ms_compute;
         bool last;
         { std::lock_guard<std::mutex> lk(mu); full[b] = false; last = eof && n < block; cv.notify_all(); }
@@ -180,244 +244,183 @@ static int bulk(Handle& h, const std::string& mode, std::ifstream& in, const cha
     { std::lock_guard<std::mutex> lk(mu); stop = true; cv.notify_all(); }
     reader.join();
     out.close();
-    if (!failed && out.fail()) { std::fprintf(stderr, "p25fe_replay: write error on %s at close\n", out_path); failed = 1; }
+    if (!failed && out.fail()) { std::fprintf(stderr, "p25fe_replay: write error on %s at close\n", o.out_path); failed = 1; }
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    for (int b = 0; b < 2; ++b) (void)hipHostFree(buf[b]);
     if (failed) return 1;
     std::fprintf(stderr, "p25fe_replay: %zu dibits from %zu samples in %zu windows, %.1f ms (%.1f Msamples/s, %.2f GB/s; H2D copies %.1f ms, "
                          "kernels %.1f ms)\n", total, samples, windows, ms, samples / ms / 1e3, samples * eb / ms / 1e6, ms_h2d, ms_comp);
     return 0;
 }
 
-int main(int argc, char** argv)
+// The read loop of every chunked mode: the next chunk -- len() elements, a final short read cut to whole units -- goes into the
+// front of the chain (`push` may move it away), then `recv` runs the receiver.  An empty chunk goes through like any other.
+template <class T, class Len, class Push, class Recv> static void pump(std::ifstream& in, size_t unit, Len len, Push push, Recv recv)
 {
-    const char *wpath = nullptr, *jpath = nullptr;
-    size_t batch = 64, window_bytes = 0;
-    unsigned long rate_hz = 0;
-    long long offset_hz = 0;
-    double offset_nco_hz = 0.0;
-    double afc_ms = 0.0;                                              // -a: measure the first MS ms at -F's offset, correct once
-    bool tune = false, nco = false;
-    int a = 1;
-    for (; a < argc && argv[a][0] == '-' && argv[a][1] != '\0'; a += 2) {
-        if (a + 1 >= argc) return usage(argv[0]);
-        if (!std::strcmp(argv[a], "-w")) wpath = argv[a + 1];
-        else if (!std::strcmp(argv[a], "-j")) jpath = argv[a + 1];
-        else if (!std::strcmp(argv[a], "-b")) batch = (size_t)std::strtoull(argv[a + 1], nullptr, 10);
-        else if (!std::strcmp(argv[a], "-r")) {
-            rate_hz = std::strtoul(argv[a + 1], nullptr, 10);
-            if (rate_hz == 0 || rate_hz > 0xfffffffful) return usage(argv[0]);
-        }
-        else if (!std::strcmp(argv[a], "-f")) { offset_hz = std::strtoll(argv[a + 1], nullptr, 10); tune = true; }
-        else if (!std::strcmp(argv[a], "-F")) {
-            char* end = nullptr;
-            offset_nco_hz = std::strtod(argv[a + 1], &end);
-            if (end == argv[a + 1] || *end != '\0') return usage(argv[0]);
-            tune = nco = true;
-        }
-        else if (!std::strcmp(argv[a], "-a")) {
-            char* end = nullptr;
-            afc_ms = std::strtod(argv[a + 1], &end);
-            if (end == argv[a + 1] || *end != '\0' || !(afc_ms > 0.0) || afc_ms > 60000.0) return usage(argv[0]);
-        }
-        else if (!std::strcmp(argv[a], "-W")) {
-            char* end = nullptr;
-            window_bytes = (size_t)std::strtoull(argv[a + 1], &end, 10);
-            if (end && (*end == 'k' || *end == 'K')) window_bytes <<= 10;
-            else if (end && (*end == 'm' || *end == 'M')) window_bytes <<= 20;
-        }
-        else return usage(argv[0]);
+    for (std::vector<T> chunk;;) {
+        chunk.resize(len());
+        if (!(in.read(reinterpret_cast<char*>(chunk.data()), (std::streamsize)(chunk.size() * sizeof(T))) || in.gcount() > 0)) break;
+        chunk.resize((size_t)in.gcount() / (unit * sizeof(T)) * unit);
+        push(chunk);
+        recv();
     }
-    bool rational = false;                                            // -f and -F exclude each other
-    for (int k = 1; k < a; k += 2) rational = rational || !std::strcmp(argv[k], "-f");
-    if (argc - a != 3 || batch == 0 || (tune && !rate_hz) || (nco && rational) || (afc_ms > 0.0 && !nco)) return usage(argv[0]);
-    const std::string mode = argv[a];
-    std::ifstream in(argv[a + 1], std::ios::binary);
-    if (!in) { std::fprintf(stderr, "unable to open %s\n", argv[a + 1]); return 1; }
+}
+
+// chunks of In -> `front` -> 240 ksps IQ chunks of Sample -> DemodTask -> the receiver
+template <class Sample, class In, class Len, class Front, class Recv>
+static void demodulate(Handle& h, std::ifstream& in, Hub& hub, Chan<Baseband>& chan, size_t unit, Len len, Front front, Recv recv)
+{
+    Chan<std::vector<Sample>> reader;
+    DemodTask<Chan<std::vector<Sample>>, Hub, Chan<Baseband>, Sample> demod(h, reader, hub, chan);
+    pump<In>(in, unit, len, [&](std::vector<In>& chunk) { reader.send(front(chunk)); demod.run(); }, recv);
+}
+
+// -a MS: the frequency measure (docs/SPEC.md 3.0f, the recommended prefilter) runs on the tuned row while the first MS ms of the
+// capture go by; then the channel's step is corrected ONCE, without a phase jump (3.0e), and the stream carries on
+class Afc {                                                           // (span: input samples to measure; cap240: the most tuned samples of one chunk)
+    static constexpr int32_t D = 10, T = 240;
+    static constexpr size_t KEEP = (size_t)(T - 1 + D);
+    size_t left_;                                                     // input samples still to measure
+    FreqMeasure measure_;
+    HipMem d_row_, d_acc_;
+    std::vector<float> row_;                                          // [history | the chunk's tuned samples], as it goes to the device
+    float* row() const { return static_cast<float*>(d_row_.p); }
+    p25fe_afc_acc_t* acc() const { return static_cast<p25fe_afc_acc_t*>(d_acc_.p); }
+public:
+    Afc(Handle& h, size_t span, size_t cap240) : left_(span), d_row_((KEEP + cap240) * 2 * sizeof(float), false), d_acc_(sizeof(p25fe_afc_acc_t), false)
+    {
+        std::vector<float> g((size_t)T);
+        expect(p25fe_afc_design(D, 7000.0, T, g.data(), g.size()), "unable to design the measure's prefilter");
+        measure_ = FreqMeasure(h, D, T, g.data(), 1);
+        const p25fe_afc_acc_t zero = {0, 0, 0, 0};
+        if (!row() || !acc() || hipMemcpy(acc(), &zero, sizeof zero, hipMemcpyHostToDevice) != hipSuccess)
+            fail("p25fe_replay: no device memory for the frequency measure\n");
+    }
+    bool over() const { return left_ == 0; }
+    size_t chunk(size_t n_chunk) const { return left_ ? std::min(n_chunk, left_) : n_chunk; }   // input samples of the next read
+    // one chunk: its n_in input samples (short_read: the capture ended in it) gave the tuned samples x240, the first at pos240
+    void feed(const std::vector<float>& x240, uint64_t pos240, size_t n_in, bool short_read)
+    {
+        row_.erase(row_.begin(), row_.end() - (long)(2 * std::min(KEEP, row_.size() / 2)));     // the last KEEP tuned samples (fewer at the start)
+        const size_t nh = row_.size() / 2;
+        row_.insert(row_.end(), x240.begin(), x240.end());
+        if (hipMemcpy(row(), row_.data(), row_.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+            fail("p25fe_replay: unable to copy the tuned row to the device\n");
+        expect(p25fe_afc_measure_dev(measure_.get(), row() + 2 * nh, 0, nh, x240.size() / 2, pos240, 24, acc(), nullptr), "unable to measure the frequency");
+        left_ = short_read ? 0 : left_ - n_in;                        // (a capture shorter than MS ms: what there is)
+    }
+    // the span is over: the estimate, reported on stderr and in the -j events, and the one correction from input sample `at` on
+    int32_t correct(const Tuner& tn, uint32_t rate_hz, int32_t step, uint64_t at, FILE* js) const
+    {
+        p25fe_afc_acc_t a;
+        if (hipMemcpy(&a, acc(), sizeof a, hipMemcpyDeviceToHost) != hipSuccess) fail("p25fe_replay: unable to read the frequency measure\n");
+        double hz = 0.0, coherence = 0.0;
+        int32_t dstep = 0;
+        expect(p25fe_afc_hz(&a, D, &hz, &coherence), "unable to evaluate the frequency measure");
+        expect(p25fe_nco_step(rate_hz, hz, &dstep), "unable to turn the estimate into a step");
+        const int32_t new_step = (int32_t)((uint32_t)step + (uint32_t)dstep);
+        expect(p25fe_afc_set_step(tn.get(), 0, new_step, at, nullptr), "unable to retune");
+        std::fprintf(stderr, "p25fe_replay: afc: %.1f Hz off (coherence %.3f, %" PRIu64 " products); step %d -> %d at sample %" PRIu64 "\n",
+                     hz, coherence, a.n, step, new_step, at);
+        if (js)
+            std::fprintf(js, "{\"event\":\"afc\",\"hz\":%.3f,\"coherence\":%.6f,\"products\":%" PRIu64 ",\"step\":%d,\"at\":%" PRIu64 "}\n",
+                         hz, coherence, a.n, new_step, at);
+        return new_step;
+    }
+};
+
+// -r: what sits in front of the cf32 DemodTask when the capture is not at 240 ksps -- the resampler (docs/SPEC.md 3.0b), or the tuner
+// with a rational (-f, 3.0c) or an NCO channel (-F, 3.0d) and the optional AFC (-a).  A raw chunk in, its 240 ksps cf32 samples out.
+class ToChannelRate {
+    const Options& o_;
+    FILE* js_;
+    Resampler rs_;                                                    // -r alone
+    Tuner tn_;                                                        // -r with -f or -F
+    std::optional<Afc> afc_;
+    int32_t step_ = 0;                                                // the NCO channel's
+    size_t n_chunk_ = 0, cap240_ = 0;                                 // input samples per chunk; the most 240 ksps samples one gives
+    uint64_t consumed_ = 0, pos240_ = 0;
+public:
+    ToChannelRate(Handle& h, const Options& o, FILE* js) : o_(o), js_(js)
+    {
+        int32_t L = 0, M = 0, T = 0, num = 0, den = 0;
+        const uint32_t rate = (uint32_t)o.rate_hz;
+        if (p25fe_resampler_design(rate, &L, &M, &T, nullptr, 0) != P25FE_ERR_CAPACITY)
+            fail("no resampler for %lu Hz (240000 / rate in lowest terms must be L / M with L <= %d, L < M <= %d)\n", o.rate_hz, P25FE_RS_MAX_L, P25FE_RS_MAX_M);
+        std::vector<float> taps((size_t)L * (size_t)T);
+        expect(p25fe_resampler_design(rate, &L, &M, &T, taps.data(), taps.size()), "unable to design the resampler");
+        if (o.offset.kind == o.offset.NONE) rs_ = Resampler(h, L, M, T, taps.data());
+        else if (o.offset.kind == o.offset.NCO) {
+            if (p25fe_nco_step(rate, o.offset.nco_hz, &step_) != P25FE_OK) fail("no tuner for %g Hz at %lu Hz (beyond half the rate)\n", o.offset.nco_hz, o.rate_hz);
+            tn_ = Tuner::nco(h, L, M, T, taps.data(), 1, &step_);
+        } else {
+            if (p25fe_tuner_freq(rate, o.offset.hz, &num, &den) != P25FE_OK)
+                fail("no tuner for %lld Hz at %lu Hz (beyond half the rate, or offset / rate in lowest terms has a denominator above %d)\n",
+                     o.offset.hz, o.rate_hz, P25FE_TUNE_MAX_DEN);
+            tn_ = Tuner::rational(h, L, M, T, taps.data(), 1, &num, &den);
+        }
+        n_chunk_ = (size_t)BUF_SAMPLES * o.batch * (size_t)M / (size_t)L;       // about one cf32-mode chunk of 240 ksps samples
+        cap240_ = n_chunk_ * (size_t)L / (size_t)M + 2;
+        if (o.afc_ms > 0.0) afc_.emplace(h, std::max<size_t>(1, (size_t)((double)o.rate_hz * o.afc_ms / 1000.0)), cap240_);
+    }
+    size_t next_bytes() const { return (afc_ ? afc_->chunk(n_chunk_) : n_chunk_) * o_.bps; }
+    std::vector<float> operator()(const std::vector<char>& raw)       // tune, measure, maybe retune
+    {
+        const size_t n = raw.size() / o_.bps;
+        const bool short_read = raw.size() < next_bytes();
+        std::vector<float> x240(2 * cap240_);
+        size_t n240 = 0;
+        if (tn_.get()) expect(p25fe_tune(tn_.get(), raw.data(), o_.fmt, n, x240.data(), cap240_, &n240), "unable to tune");
+        else expect(p25fe_resample(rs_.get(), raw.data(), o_.fmt, n, x240.data(), cap240_, &n240), "unable to resample");
+        x240.resize(2 * n240);
+        consumed_ += n;
+        if (afc_ && !afc_->over()) {
+            afc_->feed(x240, pos240_, n, short_read);
+            if (afc_->over()) step_ = afc_->correct(tn_, (uint32_t)o_.rate_hz, step_, consumed_, js_);
+        }
+        pos240_ += n240;
+        return x240;
+    }
+};
+
+int main(int argc, char** argv)
+try {
+    Options o;
+    if (!parse(argc, argv, o)) return usage(argv[0]);
+    std::ifstream in(o.in_path, std::ios::binary);
+    if (!in) fail("unable to open %s\n", o.in_path);
     Handle h(0, 1);
-    if (window_bytes) {
-        if (wpath || jpath || rate_hz || tune || afc_ms > 0.0 || (mode != "u8" && mode != "s16" && mode != "cf32")) return usage(argv[0]);
-        return bulk(h, mode, in, argv[a + 2], window_bytes);
-    }
-    Chan<std::vector<uint8_t>> reader;
+    if (o.window_bytes) return bulk(h, o, in);
     Hub hub;
     Chan<Baseband> chan;
     Sink sink;
-    sink.out.open(argv[a + 2], std::ios::binary);
-    sink.keep = jpath != nullptr;
-    if (jpath && !(hub.js = std::fopen(jpath, "w"))) { std::fprintf(stderr, "unable to open %s\n", jpath); return 1; }
+    sink.out.open(o.out_path, std::ios::binary);
+    sink.keep = o.jpath != nullptr;
+    if (o.jpath && !(hub.js = std::fopen(o.jpath, "w"))) fail("unable to open %s\n", o.jpath);
     std::ofstream bbfile;                                             // samples_file, src/main.rs:174-175
-    if (wpath) {
-        bbfile.open(wpath, std::ios::binary);
-        if (!bbfile) { std::fprintf(stderr, "unable to open baseband file\n"); return 1; }
-    }
-    auto dump = [&](const std::vector<float>& s) {                    // the closure of src/main.rs:278-283
-        if (wpath) bbfile.write(reinterpret_cast<const char*>(s.data()), (std::streamsize)(s.size() * sizeof(float)));
-    };
+    if (o.wpath) bbfile.open(o.wpath, std::ios::binary);
+    if (o.wpath && !bbfile) fail("unable to open baseband file\n");
     RecvTask<Chan<Baseband>, Sink> recv(h, chan, sink);
-
-    if (rate_hz) {
-        // a tuner rate other than 240 ksps: chunk -> p25fe_resample -> the cf32 mode's body
-        if (mode != "u8" && mode != "s16" && mode != "cf32") return usage(argv[0]);
-        const int fmt = mode == "u8" ? P25FE_FMT_U8 : (mode == "s16" ? P25FE_FMT_S16 : P25FE_FMT_CF32);
-        const size_t bps = fmt == P25FE_FMT_U8 ? 2 : (fmt == P25FE_FMT_S16 ? 4 : 8);
-        int32_t L = 0, M = 0, T = 0;
-        if (p25fe_resampler_design((uint32_t)rate_hz, &L, &M, &T, nullptr, 0) != P25FE_ERR_CAPACITY) {
-            std::fprintf(stderr, "no resampler for %lu Hz (240000 / rate in lowest terms must be L / M with L <= %d, L < M <= %d)\n", rate_hz,
-                         P25FE_RS_MAX_L, P25FE_RS_MAX_M);
-            return 1;
-        }
-        std::vector<float> taps((size_t)L * (size_t)T);
-        expect(p25fe_resampler_design((uint32_t)rate_hz, &L, &M, &T, taps.data(), taps.size()), "unable to design the resampler");
-        p25fe_resampler_t* rs = nullptr;
-        p25fe_tuner_t* tn = nullptr;
-        int32_t step = 0;
-        if (nco) {
-            if (p25fe_nco_step((uint32_t)rate_hz, offset_nco_hz, &step) != P25FE_OK) {
-                std::fprintf(stderr, "no tuner for %g Hz at %lu Hz (beyond half the rate)\n", offset_nco_hz, rate_hz);
-                return 1;
-            }
-            expect(p25fe_nco_create(h.get(), L, M, T, taps.data(), 1, &step, &tn), "unable to create the tuner");
-        } else if (tune) {
-            int32_t num = 0, den = 0;
-            if (p25fe_tuner_freq((uint32_t)rate_hz, offset_hz, &num, &den) != P25FE_OK) {
-                std::fprintf(stderr, "no tuner for %lld Hz at %lu Hz (beyond half the rate, or offset / rate in lowest terms has a denominator above %d)\n",
-                             offset_hz, rate_hz, P25FE_TUNE_MAX_DEN);
-                return 1;
-            }
-            expect(p25fe_tuner_create(h.get(), L, M, T, taps.data(), 1, &num, &den, &tn), "unable to create the tuner");
-        } else {
-            expect(p25fe_resampler_create(h.get(), L, M, T, taps.data(), &rs), "unable to create the resampler");
-        }
-        const size_t n_chunk = (size_t)BUF_SAMPLES * batch * (size_t)M / (size_t)L;     // about one cf32-mode chunk of 240 ksps samples
-        std::vector<char> buf(n_chunk * bps);
-        std::vector<float> x240(2 * (n_chunk * (size_t)L / (size_t)M + 2)), bb(x240.size() / 10 + 2);
-        unsigned notifier = 0;
-        // -a MS: the frequency measure (docs/SPEC.md 3.0f, the recommended prefilter) runs on the tuned row while the first MS ms of
-        // the capture go by; then the channel's step is corrected ONCE, without a phase jump (3.0e), and the stream carries on
-        size_t meas_left = afc_ms > 0.0 ? std::max<size_t>(1, (size_t)((double)rate_hz * afc_ms / 1000.0)) : 0;   // input samples still to measure
-        const int32_t afc_d = 10, afc_t = 240;
-        const size_t afc_keep = (size_t)(afc_t - 1 + afc_d);
-        p25fe_afc_t* afc = nullptr;
-        float* d_row = nullptr;
-        p25fe_afc_acc_t* d_acc = nullptr;
-        std::vector<float> row;                                       // [history | the chunk's tuned samples], as it goes to the device
-        std::vector<float> tail;                                      // the last afc_keep tuned samples (fewer at the start)
-        uint64_t consumed = 0, pos240 = 0;
-        if (meas_left) {
-            std::vector<float> g((size_t)afc_t);
-            expect(p25fe_afc_design(afc_d, 7000.0, afc_t, g.data(), g.size()), "unable to design the measure's prefilter");
-            expect(p25fe_afc_create(h.get(), afc_d, afc_t, g.data(), 1, &afc), "unable to create the frequency measure");
-            const p25fe_afc_acc_t zero = {0, 0, 0, 0};
-            if (hipMalloc(reinterpret_cast<void**>(&d_row), (afc_keep + x240.size() / 2) * 2 * sizeof(float)) != hipSuccess ||
-                hipMalloc(reinterpret_cast<void**>(&d_acc), sizeof zero) != hipSuccess ||
-                hipMemcpy(d_acc, &zero, sizeof zero, hipMemcpyHostToDevice) != hipSuccess) {
-                std::fprintf(stderr, "p25fe_replay: no device memory for the frequency measure\n");
-                return 1;
-            }
-        }
-        for (;;) {
-            const size_t want_n = meas_left ? std::min(n_chunk, meas_left) : n_chunk;
-            if (!(in.read(buf.data(), (std::streamsize)(want_n * bps)) || in.gcount() > 0)) break;
-            const size_t n = (size_t)in.gcount() / bps;
-            size_t n240 = 0, n_out = 0;
-            if (tn) expect(p25fe_tune(tn, buf.data(), fmt, n, x240.data(), x240.size() / 2, &n240), "unable to tune");
-            else expect(p25fe_resample(rs, buf.data(), fmt, n, x240.data(), x240.size() / 2, &n240), "unable to resample");
-            consumed += n;
-            if (meas_left) {
-                const size_t nh = tail.size() / 2;
-                row.assign(tail.begin(), tail.end());
-                row.insert(row.end(), x240.begin(), x240.begin() + (long)(2 * n240));
-                if (hipMemcpy(d_row, row.data(), row.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
-                    std::fprintf(stderr, "p25fe_replay: unable to copy the tuned row to the device\n");
-                    return 1;
-                }
-                expect(p25fe_afc_measure_dev(afc, d_row + 2 * nh, 0, nh, n240, pos240, 24, d_acc, nullptr), "unable to measure the frequency");
-                tail.assign(row.end() - (long)(2 * std::min(afc_keep, row.size() / 2)), row.end());
-                meas_left = n < want_n ? 0 : meas_left - n;           // (a capture shorter than MS ms: what there is)
-                if (!meas_left) {
-                    p25fe_afc_acc_t acc;
-                    if (hipMemcpy(&acc, d_acc, sizeof acc, hipMemcpyDeviceToHost) != hipSuccess) {
-                        std::fprintf(stderr, "p25fe_replay: unable to read the frequency measure\n");
-                        return 1;
-                    }
-                    double hz = 0.0, coherence = 0.0;
-                    int32_t dstep = 0;
-                    expect(p25fe_afc_hz(&acc, afc_d, &hz, &coherence), "unable to evaluate the frequency measure");
-                    expect(p25fe_nco_step((uint32_t)rate_hz, hz, &dstep), "unable to turn the estimate into a step");
-                    const int32_t new_step = (int32_t)((uint32_t)step + (uint32_t)dstep);
-                    expect(p25fe_afc_set_step(tn, 0, new_step, consumed, nullptr), "unable to retune");
-                    std::fprintf(stderr, "p25fe_replay: afc: %.1f Hz off (coherence %.3f, %" PRIu64 " products); step %d -> %d at sample %" PRIu64 "\n",
-                                 hz, coherence, acc.n, step, new_step, consumed);
-                    if (hub.js)
-                        std::fprintf(hub.js, "{\"event\":\"afc\",\"hz\":%.3f,\"coherence\":%.6f,\"products\":%" PRIu64 ",\"step\":%d,\"at\":%" PRIu64 "}\n",
-                                     hz, coherence, acc.n, new_step, consumed);
-                    step = new_step;
-                }
-            }
-            pos240 += n240;
-            float power = 0.f;
-            const bool want = (++notifier % 4) == 0;
-            expect(p25fe_demod_cf32(h.get(), x240.data(), n240, bb.data(), bb.size(), &n_out, want ? &power : nullptr),
-                   "unable to demodulate");
-            if (want) hub.send(HubEvent{power});
-            chan.send(Baseband{std::vector<float>(bb.begin(), bb.begin() + (long)n_out)});
-            recv.run(dump, hub);
-        }
-        p25fe_afc_destroy(afc);
-        (void)hipFree(d_row);
-        (void)hipFree(d_acc);
-        p25fe_resampler_destroy(rs);
-        p25fe_tuner_destroy(tn);
-    } else if (mode == "u8") {
-        std::vector<uint8_t> buf(BUF_BYTES * batch);
-        DemodTask<Chan<std::vector<uint8_t>>, Hub, Chan<Baseband>> demod(h, reader, hub, chan);
-        while (in.read(reinterpret_cast<char*>(buf.data()), (std::streamsize)buf.size()) || in.gcount() > 0) {
-            std::vector<uint8_t> chunk(buf.begin(), buf.begin() + (in.gcount() & ~std::streamsize(1)));
-            reader.send(std::move(chunk));
-            demod.run();
-            recv.run(dump, hub);
-        }
-    } else if (mode == "s16") {
-        Chan<std::vector<int16_t>> reader16;
-        std::vector<int16_t> buf(2 * BUF_SAMPLES * batch);
-        DemodTask<Chan<std::vector<int16_t>>, Hub, Chan<Baseband>, int16_t> demod(h, reader16, hub, chan);
-        while (in.read(reinterpret_cast<char*>(buf.data()), (std::streamsize)(buf.size() * 2)) || in.gcount() > 0) {
-            std::vector<int16_t> chunk(buf.begin(), buf.begin() + (in.gcount() / 4) * 2);      // whole complex samples
-            reader16.send(std::move(chunk));
-            demod.run();
-            recv.run(dump, hub);
-        }
-    } else if (mode == "cf32") {
-        std::vector<float> buf(2 * BUF_SAMPLES * batch), bb(BUF_SAMPLES * batch / 5 + 2);
-        unsigned notifier = 0;
-        while (in.read(reinterpret_cast<char*>(buf.data()), (std::streamsize)(buf.size() * 4)) || in.gcount() > 0) {
-            const size_t n = (size_t)in.gcount() / 8;
-            size_t n_out = 0;
-            float power = 0.f;
-            const bool want = (++notifier % 4) == 0;                  // Throttler::new(4), src/demod.rs:67, 95
-            expect(p25fe_demod_cf32(h.get(), buf.data(), n, bb.data(), bb.size(), &n_out, want ? &power : nullptr),
-                   "unable to demodulate");
-            if (want) hub.send(HubEvent{power});
-            chan.send(Baseband{std::vector<float>(bb.begin(), bb.begin() + (long)n_out)});
-            recv.run(dump, hub);
-        }
-    } else if (mode == "bb") {
-        std::vector<float> buf(8192 * batch);                         // replay.rs reads 32768-byte blocks (src/replay.rs:27)
-        while (in.read(reinterpret_cast<char*>(buf.data()), (std::streamsize)(buf.size() * 4)) || in.gcount() > 0) {
-            const size_t n = (size_t)in.gcount() / 4;                 // only the bytes actually read (replay.rs:36 re-feeds stale tail)
-            chan.send(Baseband{std::vector<float>(buf.begin(), buf.begin() + (long)n)});
-            recv.run(dump, hub);
-        }
-    } else {
-        return usage(argv[0]);
-    }
+    const auto receive = [&] {
+        recv.run([&](const std::vector<float>& s) {                   // the closure of src/main.rs:278-283
+            if (o.wpath) bbfile.write(reinterpret_cast<const char*>(s.data()), (std::streamsize)(s.size() * sizeof(float)));
+        }, hub);
+    };
+    const auto len240k = [&] { return 2 * BUF_SAMPLES * o.batch; };  // BUF_SAMPLES * batch samples per chunk, whatever the format
+    const auto take = [](auto& chunk) { return std::move(chunk); };   // straight into the reader channel
+    if (o.rate_hz) {
+        ToChannelRate front(h, o, hub.js);
+        demodulate<float, char>(h, in, hub, chan, o.bps, [&] { return front.next_bytes(); }, [&](std::vector<char>& raw) { return front(raw); }, receive);
+    } else if (o.bb)                                                  // replay.rs reads 32768-byte blocks (src/replay.rs:27); only the bytes
+        pump<float>(in, 1, [&] { return 8192 * o.batch; },            // actually read go on (replay.rs:36 re-feeds the stale tail)
+                    [&](std::vector<float>& chunk) { chan.send(Baseband{std::move(chunk)}); }, receive);
+    else if (o.fmt == P25FE_FMT_U8) demodulate<uint8_t, uint8_t>(h, in, hub, chan, 2, len240k, take, receive);
+    else if (o.fmt == P25FE_FMT_S16) demodulate<int16_t, int16_t>(h, in, hub, chan, 2, len240k, take, receive);
+    else demodulate<float, float>(h, in, hub, chan, 2, len240k, take, receive);
 
     if (hub.js) {
         // network identifiers of all frame syncs in one pass over the finished dibit stream, then the stats row
         std::vector<p25fe_nid_t> nid(sink.sync_pos.size());
-        expect(p25fe_nid(h.get(), sink.all_dibits.data(), sink.all_dibits.size(), sink.sync_dibit.data(), sink.sync_pos.data(),
-                         nid.size(), nid.data()),
+        expect(p25fe_nid(h.get(), sink.all_dibits.data(), sink.all_dibits.size(), sink.sync_dibit.data(), sink.sync_pos.data(), nid.size(), nid.data()),
                "unable to decode network identifiers");
         uint64_t words = 0, errs = 0, fixed = 0;
         for (const p25fe_nid_t& r : nid) {
@@ -426,13 +429,9 @@ int main(int argc, char** argv)
             if (r.valid >= 0) { ++words; if (r.valid == 0) ++errs; else fixed += r.n_errors; }
         }
         // serialize_code_stats (src/hub.rs:574-581): totalWords, errWords, totalSymbols = words * size, fixedSymbols
-        std::fprintf(hub.js,
-                     "{\"event\":\"updateStats\",\"dibits\":%zu,\"syncs\":%zu,\"bch\":{\"totalWords\":%" PRIu64 ",\"errWords\":%" PRIu64
-                     ",\"totalSymbols\":%" PRIu64 ",\"fixedSymbols\":%" PRIu64 "}}\n",
-                     sink.n_dibits, sink.n_sync, words, errs, words * 63, fixed);
-        std::fclose(hub.js);
+        std::fprintf(hub.js, "{\"event\":\"updateStats\",\"dibits\":%zu,\"syncs\":%zu,\"bch\":{\"totalWords\":%" PRIu64 ",\"errWords\":%" PRIu64
+                             ",\"totalSymbols\":%" PRIu64 ",\"fixedSymbols\":%" PRIu64 "}}\n", sink.n_dibits, sink.n_sync, words, errs, words * 63, fixed);
     }
-    std::fprintf(stderr, "p25fe_replay: %zu dibits, %zu frame syncs, %zu power reports\n", sink.n_dibits, sink.n_sync,
-                 hub.n_power);
+    std::fprintf(stderr, "p25fe_replay: %zu dibits, %zu frame syncs, %zu power reports\n", sink.n_dibits, sink.n_sync, hub.n_power);
     return 0;
-}
+} catch (const Exit& e) { return e.status; }

@@ -42,7 +42,7 @@ def test_python_demodtask_recvtask_pipeline(c4fm_1s):
     assert all(x["dibits"] <= len(dib) and x["syncs"] <= len(spos) for x in st)           # (15 chunks in this second: none yet)
 
 
-@pytest.mark.parametrize("mode", ["u8", "cf32", "bb"])
+@pytest.mark.parametrize("mode", ["u8", "s16", "cf32", "bb"])
 def test_cpp_replay_driver(tmp_path, c4fm_1s, mode):
     """C++ DemodTask/RecvTask mirror (p25rx_amd/host) through the replay-style CLI vs the oracle."""
     from oracle import oracle as O
@@ -55,6 +55,11 @@ def test_cpp_replay_driver(tmp_path, c4fm_1s, mode):
         u8 = c4fm.to_u8(iq)
         u8.tofile(src)
         ref = O.Recv().feed(O.Demod().feed_u8(u8))[0]
+    elif mode == "s16":
+        from test_gpu_s16 import conv
+        s16 = c4fm.to_s16(iq)
+        s16.tofile(src)
+        ref = O.run_cf32(conv(s16))                           # the format's definition: v * 2^-15
     elif mode == "cf32":
         iq.tofile(src)
         ref = O.run_cf32(iq)

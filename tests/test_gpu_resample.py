@@ -321,6 +321,37 @@ def test_end_to_end(O, mods, up, down, fs):
     assert np.array_equal(got[:k], truth[24:24 + k])
 
 
+@pytest.mark.parametrize("mode", ["u8", "s16"])
+def test_replay_resamples(O, mods, tmp_path, mode):
+    """p25fe_replay -r 2048000 u8|s16 (the resampler alone in front of the cf32 mode's path) on test_end_to_end's 2.048 Msps capture,
+    one 32768-byte buffer's worth per call and the default batch: the oracle's dibits on the model's output for the converted
+    capture, bit for bit.  The capture is scaled to the formats' range first: channel plus interferer reach 1.4."""
+    import os
+    import subprocess
+    from scipy import signal as sps
+    from p25rx_amd import c4fm
+    _lib, FE, RS = mods
+    up, down, fs = 128, 15, 2048000
+    exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "build", "p25fe_replay")
+    assert os.path.exists(exe), "run __graft_entry__.build()"
+    iq, truth, _ = c4fm.synth(0.25, seed=12, snr_db=25.0)
+    wide = sps.resample_poly(iq.astype(np.complex128), up, down)
+    t = np.arange(len(wide)) / float(fs)
+    wide = (0.5 * (wide + 0.8 * np.exp(2j * np.pi * 300e3 * t))).astype(np.complex64)
+    raw = c4fm.to_u8(wide) if mode == "u8" else c4fm.to_s16(wide)
+    L, M, T, taps = RS.design(fs)
+    assert (L, M) == (down, up)
+    ref = O.run_cf32(RM.resample(conv(raw), L, M, T, taps))
+    k = min(len(ref), len(truth) - 24)
+    assert k > 1100 and np.array_equal(ref[:k], truth[24:24 + k])
+    src, out = tmp_path / ("cap." + mode), tmp_path / "dibits.out"
+    raw.tofile(src)
+    for batch in (["-b", "1"], []):
+        r = subprocess.run([exe] + batch + ["-r", str(fs), mode, str(src), str(out)], capture_output=True, text=True, timeout=100)
+        assert r.returncode == 0, r.stderr[-1000:]
+        assert np.array_equal(np.fromfile(out, dtype=np.uint8), ref), batch
+
+
 # ---- 9: lifetimes -------------------------------------------------------------------------------------------------------------
 def test_destroy_after_the_handle(mods, stream):
     """A garbage collector may finalise the handle before the resampler made from it (both sit in one reference cycle as soon as a
