@@ -157,6 +157,37 @@ pub const RS_MAX_TABLE: i32 = 4096;
 pub enum Tuner {}
 /// p25fe_afc_t: the frequency measure of docs/SPEC.md 3.0f (made from a Handle, which must outlive it)
 pub enum Afc {}
+/// p25fe_track_t: the AFC loop of docs/SPEC.md 3.0g (made from a Tuner of NCO channels and an Afc, which must outlive it)
+pub enum Track {}
+pub const TRACK_NONE: u32 = 0;
+pub const TRACK_SHORT: u32 = 1;
+pub const TRACK_REJECT: u32 = 2;
+pub const TRACK_APPLY: u32 = 3;
+/// p25fe_track_cfg_t: the loop's configuration, 32 bytes
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct TrackCfg {
+    pub shift: i32,
+    pub coh_min_q15: i32,
+    pub gain_q16: i32,
+    pub max_pull: i32,
+    pub max_dev: i32,
+    pub reserved: i32,
+    pub min_products: u64,
+}
+/// p25fe_track_state_t: one channel's state, 32 bytes
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct TrackState {
+    pub step: i32,
+    pub ph0: u32,
+    pub last_theta: i32,
+    pub last_dstep: i32,
+    pub n_applied: u32,
+    pub n_rejected: u32,
+    pub n_short: u32,
+    pub status: u32,
+}
 /// p25fe_afc_acc_t: one row's sums, 32 bytes
 #[repr(C)]
 #[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
@@ -253,6 +284,19 @@ extern "C" {
     pub fn p25fe_afc_measure_dev(afc: *mut Afc, d_rows: *const f32, row_stride: usize, n_hist: usize, n: usize, abs_first: u64,
                                  shift: i32, d_acc: *mut AfcAcc, stream: *mut c_void) -> c_int;
     pub fn p25fe_afc_hz(acc: *const AfcAcc, d: i32, hz: *mut f64, coherence: *mut f64) -> c_int;
+    // AFC loop (docs/SPEC.md 3.0g): every channel's (step, ph0) updated on the device from its record, in stream order
+    pub fn p25fe_track_create(tn: *mut Tuner, afc: *mut Afc, cfg: *const TrackCfg, out: *mut *mut Track) -> c_int;
+    pub fn p25fe_track_destroy(lp: *mut Track);
+    pub fn p25fe_track_records(lp: *mut Track, get: *mut AfcAcc, set: *const AfcAcc) -> c_int;
+    pub fn p25fe_track_measure_dev(lp: *mut Track, d_rows: *const f32, row_stride: usize, n_hist: usize, n: usize, abs_first: u64,
+                                   stream: *mut c_void) -> c_int;
+    pub fn p25fe_track_update_dev(lp: *mut Track, abs_at: u64, stream: *mut c_void) -> c_int;
+    pub fn p25fe_track_run_dev(lp: *mut Track, d_iq: *const c_void, fmt: c_int, n_hist: usize, n: usize, abs_first: u64, window: u64,
+                               d_out: *mut f32, out_stride: usize, n_hist_out: usize, stream: *mut c_void) -> c_int;
+    pub fn p25fe_track_read(lp: *mut Track, state_out: *mut TrackState) -> c_int;
+    pub fn p25fe_track_step(cfg: *const TrackCfg, l: i32, m: i32, d: i32, step_ref: i32, acc_in: *const AfcAcc,
+                            state_in: *const TrackState, abs_at: u64, acc_out: *mut AfcAcc, state_out: *mut TrackState) -> c_int;
+    pub fn p25fe_track_hz(state: *const TrackState, d: i32, hz: *mut f64) -> c_int;
     pub fn p25fe_n_baseband(abs0: u64, n: usize) -> usize;
     pub fn p25fe_slice_dev(h: *mut Handle, d_bb: *const f32, bb_stride: usize, n_hist_bb: usize, n_bb: usize, abs_bb0: u64,
                            d_anchor_in: *const Anchor, d_dibits: *mut u8, dibit_stride: usize, d_sync_pos: *mut i64,

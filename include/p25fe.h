@@ -490,10 +490,12 @@ int p25fe_nco_create(p25fe_t *h, int32_t L, int32_t M, int32_t T, const float *t
  * stream, where p25fe_tune_dev with a null stream enqueues.  A call mixes its WHOLE window, the T - 1 history samples
  * included, with the current (step, ph0): the first T - 1 taps after a change see history mixed at a frequency that is off by the
  * change (100 Hz over 84 samples at 2.5 Msps: 0.0034 cycles).  p25fe_tuner_reset leaves steps and offsets alone.
- * P25FE_ERR_ARG: a null or rational tuner, k outside [0, n_out_channels), abs_at >= 2^62. */
+ * P25FE_ERR_ARG: a null or rational tuner, k outside [0, n_out_channels), abs_at >= 2^62; a tuner whose steps a tracking loop
+ * (part 3) has updated on the device since the last p25fe_track_read: the host's (step, ph0) are stale then, and nothing is computed
+ * from stale numbers. */
 int p25fe_afc_set_step(p25fe_tuner_t *tn, int32_t k, int32_t step, uint64_t abs_at, void *stream);
 /* channel k's current step and phase offset, as the host holds them; no device is touched.  P25FE_ERR_ARG: a null or rational
- * tuner, k outside the range, a null pointer. */
+ * tuner, k outside the range, a null pointer; a tuner whose host pair is stale (p25fe_afc_set_step). */
 int p25fe_afc_get_step(const p25fe_tuner_t *tn, int32_t k, int32_t *step, uint32_t *ph0);
 /* (c, s) of 3.0e for a step, a phase offset and an absolute index, with exactly the kernel's operations (ph0 = 0:
  * p25fe_nco_factor); no device needed.  P25FE_ERR_ARG: a null pointer. */
@@ -544,6 +546,87 @@ int p25fe_afc_measure_dev(p25fe_afc_t *afc, const float *d_rows, size_t row_stri
  * hypot(re, im) / pow (1: one clean carrier; near 0: noise); both 0 when pow <= 0.  Host only.  P25FE_ERR_ARG: a null pointer, D
  * outside the limits. */
 int p25fe_afc_hz(const p25fe_afc_acc_t *acc, int32_t D, double *hz, double *coherence);
+
+/* ---- AFC, part 3: the tracking loop, closed on the device in stream order (docs/SPEC.md 3.0g) ---------------------------------------
+ * One kernel launch (k_afc_loop, one thread per channel) reads every channel's record of part 2 and its (step, ph0), and by an
+ * integer law writes the next (step, ph0): tune -> measure -> update -> tune is enqueued without the host reading a record.  Per
+ * channel, for an update at the absolute INPUT index abs_at, the first of these that applies:
+ *     SHORT   n < min_products: nothing changes, the record keeps accumulating;  n_short += 1
+ *     REJECT  pow <= 0, or hypot(re, im) / pow < coh_min_q15 / 32768 (compared in integers, 3.0g): the record is zeroed, the step
+ *             stays;  n_rejected += 1
+ *     APPLY   theta = the angle of (re, im) in 2^-32 turns (a 32-iteration CORDIC on 64-bit integers, 3.0g; within 2^-32 turn);
+ *             e = round_half_away(theta L / (M D));  d = clamp((e gain_q16 + 2^15) >> 16, +-max_pull);
+ *             step' = clamp(step + d, step_ref +- max_dev), then to int32;  ph0' = ph0 + (step - step') abs_at (mod 2^32), part 1's
+ *             rule;  the record is zeroed;  n_applied += 1;  last_theta = theta, last_dstep = d
+ * step_ref is the channel's step when the loop was made.  A positive theta (the signal above the channel's centre) raises the step:
+ * the sign of step + p25fe_nco_step(fs, hz) on part 2's estimate.  The names do not begin with p25fe_afc_: the loop is an object of
+ * its own that holds a tuner and a measure. */
+#define P25FE_TRACK_NONE   0      /* status: no update yet */
+#define P25FE_TRACK_SHORT  1
+#define P25FE_TRACK_REJECT 2
+#define P25FE_TRACK_APPLY  3
+typedef struct p25fe_track p25fe_track_t;
+typedef struct p25fe_track_cfg {
+    int32_t shift;           /* Q's shift of the loop's measure, 0 .. P25FE_AFC_MAX_SHIFT (recommended: 24) */
+    int32_t coh_min_q15;     /* coherence gate, 0 .. 32768 (recommended: 24576 = 0.75) */
+    int32_t gain_q16;        /* loop gain, 1 .. 65536 (recommended: 65536 = 1) */
+    int32_t max_pull;        /* largest change of the step in one update, > 0 */
+    int32_t max_dev;         /* largest distance of the step from step_ref, > 0 */
+    int32_t reserved;        /* 0 */
+    uint64_t min_products;   /* products a record needs before it is judged, >= 1 (recommended: half a window's) */
+} p25fe_track_cfg_t;         /* 32 bytes */
+typedef struct p25fe_track_state {
+    int32_t step;            /* the channel's current step ... */
+    uint32_t ph0;            /* ... and phase offset (part 1) */
+    int32_t last_theta;      /* the last applied angle, 2^-32 turns per D samples at 240 ksps */
+    int32_t last_dstep;      /* the last applied change of the step, before the max_dev clamp */
+    uint32_t n_applied, n_rejected, n_short;   /* wrapping counts of the outcomes */
+    uint32_t status;         /* the last outcome, P25FE_TRACK_* */
+} p25fe_track_state_t;       /* 32 bytes */
+
+/* A loop over the NCO tuner tn and the measure afc, which must be of the same handle and have the same channel count; both must
+ * outlive every use of it, and a tuner has one loop at a time.  The loop owns zeroed records d_acc[K] and the states d_state[K],
+ * made from the (step, ph0) the host holds.  Every argument is checked before any device is touched.  P25FE_ERR_ARG: a null
+ * pointer, a rational tuner, a tuner whose host pair is stale (below), different handles or channel counts, a configuration
+ * outside the ranges above (reserved != 0 among them). */
+int p25fe_track_create(p25fe_tuner_t *tn, p25fe_afc_t *afc, const p25fe_track_cfg_t *cfg, p25fe_track_t **out);
+void p25fe_track_destroy(p25fe_track_t *lp);
+/* The loop's K open records, synchronously: waits for the device, copies them to `get` (nullable), then overwrites them from `set`
+ * (nullable) -- for a caller that reports a window's coherence before the update closes it, or opens a window with records of its
+ * own.  P25FE_ERR_ARG: a null loop. */
+int p25fe_track_records(p25fe_track_t *lp, p25fe_afc_acc_t *get, const p25fe_afc_acc_t *set);
+/* p25fe_afc_measure_dev into the loop's own records with the configuration's shift: same arguments, same refusals. */
+int p25fe_track_measure_dev(p25fe_track_t *lp, const float *d_rows, size_t row_stride, size_t n_hist, size_t n, uint64_t abs_first,
+                            void *stream);
+/* The one launch of k_afc_loop: every channel's update at abs_at, ordered on `stream` behind the measure launches that fed the
+ * records and in front of the next p25fe_tune_dev, as p25fe_afc_set_step is (a null stream is treated as there).  Synchronises
+ * nothing.  From the first call on, the (step, ph0) the host holds for tn are STALE until p25fe_track_read: p25fe_afc_set_step and
+ * p25fe_afc_get_step refuse.  P25FE_ERR_ARG: a null loop, abs_at >= 2^62. */
+int p25fe_track_update_dev(p25fe_track_t *lp, uint64_t abs_at, void *stream);
+/* The sequencer for a device-resident range of the capture (p25fe_tune_dev's conventions for d_iq, fmt, n_hist, n, abs_first,
+ * d_out, out_stride).  The range is cut at the absolute multiples of `window` input samples; for each piece it enqueues
+ * p25fe_tune_dev, then the measure of the rows just written, then, where the piece ends on a multiple of `window`, the update at
+ * that index.  A trailing partial window is tuned and measured but not updated: the next call continues it.  n_hist_out is the
+ * number of valid OUTPUT samples in front of d_out (the measure's T - 1 + D history; what is missing reads as zero).  The rows
+ * and states a stream leaves are the same bits for any split of it into calls that keep the alignment; `window` is part of the
+ * definition, like D.  Writes exactly p25fe_n_resample(L, M, abs_first, n) samples per row.  Marks the host pair stale as
+ * p25fe_track_update_dev does.  P25FE_ERR_ARG: p25fe_tune_dev's refusals for the whole range; window or abs_first not a multiple
+ * of the format's 16-byte vector (2 / 4 / 8 samples for cf32 / s16 / u8: multiples of 8 serve every format); window < T - 1 of the
+ * tuner or window >= 2^62. */
+int p25fe_track_run_dev(p25fe_track_t *lp, const void *d_iq, int fmt, size_t n_hist, size_t n, uint64_t abs_first, uint64_t window,
+                        float *d_out, size_t out_stride, size_t n_hist_out, void *stream);
+/* Synchronous: waits for the device, copies the K state records to state_out (nullable) and refreshes the (step, ph0) the host
+ * holds for every channel of tn, after which p25fe_afc_set_step / p25fe_afc_get_step work again.  The kernel takes a channel's
+ * (step, ph0) from the tuner's device record, so the next update goes on from what a p25fe_afc_set_step after the read left there
+ * (step_ref stays).  P25FE_ERR_ARG: a null loop. */
+int p25fe_track_read(p25fe_track_t *lp, p25fe_track_state_t *state_out);
+/* One channel's update on the host with exactly the kernel's operations (the same function compiled for both); no device needed.
+ * acc_out / state_out may alias the inputs.  P25FE_ERR_ARG: a null pointer, a configuration outside the ranges, a ratio L / M
+ * outside the resampler's limits, D outside the measure's. */
+int p25fe_track_step(const p25fe_track_cfg_t *cfg, int32_t L, int32_t M, int32_t D, int32_t step_ref, const p25fe_afc_acc_t *acc_in,
+                     const p25fe_track_state_t *state_in, uint64_t abs_at, p25fe_afc_acc_t *acc_out, p25fe_track_state_t *state_out);
+/* hz = last_theta / 2^32 * 240000 / D, for reports.  Host only.  P25FE_ERR_ARG: a null pointer, D outside the limits. */
+int p25fe_track_hz(const p25fe_track_state_t *state, int32_t D, double *hz);
 
 /* stages 6-7 on device baseband.  d_bb points at the first owned sample; n_hist_bb valid
  * samples precede it; abs_bb0 is its absolute index; d_anchor_in (nullable = no lock) is the

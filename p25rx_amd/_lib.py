@@ -66,6 +66,12 @@ assert CHAN_STATS_DTYPE.itemsize == 64
 assert ANCHOR_DTYPE.itemsize == C.sizeof(Anchor) and RESULT_DTYPE.itemsize == C.sizeof(Result)
 AFC_ACC_DTYPE = np.dtype([("re", "<i8"), ("im", "<i8"), ("pow", "<i8"), ("n", "<u8")])      # p25fe_afc_acc_t
 assert AFC_ACC_DTYPE.itemsize == 32
+TRACK_CFG_DTYPE = np.dtype([("shift", "<i4"), ("coh_min_q15", "<i4"), ("gain_q16", "<i4"), ("max_pull", "<i4"), ("max_dev", "<i4"),
+                            ("reserved", "<i4"), ("min_products", "<u8")])                     # p25fe_track_cfg_t
+TRACK_STATE_DTYPE = np.dtype([("step", "<i4"), ("ph0", "<u4"), ("last_theta", "<i4"), ("last_dstep", "<i4"), ("n_applied", "<u4"),
+                              ("n_rejected", "<u4"), ("n_short", "<u4"), ("status", "<u4")])    # p25fe_track_state_t
+assert TRACK_CFG_DTYPE.itemsize == 32 and TRACK_STATE_DTYPE.itemsize == 32
+TRACK_NONE, TRACK_SHORT, TRACK_REJECT, TRACK_APPLY = 0, 1, 2, 3     # p25fe_track_state_t.status
 
 # every symbol include/p25fe.h declares (tests check the library exports exactly these)
 SYMBOLS = [
@@ -88,6 +94,8 @@ SYMBOLS = [
     "p25fe_nco_step", "p25fe_nco_factor", "p25fe_nco_create",
     "p25fe_afc_set_step", "p25fe_afc_get_step", "p25fe_afc_factor", "p25fe_afc_design", "p25fe_afc_create", "p25fe_afc_destroy",
     "p25fe_afc_measure_dev", "p25fe_afc_hz",
+    "p25fe_track_create", "p25fe_track_destroy", "p25fe_track_records", "p25fe_track_measure_dev", "p25fe_track_update_dev", "p25fe_track_run_dev",
+    "p25fe_track_read", "p25fe_track_step", "p25fe_track_hz",
     "p25fe_debug_planes_size", "p25fe_debug_planes_dev",
 ]
 
@@ -215,6 +223,16 @@ def load():
     L.p25fe_afc_destroy.restype = None
     L.p25fe_afc_measure_dev.argtypes = [vp, vp, sz, sz, sz, u64, C.c_int32, vp, vp]
     L.p25fe_afc_hz.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.p25fe_track_create.argtypes = [vp, vp, vp, C.POINTER(vp)]
+    L.p25fe_track_destroy.argtypes = [vp]
+    L.p25fe_track_destroy.restype = None
+    L.p25fe_track_records.argtypes = [vp, vp, vp]
+    L.p25fe_track_measure_dev.argtypes = [vp, vp, sz, sz, sz, u64, vp]
+    L.p25fe_track_update_dev.argtypes = [vp, u64, vp]
+    L.p25fe_track_run_dev.argtypes = [vp, vp, C.c_int, sz, sz, u64, u64, vp, sz, sz, vp]
+    L.p25fe_track_read.argtypes = [vp, vp]
+    L.p25fe_track_step.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, u64, vp, vp]
+    L.p25fe_track_hz.argtypes = [vp, C.c_int32, C.POINTER(C.c_double)]
     L.p25fe_n_predecim.argtypes = [u64, sz]
     L.p25fe_n_predecim.restype = sz
     L.p25fe_n_baseband.argtypes = [u64, sz]

@@ -1386,6 +1386,7 @@ struct p25fe_tuner : RsCore {
     std::vector<int32_t> step;             // NCO channels: the current step ...
     std::vector<uint32_t> ph0;             // ... and phase offset of every channel, as the launches issued from now on see them
     hipEvent_t ev = nullptr;               // orders a record's update between the handle's stream and the default stream (made on first use)
+    bool stale = false;                    // a tracking loop has rewritten the device records since step / ph0 were last read back
     ~p25fe_tuner() { if (ev) (void)hipEventDestroy(ev); }
 };
 // The frequency measure of SPEC 3.0f (kernel: k_afc_measure): the prefilter's taps on the device and the shape
@@ -1395,6 +1396,18 @@ struct p25fe_afc {
     int D = 0, T = 0, K = 0;
     DevBuf d_taps;
 };
+// The tracking loop of SPEC 3.0g (kernel: k_afc_loop): a tuner of NCO channels, a measure, and per channel the open record, the
+// state and the step the loop was made at, all on the device
+struct p25fe_track {
+    p25fe_t* h = nullptr;
+    int device = 0;
+    p25fe_tuner* tn = nullptr;
+    p25fe_afc* afc = nullptr;
+    p25fe_track_cfg_t cfg{};
+    int K = 0;
+    DevBuf d_acc, d_state, d_ref;
+};
+static_assert(sizeof(p25fe_track_cfg_t) == 32 && sizeof(p25fe_track_state_t) == 32 && sizeof(p25fe_afc_acc_t) == 32, "32-byte records");
 static bool afc_shape_ok(int64_t D, int64_t T)
 {
     return D >= P25FE_AFC_MIN_D && D <= P25FE_AFC_MAX_D && T >= 1 && T <= P25FE_AFC_MAX_T;
@@ -1813,6 +1826,7 @@ int p25fe_afc_factor(int32_t step, uint32_t ph0, uint64_t n, float cs[2])
 int p25fe_afc_set_step(p25fe_tuner_t* tn, int32_t k, int32_t step, uint64_t abs_at, void* stream)
 {
     if (!tn || !tn->h || tn->mix != MIX_NCO || k < 0 || k >= tn->K || position_refused(abs_at)) return P25FE_ERR_ARG;
+    if (tn->stale) return P25FE_ERR_ARG;                            // the device has newer numbers than the host (p25fe_track_read)
     p25fe_t* h = tn->h;
     // the phase at abs_at stays: ph0 + step_old abs_at = ph0' + step abs_at (mod 2^32)
     const uint32_t ph0 = tn->ph0[(size_t)k] + ((uint32_t)tn->step[(size_t)k] - (uint32_t)step) * (uint32_t)abs_at;
@@ -1840,7 +1854,7 @@ int p25fe_afc_set_step(p25fe_tuner_t* tn, int32_t k, int32_t step, uint64_t abs_
 
 int p25fe_afc_get_step(const p25fe_tuner_t* tn, int32_t k, int32_t* step, uint32_t* ph0)
 {
-    if (!tn || tn->mix != MIX_NCO || k < 0 || k >= tn->K || !step || !ph0) return P25FE_ERR_ARG;
+    if (!tn || tn->mix != MIX_NCO || k < 0 || k >= tn->K || !step || !ph0 || tn->stale) return P25FE_ERR_ARG;
     *step = tn->step[(size_t)k]; *ph0 = tn->ph0[(size_t)k];
     return P25FE_OK;
 }
@@ -1911,6 +1925,153 @@ int p25fe_afc_hz(const p25fe_afc_acc_t* acc, int32_t D, double* hz, double* cohe
     const double re = (double)acc->re, im = (double)acc->im;
     *hz = atan2(im, re) / (2.0 * 3.14159265358979323846) * (double)P25FE_RS_RATE_OUT_HZ / (double)D;
     *coherence = hypot(re, im) / (double)acc->pow;
+    return P25FE_OK;
+}
+
+// --------------------------------------------------------------------------------------------
+// AFC loop (SPEC 3.0g): the update of every channel on the device, and the sequencer tune -> measure -> update
+// --------------------------------------------------------------------------------------------
+static bool track_cfg_ok(const p25fe_track_cfg_t* c)
+{
+    return c && c->shift >= 0 && c->shift <= P25FE_AFC_MAX_SHIFT && c->coh_min_q15 >= 0 && c->coh_min_q15 <= 32768 &&
+           c->gain_q16 >= 1 && c->gain_q16 <= 65536 && c->max_pull > 0 && c->max_dev > 0 && c->reserved == 0 && c->min_products >= 1;
+}
+
+int p25fe_track_create(p25fe_tuner_t* tn, p25fe_afc_t* afc, const p25fe_track_cfg_t* cfg, p25fe_track_t** out)
+{
+    if (out) *out = nullptr;
+    if (!out || !tn || !afc || !track_cfg_ok(cfg)) return P25FE_ERR_ARG;
+    if (tn->mix != MIX_NCO || tn->stale || tn->K != afc->K || !tn->h || tn->h != afc->h) return P25FE_ERR_ARG;
+    p25fe_t* h = tn->h;
+    p25fe_track* o = new (std::nothrow) p25fe_track;
+    if (!o) return P25FE_ERR_NOMEM;
+    o->h = h; o->device = h->cfg.device; o->tn = tn; o->afc = afc; o->cfg = *cfg; o->K = tn->K;
+    const size_t K = (size_t)o->K;
+    std::vector<p25fe_track_state_t> st(K);
+    for (size_t k = 0; k < K; ++k) { st[k] = p25fe_track_state_t{}; st[k].step = tn->step[k]; st[k].ph0 = tn->ph0[k]; }
+    if (hipSetDevice(h->cfg.device) != hipSuccess || o->d_acc.ensure(K * sizeof(p25fe_afc_acc_t)) != hipSuccess ||
+        o->d_state.ensure(K * sizeof(p25fe_track_state_t)) != hipSuccess || o->d_ref.ensure(K * sizeof(int32_t)) != hipSuccess ||
+        hipMemset(o->d_acc.p, 0, K * sizeof(p25fe_afc_acc_t)) != hipSuccess ||
+        hipMemcpy(o->d_state.p, st.data(), K * sizeof(p25fe_track_state_t), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(o->d_ref.p, tn->step.data(), K * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess ||
+        hipDeviceSynchronize() != hipSuccess) {
+        h->last_hip = (int)hipGetLastError(); delete o; return P25FE_ERR_HIP;
+    }
+    *out = o;
+    return P25FE_OK;
+}
+
+void p25fe_track_destroy(p25fe_track_t* lp) { rs_destroy(lp); }
+
+int p25fe_track_records(p25fe_track_t* lp, p25fe_afc_acc_t* get, const p25fe_afc_acc_t* set)
+{
+    if (!lp) return P25FE_ERR_ARG;
+    p25fe_t* h = lp->h;
+    const size_t bytes = (size_t)lp->K * sizeof(p25fe_afc_acc_t);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipDeviceSynchronize());
+    if (get) HIPCHK(h, hipMemcpy(get, lp->d_acc.p, bytes, hipMemcpyDeviceToHost));
+    if (set) HIPCHK(h, hipMemcpy(lp->d_acc.p, set, bytes, hipMemcpyHostToDevice));
+    return P25FE_OK;
+}
+
+int p25fe_track_measure_dev(p25fe_track_t* lp, const float* d_rows, size_t row_stride, size_t n_hist, size_t n, uint64_t abs_first,
+                            void* stream)
+{
+    if (!lp) return P25FE_ERR_ARG;
+    return p25fe_afc_measure_dev(lp->afc, d_rows, row_stride, n_hist, n, abs_first, lp->cfg.shift, lp->d_acc.as<p25fe_afc_acc_t>(), stream);
+}
+
+int p25fe_track_update_dev(p25fe_track_t* lp, uint64_t abs_at, void* stream)
+{
+    if (!lp || position_refused(abs_at)) return P25FE_ERR_ARG;
+    p25fe_t* h = lp->h;
+    p25fe_tuner* tn = lp->tn;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    (void)hipGetLastError();
+    // the ordering of p25fe_afc_set_step: a null stream is the handle's, ordered against the default stream on both sides
+    const hipStream_t st = stream ? (hipStream_t)stream : h->stream;
+    if (!stream) {
+        if (!tn->ev) HIPCHK(h, hipEventCreateWithFlags(&tn->ev, hipEventDisableTiming));
+        HIPCHK(h, hipEventRecord(tn->ev, nullptr));
+        HIPCHK(h, hipStreamWaitEvent(st, tn->ev, 0));
+    }
+    AfcLoopArgs a;
+    a.cfg = lp->cfg; a.L = tn->L; a.M = tn->M; a.D = lp->afc->D; a.K = lp->K;
+    a.step_ref = lp->d_ref.as<int32_t>(); a.acc = lp->d_acc.as<p25fe_afc_acc_t>(); a.state = lp->d_state.as<p25fe_track_state_t>();
+    a.ch = tn->d_ch.as<TuneCh>(); a.abs_at = (unsigned long)abs_at;
+    tn->stale = true;                                               // from here on the device's numbers are the newer ones
+    hipLaunchKernelGGL(k_afc_loop, dim3(1), dim3((unsigned)round_up((size_t)lp->K, (size_t)WV)), 0, st, a);
+    HIPCHK(h, hipGetLastError());
+    if (!stream) {
+        HIPCHK(h, hipEventRecord(tn->ev, st));
+        HIPCHK(h, hipStreamWaitEvent(nullptr, tn->ev, 0));
+    }
+    return P25FE_OK;
+}
+
+int p25fe_track_run_dev(p25fe_track_t* lp, const void* d_iq, int fmt, size_t n_hist, size_t n, uint64_t abs_first, uint64_t window,
+                        float* d_out, size_t out_stride, size_t n_hist_out, void* stream)
+{
+    if (!lp || !wide_fmt_known(fmt)) return P25FE_ERR_ARG;
+    p25fe_tuner* tn = lp->tn;
+    if (rs_pointers_refused(tn, d_iq, fmt, 0, abs_first, d_out) || n >= P25FE_MAX_POSITION) return P25FE_ERR_ARG;
+    // every piece starts on an aligned 16-byte vector of the input, and a window holds at least the tuner's history
+    const uint64_t unit = fmt_stride_unit(fmt);
+    if (window >= P25FE_MAX_POSITION || window == 0 || window % unit != 0 || abs_first % unit != 0 || window + 1 < (uint64_t)tn->T)
+        return P25FE_ERR_ARG;
+    const uint64_t L = (uint64_t)tn->L, M = (uint64_t)tn->M;
+    if (out_stride < p25fe_n_resample(tn->L, tn->M, abs_first, n)) return P25FE_ERR_ARG;
+    const uint64_t end = abs_first + n, out_first = rs_floor(abs_first, L, M);
+    const unsigned char* src = static_cast<const unsigned char*>(d_iq);
+    for (uint64_t a = abs_first; a < end;) {
+        const uint64_t b = std::min(end, (a / window + 1) * window);
+        const size_t off = (size_t)(a - abs_first), len = (size_t)(b - a);
+        const size_t out_off = (size_t)(rs_floor(a, L, M) - out_first), cnt = p25fe_n_resample(tn->L, tn->M, a, len);
+        float* rows = d_out + 2 * out_off;
+        if (int rc = rs_launch(tn, tn, src + off * fmt_bytes(fmt), fmt, 0, n_hist + off, len, a, rows, out_stride, (hipStream_t)stream)) return rc;
+        if (int rc = p25fe_track_measure_dev(lp, rows, out_stride, n_hist_out + out_off, cnt, out_first + out_off, stream)) return rc;
+        if (b % window == 0) if (int rc = p25fe_track_update_dev(lp, b, stream)) return rc;
+        a = b;
+    }
+    return P25FE_OK;
+}
+
+int p25fe_track_read(p25fe_track_t* lp, p25fe_track_state_t* state_out)
+{
+    if (!lp) return P25FE_ERR_ARG;
+    p25fe_t* h = lp->h;
+    p25fe_tuner* tn = lp->tn;
+    const size_t K = (size_t)lp->K;
+    std::vector<p25fe_track_state_t> st(K);
+    std::vector<TuneCh> ch(K);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipDeviceSynchronize());                              // whatever stream the updates went to
+    HIPCHK(h, hipMemcpy(st.data(), lp->d_state.p, K * sizeof(p25fe_track_state_t), hipMemcpyDeviceToHost));
+    HIPCHK(h, hipMemcpy(ch.data(), tn->d_ch.p, K * sizeof(TuneCh), hipMemcpyDeviceToHost));
+    // the tuner's record is what runs: a p25fe_afc_set_step after the last update shows there and not in the state
+    for (size_t k = 0; k < K; ++k) { st[k].step = tn->step[k] = ch[k].step; st[k].ph0 = tn->ph0[k] = ch[k].ph0; }
+    tn->stale = false;
+    if (state_out) memcpy(state_out, st.data(), K * sizeof(p25fe_track_state_t));
+    return P25FE_OK;
+}
+
+int p25fe_track_step(const p25fe_track_cfg_t* cfg, int32_t L, int32_t M, int32_t D, int32_t step_ref, const p25fe_afc_acc_t* acc_in,
+                     const p25fe_track_state_t* state_in, uint64_t abs_at, p25fe_afc_acc_t* acc_out, p25fe_track_state_t* state_out)
+{
+    if (!track_cfg_ok(cfg) || !rs_ratio_ok(L, M) || D < P25FE_AFC_MIN_D || D > P25FE_AFC_MAX_D || !acc_in || !state_in || !acc_out ||
+        !state_out) return P25FE_ERR_ARG;
+    p25fe_afc_acc_t acc = *acc_in;
+    p25fe_track_state_t st = *state_in;
+    afc_loop_law(*cfg, L, M, D, step_ref, abs_at, acc, st);
+    *acc_out = acc; *state_out = st;
+    return P25FE_OK;
+}
+
+int p25fe_track_hz(const p25fe_track_state_t* state, int32_t D, double* hz)
+{
+    if (!state || !hz || D < P25FE_AFC_MIN_D || D > P25FE_AFC_MAX_D) return P25FE_ERR_ARG;
+    *hz = ldexp((double)state->last_theta, -32) * (double)P25FE_RS_RATE_OUT_HZ / (double)D;
     return P25FE_OK;
 }
 

@@ -1886,6 +1886,111 @@ __global__ void k_afc_set_ch(TuneCh* ch, int step, unsigned ph0)
 }
 
 // ------------------------------------------------------------------------------------------
+// The AFC loop (SPEC 3.0g; kernel: k_afc_loop): one channel's update as ONE function for the device and the host
+// (p25fe_track_step), 64-bit integers only.  Wrapping sums go through unsigned types, right shifts of signed values are arithmetic
+// (floor), and no intermediate of the signed paths passes 2^63 - 1 (SPEC 3.0g gives the bounds).
+// ------------------------------------------------------------------------------------------
+__host__ __device__ __forceinline__ int afc_bitlen(uint64_t v) { return v ? 64 - __builtin_clzll(v) : 0; }
+__host__ __device__ __forceinline__ uint64_t afc_abs(int64_t v) { return v < 0 ? 0 - (uint64_t)v : (uint64_t)v; }
+
+// the angle of (re, im) in 2^-32 turns, wrapped to int32 (a half turn is -2^31); (0, 0) -> 0
+__host__ __device__ __forceinline__ int32_t afc_loop_angle(int64_t re, int64_t im)
+{
+    const uint64_t ar = afc_abs(re), ai = afc_abs(im), big = ar > ai ? ar : ai;
+    if (big == 0) return 0;
+    // the larger component to exactly P25FE_AFC_CORDIC_NORM bits: the rotated pair then stays below 1.65 sqrt(2) 2^60 < 2^62
+    const int b = afc_bitlen(big);
+    int64_t x, y;
+    if (b > P25FE_AFC_CORDIC_NORM) { x = re >> (b - P25FE_AFC_CORDIC_NORM); y = im >> (b - P25FE_AFC_CORDIC_NORM); }
+    else {
+        x = (int64_t)((uint64_t)re << (P25FE_AFC_CORDIC_NORM - b));
+        y = (int64_t)((uint64_t)im << (P25FE_AFC_CORDIC_NORM - b));
+    }
+    // a quarter turn brings the left half plane to the right one
+    int64_t z = 0;
+    if (x < 0) {
+        const int64_t t = x;
+        if (y >= 0) { x = y; y = -t; z = 1ll << (P25FE_AFC_CORDIC_FRAC - 2); }
+        else { x = -y; y = t; z = -(1ll << (P25FE_AFC_CORDIC_FRAC - 2)); }
+    }
+#pragma unroll
+    for (int i = 0; i < P25FE_AFC_CORDIC_N; ++i) {
+        const int64_t xs = x >> i, ys = y >> i;
+        if (y >= 0) { x += ys; y -= xs; z += P25FE_AFC_CORDIC_ATAN[i]; }
+        else { x -= ys; y += xs; z -= P25FE_AFC_CORDIC_ATAN[i]; }
+    }
+    const int fr = P25FE_AFC_CORDIC_FRAC - 32;
+    return (int32_t)(uint32_t)(uint64_t)((z + (1ll << (fr - 1))) >> fr);
+}
+
+// hypot(re, im) / pw >= c / 32768 on the three magnitudes shifted right until the largest has 16 bits; pw > 0
+__host__ __device__ __forceinline__ bool afc_loop_coherent(int64_t re, int64_t im, int64_t pw, int32_t c)
+{
+    const uint64_t ar = afc_abs(re), ai = afc_abs(im), ap = (uint64_t)pw;
+    uint64_t big = ar > ai ? ar : ai;
+    big = big > ap ? big : ap;
+    const int b = afc_bitlen(big), s = b > 16 ? b - 16 : 0;
+    const uint64_t r = ar >> s, i = ai >> s, g = (uint64_t)c * (ap >> s);       // r, i < 2^16;  g < 2^31
+    return ((r * r + i * i) << 30) >= g * g;                                     // < 2^63 and < 2^62
+}
+
+__host__ __device__ __forceinline__ void afc_loop_law(const p25fe_track_cfg_t& cfg, int L, int M, int D, int32_t step_ref, uint64_t abs_at,
+                                             p25fe_afc_acc_t& acc, p25fe_track_state_t& st)
+{
+    const int64_t re = acc.re, im = acc.im, pw = acc.pow;
+    // the outcome first; the three counts then move by a comparison each (no indexed access to the record)
+    uint32_t outcome = P25FE_TRACK_APPLY;
+    if (acc.n < cfg.min_products) outcome = P25FE_TRACK_SHORT;
+    else if (pw <= 0 || !afc_loop_coherent(re, im, pw, cfg.coh_min_q15)) outcome = P25FE_TRACK_REJECT;
+    st.status = outcome;
+    st.n_short += outcome == P25FE_TRACK_SHORT ? 1u : 0u;
+    st.n_rejected += outcome == P25FE_TRACK_REJECT ? 1u : 0u;
+    st.n_applied += outcome == P25FE_TRACK_APPLY ? 1u : 0u;
+    if (outcome == P25FE_TRACK_SHORT) return;
+    acc.re = 0; acc.im = 0; acc.pow = 0; acc.n = 0;                  // either outcome from here on closes the window
+    if (outcome == P25FE_TRACK_REJECT) return;
+    const int32_t theta = afc_loop_angle(re, im);
+    // theta turns / 2^32 per D samples at 240 ksps, in steps of fs_in / 2^32: theta L / (M D), halves away from zero
+    const int64_t num = (int64_t)theta * L, den = (int64_t)M * D, an = num < 0 ? -num : num;
+    int64_t e = (2 * an + den) / (2 * den);
+    if (num < 0) e = -e;
+    int64_t d = (e * cfg.gain_q16 + 32768) >> 16;
+    d = d > cfg.max_pull ? cfg.max_pull : (d < -(int64_t)cfg.max_pull ? -(int64_t)cfg.max_pull : d);
+    int64_t ns = (int64_t)st.step + d;
+    const int64_t lo = (int64_t)step_ref - cfg.max_dev, hi = (int64_t)step_ref + cfg.max_dev;
+    ns = ns < lo ? lo : (ns > hi ? hi : ns);
+    ns = ns < -2147483648ll ? -2147483648ll : (ns > 2147483647ll ? 2147483647ll : ns);
+    st.ph0 += ((uint32_t)st.step - (uint32_t)(int32_t)ns) * (uint32_t)abs_at;   // the phase at abs_at stays (SPEC 3.0e)
+    st.step = (int32_t)ns;
+    st.last_theta = theta; st.last_dstep = (int32_t)d;
+}
+
+struct AfcLoopArgs {
+    p25fe_track_cfg_t cfg;
+    int L, M, D, K;
+    const int32_t* step_ref;        // [K]
+    p25fe_afc_acc_t* acc;           // [K]
+    p25fe_track_state_t* state;     // [K]
+    TuneCh* ch;                     // [K], NCO channels
+    unsigned long abs_at;
+};
+// Every channel's update in one launch, one thread per channel, in stream order as k_afc_set_ch: the measure launches before it
+// have added to acc, the tuner launches after it read the new (step, ph0).  The channel's numbers are read from its TuneCh (what
+// the tuner runs with, a p25fe_afc_set_step after a read included) and written there and to the state record.
+__global__ __launch_bounds__(256) void k_afc_loop(AfcLoopArgs a)
+{
+    const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (k >= a.K) return;
+    p25fe_afc_acc_t acc = a.acc[k];
+    p25fe_track_state_t st = a.state[k];
+    st.step = a.ch[k].step; st.ph0 = a.ch[k].ph0;
+    afc_loop_law(a.cfg, a.L, a.M, a.D, a.step_ref[k], a.abs_at, acc, st);
+    if (st.status != P25FE_TRACK_SHORT) a.acc[k] = acc;
+    a.state[k] = st;
+    a.ch[k].step = st.step; a.ch[k].ph0 = st.ph0;
+}
+
+// ------------------------------------------------------------------------------------------
 // K0d: frequency measure (SPEC 3.0f): K rows at 240 ksps -> per row the integer sums of w[m] conj(w[m-1]) and |w[m]|^2 over a
 // range, w = the row through a caller-supplied real FIR decimated by D (the L = 1 case of 3.0b: the channel-selective filter
 // the tuner's 60 kHz table is not).  One wave per workgroup, grid (tiles, K).  A tile stages its cf32 window and the taps in LDS

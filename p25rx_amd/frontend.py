@@ -833,3 +833,106 @@ class Afc:
     def records(acc):
         """the device records -> NumPy structured array [K] (syncs the stream)"""
         return np.frombuffer(acc.cpu().numpy().tobytes(), dtype=_lib.AFC_ACC_DTYPE).copy()
+
+
+class AfcLoop:
+    """The AFC loop of docs/SPEC.md 3.0g (p25fe_track_t): every channel's (step, ph0) of an NCO Tuner updated on the device from the
+    records of an Afc's measure, in stream order -- tune -> measure -> update -> tune with no record read by the host.  cfg: shift,
+    min_products, coh_min_q15, gain_q16, max_pull, max_dev (p25fe_track_cfg_t).  The tuner and the measure must outlive it.  After
+    update / tune_tracked_dev the tuner's set_step / get_step refuse until read()."""
+
+    DEFAULT = dict(shift=24, min_products=600, coh_min_q15=24576, gain_q16=65536, max_pull=1 << 24, max_dev=1 << 24)
+    STATUS = {_lib.TRACK_NONE: "none", _lib.TRACK_SHORT: "short", _lib.TRACK_REJECT: "reject", _lib.TRACK_APPLY: "apply"}
+
+    @staticmethod
+    def config(**cfg):
+        """a p25fe_track_cfg_t (TRACK_CFG_DTYPE [1]) from DEFAULT and the overrides"""
+        c = np.zeros(1, dtype=_lib.TRACK_CFG_DTYPE)
+        for k, v in dict(AfcLoop.DEFAULT, **cfg).items():
+            c[k] = v
+        return c
+
+    @staticmethod
+    def step(cfg, L, M, D, step_ref, acc, state, abs_at):
+        """one channel's update on the host with the kernel's operations (p25fe_track_step): (acc', state')"""
+        L_ = _lib.load()
+        c = cfg if isinstance(cfg, np.ndarray) else AfcLoop.config(**cfg)
+        a, s = np.zeros(1, dtype=_lib.AFC_ACC_DTYPE), np.zeros(1, dtype=_lib.TRACK_STATE_DTYPE)
+        a[0] = tuple(acc)
+        s[0] = tuple(state[f] for f in _lib.TRACK_STATE_DTYPE.names) if isinstance(state, dict) else tuple(state)
+        _lib.check(L_, None, L_.p25fe_track_step(_p(c), int(L), int(M), int(D), int(step_ref), _p(a), _p(s), int(abs_at), _p(a), _p(s)))
+        return a[0].copy(), s[0].copy()
+
+    @staticmethod
+    def hz(state, D):
+        """last_theta of a state record in Hz (p25fe_track_hz)"""
+        L_ = _lib.load()
+        s = np.zeros(1, dtype=_lib.TRACK_STATE_DTYPE)
+        s[0] = tuple(state[f] for f in _lib.TRACK_STATE_DTYPE.names) if isinstance(state, dict) else tuple(state)
+        hz = C.c_double(0.0)
+        _lib.check(L_, None, L_.p25fe_track_hz(_p(s), int(D), C.byref(hz)))
+        return hz.value
+
+    def __init__(self, tuner, afc, **cfg):
+        self.tuner, self.afc, self.fe, self.lib = tuner, afc, tuner.fe, tuner.fe.L
+        self.K = tuner.K
+        self.cfg = AfcLoop.config(**cfg)
+        self.lp = C.c_void_p()
+        _lib.check(self.lib, self.fe.h, self.lib.p25fe_track_create(tuner.tn, afc.afc, _p(self.cfg), C.byref(self.lp)))
+
+    def close(self):
+        if getattr(self, "lp", None):
+            self.lib.p25fe_track_destroy(self.lp)
+            self.lp = None
+
+    __del__ = close
+
+    def measure(self, rows, n_hist=0, abs0=0, offset=0, n=None):
+        """Afc.measure into the loop's own records with the configuration's shift"""
+        assert rows.is_cuda and rows.dim() == 3 and rows.shape[0] == self.K and rows.shape[2] == 2 and rows.stride(2) == 1
+        assert rows.stride(1) == 2 and rows.stride(0) % 2 == 0
+        if n is None:
+            n = rows.shape[1] - offset
+        assert 0 <= n_hist <= offset and offset + n <= rows.shape[1]
+        _lib.check(self.lib, self.fe.h,
+                   self.lib.p25fe_track_measure_dev(self.lp, C.c_void_p(rows.data_ptr() + 8 * offset), rows.stride(0) // 2, n_hist, n, abs0,
+                                                    self.fe._stream()))
+
+    def records(self, set=None):
+        """the K open records (AFC_ACC_DTYPE [K]), then overwritten from `set` when given (p25fe_track_records; synchronous)"""
+        got = np.zeros(self.K, dtype=_lib.AFC_ACC_DTYPE)
+        new = None
+        if set is not None:
+            new = np.ascontiguousarray(set, dtype=_lib.AFC_ACC_DTYPE)
+            assert new.shape == (self.K,)
+        _lib.check(self.lib, self.fe.h, self.lib.p25fe_track_records(self.lp, _p(got), None if new is None else _p(new)))
+        return got
+
+    def update(self, abs_at):
+        """every channel's update at the absolute input index abs_at: one launch on the current stream, nothing synchronised"""
+        _lib.check(self.lib, self.fe.h, self.lib.p25fe_track_update_dev(self.lp, int(abs_at), self.fe._stream()))
+
+    def tune_tracked_dev(self, iq, window, n_hist=0, abs0=0, offset=0, out=None, out_offset=0, n_hist_out=0):
+        """Tuner.tune_dev with the loop closed (p25fe_track_run_dev): the range is cut at the absolute multiples of `window` input
+        samples, each piece tuned and measured, every boundary reached updated.  out (cf32 [K, cols, 2]) receives the rows from
+        column out_offset on, n_hist_out valid columns before it.  -> (out, n_out)"""
+        import torch
+        assert iq.is_cuda and iq.dim() == 2 and iq.shape[1] == 2 and iq.is_contiguous()
+        fmt = _torch_fmt(iq.dtype)
+        n = iq.shape[0] - offset
+        no = self.tuner.n_out(abs0, n)
+        if out is None:
+            out = torch.empty((self.K, out_offset + (no + 3) // 2 * 2, 2), dtype=torch.float32, device=iq.device)
+        assert n_hist_out <= out_offset and out_offset + no <= out.shape[1]
+        _lib.check(self.lib, self.fe.h,
+                   self.lib.p25fe_track_run_dev(self.lp, C.c_void_p(iq.data_ptr() + fmt_bytes(fmt) * offset), fmt, n_hist, n, abs0,
+                                                int(window), C.c_void_p(out.data_ptr() + 8 * out_offset), out.stride(0) // 2,
+                                                n_hist_out, self.fe._stream()))
+        return out, no
+
+    def read(self):
+        """the K state records (TRACK_STATE_DTYPE [K]); synchronous; the tuner's host pair is fresh again afterwards"""
+        st = np.zeros(self.K, dtype=_lib.TRACK_STATE_DTYPE)
+        _lib.check(self.lib, self.fe.h, self.lib.p25fe_track_read(self.lp, _p(st)))
+        self.tuner.steps = [int(s) for s in st["step"]]
+        return st

@@ -107,6 +107,16 @@ public:
     }
 };
 
+// the AFC loop over a tuner of NCO channels and a measure (p25fe_track_create); both must outlive it
+class Track : public Owned<p25fe_track_t, p25fe_track_destroy> {
+public:
+    Track() = default;
+    Track(const Tuner& tn, const FreqMeasure& afc, const p25fe_track_cfg_t& cfg)
+    {
+        expect(p25fe_track_create(tn.get(), afc.get(), &cfg, &p_), "unable to create the AFC loop");
+    }
+};
+
 // one chunk through stages 1-5, by the chunk's sample type: uint8_t pairs (the reference's reader), int16_t pairs (P25FE_FMT_S16)
 // or float pairs (cf32)
 inline int demod_chunk(p25fe_t* h, const std::vector<uint8_t>& iq, float* bb, size_t cap, size_t* n_out, float* power)

@@ -1,7 +1,7 @@
 // p25fe_replay -- file-in / file-out driver in the role of the reference's command line for this path
 // (src/main.rs:95-102, 162-175, 278-283 and src/replay.rs:26-57): a deterministic harness for the hot path.
 //
-//   p25fe_replay [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] [-r RATE_HZ [-f OFFSET_HZ | -F OFFSET_HZ [-a MS]]] u8|s16|cf32|bb <in> <dibits.out>
+//   p25fe_replay [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] [-r RATE_HZ [-f OFFSET_HZ | -F OFFSET_HZ [-a MS | -A MS]]] u8|s16|cf32|bb <in> <dibits.out>
 //   p25fe_replay -W WINDOW_BYTES u8|s16|cf32 <in> <dibits.out>
 //
 //     u8    RTL-SDR style interleaved u8 I/Q, the reference's live input (src/consts.rs:6: 32768-byte chunks)
@@ -38,6 +38,11 @@
 //               measures the tuned row's frequency error (docs/SPEC.md 3.0f, p25fe_afc_measure_dev, the recommended prefilter);
 //               then the channel's step is corrected ONCE by the estimate, without a phase jump (3.0e, p25fe_afc_set_step), and
 //               the stream carries on.  The estimate is printed, and goes to the -j events as {"event":"afc", ...}.
+//
+//     -A MS     with -F, instead of -a: the AFC loop (docs/SPEC.md 3.0g).  The measure runs on every chunk, reads are cut at the
+//               multiples of MS ms of input, and at each of them ONE kernel updates the channel's step on the device from the window's
+//               record (the recommended loop: gate 0.75, gain 1, half a window of products); the state is read back and printed as
+//               an {"event":"afc", ...} line per boundary, in -a's format plus "status".
 //
 //     -W BYTES  bulk mode for long captures (p25fe_run_host_windows): a READER THREAD fills pinned blocks of eight windows
 //               from the file while the library pipelines the previous block -- window k + 1 on its way to the GPU,
@@ -115,7 +120,7 @@ struct Sink {
 
 static int usage(const char* argv0)
 {
-    std::fprintf(stderr, "usage: %s [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] [-r RATE_HZ [-f OFFSET_HZ | -F OFFSET_HZ [-a MS]]] u8|s16|cf32|bb <in> <dibits.out>\n"
+    std::fprintf(stderr, "usage: %s [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] [-r RATE_HZ [-f OFFSET_HZ | -F OFFSET_HZ [-a MS | -A MS]]] u8|s16|cf32|bb <in> <dibits.out>\n"
                          "       %s -W WINDOW_BYTES u8|s16|cf32 <in> <dibits.out>\n", argv0, argv0);
     return 2;
 }
@@ -135,6 +140,7 @@ struct Options {
     unsigned long rate_hz = 0;                                        // -r; 0: the capture is at 240 ksps
     struct { enum { NONE, RATIONAL, NCO } kind = NONE; long long hz = 0; double nco_hz = 0.0; } offset;   // -f: hz; -F: nco_hz
     double afc_ms = 0.0;                                              // -a: measure the first MS ms at -F's offset, correct once
+    double track_ms = 0.0;                                            // -A: the loop, updated at every multiple of MS ms of input
     bool bb = false;                                                  // the mode: 48 kHz baseband, or ...
     int fmt = 0; size_t bps = 0;                                      // ... IQ in this format (P25FE_FMT_*) of this many bytes per sample
 };
@@ -156,6 +162,7 @@ static bool parse(int argc, char** argv, Options& o)
         else if (opt == "-f") { o.offset.hz = std::strtoll(val, nullptr, 10); f = true; }
         else if (opt == "-F") { if (!number(val, o.offset.nco_hz)) return false; F = true; }
         else if (opt == "-a") { if (!number(val, o.afc_ms) || !(o.afc_ms > 0.0) || o.afc_ms > 60000.0) return false; }
+        else if (opt == "-A") { if (!number(val, o.track_ms) || !(o.track_ms > 0.0) || o.track_ms > 60000.0) return false; }
         else if (opt == "-W") {
             char* end = nullptr;
             o.window_bytes = (size_t)std::strtoull(val, &end, 10);
@@ -164,6 +171,7 @@ static bool parse(int argc, char** argv, Options& o)
         else return false;
     }
     if (argc - a != 3 || o.batch == 0 || (f && F) || ((f || F) && !o.rate_hz) || (o.afc_ms > 0.0 && !F)) return false;
+    if (o.track_ms > 0.0 && (!F || o.afc_ms > 0.0)) return false;   // -A goes with -F and instead of -a
     o.offset.kind = F ? o.offset.NCO : (f ? o.offset.RATIONAL : o.offset.NONE);
     const std::string mode = argv[a];
     o.in_path = argv[a + 1]; o.out_path = argv[a + 2];
@@ -173,7 +181,7 @@ static bool parse(int argc, char** argv, Options& o)
     else if (mode == "bb") o.bb = true;
     else return false;
     if (o.bb && (o.rate_hz || o.window_bytes)) return false;         // the resampler, the tuner and the bulk mode take IQ
-    return !(o.window_bytes && (o.wpath || o.jpath || o.rate_hz || o.afc_ms > 0.0));
+    return !(o.window_bytes && (o.wpath || o.jpath || o.rate_hz || o.afc_ms > 0.0 || o.track_ms > 0.0));
 }
 
 // device memory (hipMalloc) or pinned host memory (hipHostMalloc); p is null when there was none: the caller has the message
@@ -279,8 +287,10 @@ static void demodulate(Handle& h, std::ifstream& in, Hub& hub, Chan<Baseband>& c
 class Afc {                                                           // (span: input samples to measure; cap240: the most tuned samples of one chunk)
     static constexpr int32_t D = 10, T = 240;
     static constexpr size_t KEEP = (size_t)(T - 1 + D);
-    size_t left_;                                                     // input samples still to measure
+    size_t left_;                                                     // input samples still to measure (-A: up to the next boundary)
+    size_t window_ = 0;                                               // -A: input samples between two updates (0: -a)
     FreqMeasure measure_;
+    Track loop_;                                                      // -A
     HipMem d_row_, d_acc_;
     std::vector<float> row_;                                          // [history | the chunk's tuned samples], as it goes to the device
     float* row() const { return static_cast<float*>(d_row_.p); }
@@ -295,6 +305,17 @@ public:
         if (!row() || !acc() || hipMemcpy(acc(), &zero, sizeof zero, hipMemcpyHostToDevice) != hipSuccess)
             fail("p25fe_replay: no device memory for the frequency measure\n");
     }
+    // -A: the recommended loop of SPEC 3.0g over tn, updated every `span` input samples; a pull or a deviation of at most 6.25 kHz
+    void track(const Tuner& tn, uint32_t rate_hz)
+    {
+        window_ = left_;
+        int32_t half_channel = 1 << 24;
+        (void)p25fe_nco_step(rate_hz, 6250.0, &half_channel);
+        const uint64_t half_window = (uint64_t)((double)window_ * 240000.0 / (double)rate_hz) / (uint64_t)D / 2;
+        const p25fe_track_cfg_t cfg = {24, 24576, 65536, std::max(half_channel, 1), std::max(half_channel, 1), 0, std::max<uint64_t>(half_window, 1)};
+        loop_ = Track(tn, measure_, cfg);
+    }
+    bool tracking() const { return window_ != 0; }
     bool over() const { return left_ == 0; }
     size_t chunk(size_t n_chunk) const { return left_ ? std::min(n_chunk, left_) : n_chunk; }   // input samples of the next read
     // one chunk: its n_in input samples (short_read: the capture ended in it) gave the tuned samples x240, the first at pos240
@@ -305,8 +326,32 @@ public:
         row_.insert(row_.end(), x240.begin(), x240.end());
         if (hipMemcpy(row(), row_.data(), row_.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
             fail("p25fe_replay: unable to copy the tuned row to the device\n");
+        if (tracking()) {
+            expect(p25fe_track_measure_dev(loop_.get(), row() + 2 * nh, 0, nh, x240.size() / 2, pos240, nullptr), "unable to measure the frequency");
+            left_ -= n_in;                                            // (a trailing partial window is measured and not updated)
+            return;
+        }
         expect(p25fe_afc_measure_dev(measure_.get(), row() + 2 * nh, 0, nh, x240.size() / 2, pos240, 24, acc(), nullptr), "unable to measure the frequency");
         left_ = short_read ? 0 : left_ - n_in;                        // (a capture shorter than MS ms: what there is)
+    }
+    // -A, a boundary: the window's record (for the report), the update on the device at input sample `at`, and the state it left
+    void update(uint64_t at, FILE* js)
+    {
+        static const char* const names[] = {"none", "short", "reject", "apply"};
+        p25fe_afc_acc_t a;
+        p25fe_track_state_t st;
+        double hz = 0.0, coherence = 0.0;
+        expect(p25fe_track_records(loop_.get(), &a, nullptr), "unable to read the frequency measure");
+        expect(p25fe_afc_hz(&a, D, &hz, &coherence), "unable to evaluate the frequency measure");
+        expect(p25fe_track_update_dev(loop_.get(), at, nullptr), "unable to update the loop");
+        expect(p25fe_track_read(loop_.get(), &st), "unable to read the loop's state");
+        const char* status = names[st.status & 3u];
+        std::fprintf(stderr, "p25fe_replay: afc: %.1f Hz off (coherence %.3f, %" PRIu64 " products): %s; step %d at sample %" PRIu64 "\n",
+                     hz, coherence, a.n, status, st.step, at);
+        if (js)
+            std::fprintf(js, "{\"event\":\"afc\",\"hz\":%.3f,\"coherence\":%.6f,\"products\":%" PRIu64 ",\"step\":%d,\"at\":%" PRIu64 ",\"status\":\"%s\"}\n",
+                         hz, coherence, a.n, st.step, at, status);
+        left_ = window_;
     }
     // the span is over: the estimate, reported on stderr and in the -j events, and the one correction from input sample `at` on
     int32_t correct(const Tuner& tn, uint32_t rate_hz, int32_t step, uint64_t at, FILE* js) const
@@ -361,6 +406,10 @@ public:
         n_chunk_ = (size_t)BUF_SAMPLES * o.batch * (size_t)M / (size_t)L;       // about one cf32-mode chunk of 240 ksps samples
         cap240_ = n_chunk_ * (size_t)L / (size_t)M + 2;
         if (o.afc_ms > 0.0) afc_.emplace(h, std::max<size_t>(1, (size_t)((double)o.rate_hz * o.afc_ms / 1000.0)), cap240_);
+        if (o.track_ms > 0.0) {
+            afc_.emplace(h, std::max<size_t>(1, (size_t)((double)o.rate_hz * o.track_ms / 1000.0)), cap240_);
+            afc_->track(tn_, rate);
+        }
     }
     size_t next_bytes() const { return (afc_ ? afc_->chunk(n_chunk_) : n_chunk_) * o_.bps; }
     std::vector<float> operator()(const std::vector<char>& raw)       // tune, measure, maybe retune
@@ -373,7 +422,10 @@ public:
         else expect(p25fe_resample(rs_.get(), raw.data(), o_.fmt, n, x240.data(), cap240_, &n240), "unable to resample");
         x240.resize(2 * n240);
         consumed_ += n;
-        if (afc_ && !afc_->over()) {
+        if (afc_ && afc_->tracking()) {
+            afc_->feed(x240, pos240_, n, short_read);
+            if (afc_->over()) afc_->update(consumed_, js_);
+        } else if (afc_ && !afc_->over()) {
             afc_->feed(x240, pos240_, n, short_read);
             if (afc_->over()) step_ = afc_->correct(tn_, (uint32_t)o_.rate_hz, step_, consumed_, js_);
         }

@@ -144,6 +144,30 @@ def hexf(x):
     return float(np.float32(x)).hex() + "f"
 
 
+CORDIC_N, CORDIC_NORM, CORDIC_FRAC = 32, 60, 48
+
+
+def cordic_atan_table():
+    """round(atan(2^-i) / (2 pi) * 2^48), i < 32, in exact rational arithmetic: the arctangent's alternating series (its truncation
+    error is below the first omitted term) and Machin's pi = 16 atan(1/5) - 4 atan(1/239), both carried to 2^-120"""
+    from fractions import Fraction
+
+    def atan_inv(q):                                                 # atan(1 / q), q >= 2
+        s, k, x = Fraction(0), 0, Fraction(1, q)
+        while True:
+            t = x ** (2 * k + 1) / (2 * k + 1)
+            if t < Fraction(1, 1 << 120):
+                return s
+            s += t if k % 2 == 0 else -t
+            k += 1
+    two_pi = 2 * (16 * atan_inv(5) - 4 * atan_inv(239))
+    out = [1 << (CORDIC_FRAC - 3)]                                   # atan(1) is an eighth of a turn
+    for i in range(1, CORDIC_N):
+        v = atan_inv(1 << i) / two_pi * (1 << CORDIC_FRAC)
+        out.append(int(v + Fraction(1, 2)))
+    return out
+
+
 def main():
     dec = kaiser_sinc(T1, 12000.0, FS_IN, 7.0)
     chan = kaiser_sinc(T2, 6250.0, FS_BB, 5.0)
@@ -194,6 +218,8 @@ def main():
     with open(os.path.join(ROOT, "tests", "golden", "spec.json"), "w") as f:
         json.dump(spec, f, indent=1, sort_keys=True)
         f.write("\n")
+
+    cordic = cordic_atan_table()
 
     def arr(name, vals):
         body = ",\n    ".join(", ".join(hexf(v) for v in vals[i:i + 4]) for i in range(0, len(vals), 4))
@@ -258,6 +284,12 @@ def main():
     h.append("#define P25FE_CLK_TOL_SHIFT %d    /* interval 10 N + r accepted as a period when |r| << shift <= 10 N */\n" % CLK_TOL_SHIFT)
     h.append("#define P25FE_CLK_DMAX_LOG2 %d    /* ... and the interval is at most 2^24 samples */\n" % CLK_DMAX_LOG2)
     h.append(arr("P25FE_CLK_INTERP", [v for row in interp_table() for v in row]))
+    h.append("\n/* AFC loop (SPEC 3.0g): the angle of an integer pair by CORDIC.  atan(2^-i) / (2 pi) in units of 2^-48 turn, rounded to\n"
+             " * nearest from exact rational series (tools/gen_spec.py: cordic_atan_table) */\n")
+    h.append("#define P25FE_AFC_CORDIC_N %d       /* iterations */\n#define P25FE_AFC_CORDIC_NORM %d    /* bit length the pair is normalised to */\n"
+             "#define P25FE_AFC_CORDIC_FRAC %d    /* the table's and the accumulator's unit: 2^-48 turn */\n" % (CORDIC_N, CORDIC_NORM, CORDIC_FRAC))
+    h.append("static P25FE_SPEC_CONST long long P25FE_AFC_CORDIC_ATAN[%d] = {\n    " % CORDIC_N
+             + ",\n    ".join(", ".join("%dLL" % v for v in cordic[i:i + 4]) for i in range(0, CORDIC_N, 4)) + "\n};\n")
     h.append("\n#endif /* P25FE_SPEC_H */\n")
     os.makedirs(os.path.join(ROOT, "include"), exist_ok=True)
     with open(os.path.join(ROOT, "include", "p25fe_spec.h"), "w") as f:
