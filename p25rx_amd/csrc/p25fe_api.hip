@@ -360,6 +360,7 @@ struct p25fe {
     bool ext_events = true;                // events ride on the kernel dispatches (hipExtLaunchKernelGGL) instead of separate records
     int rx_cus = 0;                        // > 0: the receive stream is confined to this many CUs (hipExtStreamCreateWithCUMask)
     int run_depth = 2;                     // sets p25fe_run_dev_pipelined rotates through (P25FE_PIPE_DEPTH)
+    bool k1_pair = true;                   // cf32 planar main launches run k_frontend_pair (P25FE_K1_PAIR=0: k_frontend everywhere)
     int sh_depth = MAX_LANES;              // sets the pipelined shard step rotates through (P25FE_SHARD_PIPE_DEPTH)
 
     int last_hip = 0;
@@ -754,6 +755,8 @@ int p25fe_create(const p25fe_config_t* cfg, p25fe_t** out)
         if (cfg->symbol_clock != P25FE_CLOCK_FIXED) h->run_depth = 3;
         const char* rd = getenv("P25FE_PIPE_DEPTH");
         if (rd && atoi(rd) >= 2 && atoi(rd) <= MAX_LANES) h->run_depth = atoi(rd);
+        const char* kp = getenv("P25FE_K1_PAIR");                     // (A/B knob: 0 = the one-wave kernel for every K1 launch)
+        h->k1_pair = !(kp && atoi(kp) == 0);
     }
     if (e == hipSuccess) e = h->d_taps.ensure(sizeof(Taps));
     if (e == hipSuccess) e = hipMemcpy(h->d_taps.p, &h->taps, sizeof(Taps), hipMemcpyHostToDevice);
@@ -858,6 +861,7 @@ struct K1Plan {
     bool empty;                            // nothing to launch: no output, or no segment on this side of the part split
     K1Args a;                              // complete but for power_partial (the launch allocates it)
     int fmt, variant; bool ct; int pk;     // which kernel: format, the variant that format runs (format_variant_of), immediate coefficients, FIR outputs per lane
+    bool pair;                             // k_frontend_pair (two waves per workgroup) instead of k_frontend
     long n_seg;                            // segments of the whole range (a.seg_first, a.seg_count: this launch's)
     long head_end;                         // planar position up to which the head's segments write (part != K1_ALL)
     size_t lds;
@@ -870,12 +874,41 @@ static int k1_plan(const p25fe_t* h, const K1Launch& L, K1Plan* p)
     if ((reinterpret_cast<uintptr_t>(L.src) & 15u) != 0) return P25FE_ERR_ARG;   // owned sample 0 on a 16-byte boundary, every format
     if (h->C > 1 && (L.ch_stride % fmt_stride_unit(fmt)) != 0) return P25FE_ERR_ARG;
     if (L.chunk && (!L.planar || L.part)) return P25FE_ERR_ARG;
-    const bool pro = seg_prologue(fmt);                            // p25fe_kernels.hip: segment prologue (u8, s16) or recomputed halo (cf32)
-    const long m_begin = !L.planar ? 0 : (pro ? -(long)PLPAD - h->look : -(long)HIST_BB - h->look);
-    const size_t n_out = p25fe_n_baseband_h(h, L.abs0, L.n);
-    const long total = (long)n_out - m_begin;
+    bool pro = seg_prologue(fmt);                                  // p25fe_kernels.hip: segment prologue (u8, s16) or recomputed halo (cf32)
+    long m_begin = !L.planar ? 0 : (pro ? -(long)PLPAD - h->look : -(long)HIST_BB - h->look);
+    const size_t n_out_range = p25fe_n_baseband_h(h, L.abs0, L.n); // (the planes' strides follow the whole range, whatever part a launch computes)
+    long n_out = (long)n_out_range;
+    static const long subs_env = [] { const char* e = getenv("P25FE_SUBS"); return e ? atol(e) : 0L; }();
+    const long o0 = (long)(((uint64_t)h->phase + 5 - L.abs0 % 5) % 5);
+    // The pair kernel (k_frontend_pair: prologue segments, two waves per workgroup) takes the MAIN part of a cf32 range on the planar
+    // scratch when the handle runs the build's own numbers and that part holds at least one whole segment.  The range is then laid out
+    // in the prologue form; its head segments (a time shard's, whose input reaches into the halo) stay on k_frontend, which computes
+    // exactly their outputs -- positions [0, head_len), a whole number of blocks -- in its own halo form: the same planes, the same bits.
+    K1Part part = L.part;
+    bool pair = false;
+    long pair_head = -1;                                            // >= 0: this is the HEAD launch of such a range: k_frontend over [m_begin, m_begin + pair_head)
+    if (h->k1_pair && fmt == P25FE_FMT_CF32 && L.planar && variant == P25FE_VARIANT_BUILTIN && !h->long_taps && !L.chunk && !L.power_dbm) {
+        SegGeo gp{true, WV * 5, (int)(subs_env > 0 ? (subs_env > 32768 ? 32768 : subs_env) : 3), 0, 0, -(long)PLPAD - h->look, n_out};
+        const long tot = n_out - gp.m_begin;
+        const int ndp = gp.front(h->n_avg, T2);
+        if (L.part) gp.set_lead(ndp, o0, T1);
+        const long ns = tot > 0 ? gp.count(tot) : 0;
+        const long km = L.part ? gp.head_count(ns, ndp, o0, T1) : 0;
+        const long head_len = km >= ns ? tot : gp.start(km) - gp.m_begin;
+        if (tot - head_len >= gp.seg_len()) {
+            m_begin = gp.m_begin;
+            if (L.part == K1_HEAD) {
+                pair_head = head_len;
+                n_out = m_begin + head_len;                         // (nothing in front of the main part: the launch is empty, below)
+                part = K1_ALL;
+            } else {
+                pair = true; pro = true;
+            }
+        }
+    }
+    const long total = n_out - m_begin;
     K1Args& a = p->a;
-    a.m_begin = m_begin; a.n_out = (long)n_out; p->head_end = 0;
+    a.m_begin = m_begin; a.n_out = n_out; p->pair = pair; p->head_end = pair_head > 0 ? pair_head : 0;
     p->empty = total <= 0;
     if (p->empty) return P25FE_OK;
     // Segments are SHORT: three sub-tiles per one-wave workgroup.  Measured on config 2 (profiles/): one long
@@ -885,12 +918,12 @@ static int k1_plan(const p25fe_t* h, const K1Launch& L, K1Plan* p)
     // 3 sub-tiles; A/B on one box, three rounds: 2 -> 0.275, 3 -> 0.264, 4 -> 0.269 ms).  P25FE_SUBS overrides.
     const int pk = (L.planar || h->long_taps || variant == P25FE_VARIANT_SPECIALIZED) ? 5 : h->k1_p;
     const int t1 = h->long_taps ? TMAX : T1;
-    static const long subs_env = [] { const char* e = getenv("P25FE_SUBS"); return e ? atol(e) : 0L; }();
     // (round 2: the instruction-bound u8 kernel prefers longer segments -- less halo recomputed: 3 -> 239, 6 -> 231 us on one
     // box; with the final build 4 -> 222 / 216, 6 -> 217 / 215, 9 -> 212 / 209, 12 -> 216 / 205 us under rocprofv3)
     // (s16: u8's length until a box says otherwise -- docs/MEASUREMENTS.md)
     long subs = subs_env > 0 ? subs_env : (fmt == P25FE_FMT_U8 ? 9 : (fmt == P25FE_FMT_S16 ? P25FE_K1_SUBS_S16 : 3));
     if (L.chunk) subs = 1;                                          // a chunk is latency: every sub-tile its own workgroup
+    if (pair_head >= 0) subs = 1;                                   // the head of a pair range: one-sub-tile workgroups side by side, as lead segments are
     if (subs > 32768) subs = 32768;
     // the post-discriminator filter's length as far as the kernel's GEOMETRY goes (frontend_body's T3): the handle's own for the
     // immediate-coefficient kernels, the ABI's ceiling for the generic ones; the halo form's recomputed halo follows the
@@ -898,21 +931,20 @@ static int k1_plan(const p25fe_t* h, const K1Launch& L, K1Plan* p)
     const bool ct = variant != P25FE_VARIANT_GENERIC;
     const int t2e = h->long_taps ? TMAX : T2;
     const int t3geo = ct ? h->n_avg : TMAX;
-    SegGeo g{pro, WV * pk, (int)subs, seg_halo_for(h->n_avg, t2e), 0, m_begin, (long)n_out};      // p25fe_kernels.hip: the kernel's own geometry
+    SegGeo g{pro, WV * pk, (int)subs, seg_halo_for(h->n_avg, t2e), 0, m_begin, n_out};      // p25fe_kernels.hip: the kernel's own geometry
     const int nd = g.front(t3geo, t2e);
-    const long o0 = (long)(((uint64_t)h->phase + 5 - L.abs0 % 5) % 5);
-    if (L.part && subs > 1 && !L.chunk) g.set_lead(nd, o0, t1);    // a time shard's launches (part != K1_ALL)
+    if (part && subs > 1 && !L.chunk) g.set_lead(nd, o0, t1);    // a time shard's launches (part != K1_ALL)
     const long n_seg = g.count(total);
     const long pl_shift = PLPAD + h->look;       // the general receiver sees the range h->look samples late (p25fe_recv.hip)
     // (halo form: the outputs a segment recomputes and drops may lie in front of planar position 0 -- with a 160-output halo the
     // range's first segment starts 80 positions in front of it; they are never stored, only whole bytes of the planes are)
     if (L.planar && !g.planar_ok(pl_shift)) return P25FE_ERR_ARG;
-    if (L.planar && n_out > MAX_RANGE_BB) return P25FE_ERR_ARG;
+    if (L.planar && n_out_range > MAX_RANGE_BB) return P25FE_ERR_ARG;
     long seg_first = 0, seg_count = n_seg;
-    if (L.part) {
-        if (L.power_dbm) return P25FE_ERR_ARG;
+    if (L.part && L.power_dbm) return P25FE_ERR_ARG;
+    if (part) {
         const long k_min = g.head_count(n_seg, nd, o0, t1);
-        if (L.part == K1_MAIN) { seg_first = k_min; seg_count = n_seg - k_min; }
+        if (part == K1_MAIN) { seg_first = k_min; seg_count = n_seg - k_min; }
         else seg_count = k_min;
         p->head_end = g.start(k_min) - m_begin;
         p->empty = seg_count <= 0;
@@ -926,7 +958,7 @@ static int k1_plan(const p25fe_t* h, const K1Launch& L, K1Plan* p)
     a.bbp = nullptr; a.bbp_ch_stride = 0; a.bits = nullptr; a.bits_ch_stride = 0; a.pl_shift = (int)pl_shift;
     a.done_flag = L.planar ? L.done_flag : nullptr; a.done_seq = L.done_seq;
     if (L.planar) {
-        const PlanarGeo g(n_out);
+        const PlanarGeo g(n_out_range);
         a.bbp = h->rx().pl_f.get(); a.bbp_ch_stride = (long)g.floats();
         a.bits = reinterpret_cast<uint8_t*>(h->rx().pl_bits.get()); a.bits_ch_stride = (long)(4 * g.words());   // (K1 stores the sign words' bytes)
     }
@@ -938,6 +970,7 @@ static int k1_plan(const p25fe_t* h, const K1Launch& L, K1Plan* p)
     // (experiments: extra dynamic LDS per workgroup = fewer resident waves per CU; the occupancy sensitivity of docs/MEASUREMENTS.md)
     static const size_t lds_pad_env = [] { const char* e = getenv("P25FE_K1_LDS_PAD"); return e ? (size_t)atol(e) : (size_t)0; }();
     p->lds += lds_pad_env;
+    if (pair) p->lds = PairGeo::LDS;                                // (the pair kernel's own layout: 8 two-wave workgroups per CU)
     return P25FE_OK;
 }
 
@@ -1012,8 +1045,8 @@ static int launch_k1(p25fe_t* h, const K1Launch& L)
         const ChunkKernel k = chunk_kernel_of(p.fmt, p.ct, h->long_taps);
         hipLaunchKernelGGL(k, grid, dim3(WV), p.lds, st, a, dt, tail);
     } else {
-        const K1Kernel k = k1_kernel_of(p.fmt, p.ct, p.pk, L.planar, h->long_taps);
-        launch_ev(k, grid, dim3(WV), p.lds, st, L.ev0, L.ev1, a, dt);
+        const K1Kernel k = p.pair ? k_frontend_pair : k1_kernel_of(p.fmt, p.ct, p.pk, L.planar, h->long_taps);
+        launch_ev(k, grid, dim3(p.pair ? 2 * WV : WV), p.lds, st, L.ev0, L.ev1, a, dt);
     }
     HIPCHK(h, hipGetLastError());
     if (L.power_dbm) {

@@ -53,6 +53,8 @@ namespace p25k {
 #define P25FE_M_PIN_F2(arr_, n_) do { } while (0)
 #define P25FE_M_CUT_LOADS do { } while (0)                          // truncated builds: leave the sub-tile after stage N
 #define P25FE_M_CUT(stage_) do { } while (0)
+#define P25FE_M_PAIR_PRODUCER_CUT do { } while (0)                  // k_frontend_pair: the producer behind its window turnaround,
+#define P25FE_M_PAIR_CONSUMER_CUT do { } while (0)                  // the consumer behind B(t)
 #define P25FE_M_CUT_KEEP_F2(stage_, arr_, n_) do { } while (0)
 #define P25FE_M_CUT_KEEP_F(stage_, arr_, n_) do { } while (0)
 #define P25FE_M_KEEP1(a_) do { } while (0)
@@ -1316,6 +1318,288 @@ __global__ __launch_bounds__(WV, k1_wps(FMT, CT, PK, OM)) void k_frontend(K1Args
 {
     frontend_body<FMT, CT, PK, OM, TX>(a, gtaps);
 }
+
+#ifndef P25FE_JIT
+// ------------------------------------------------------------------------------------------
+// K1, pair form (cf32, the build's own tables, planar output, prologue segments): the sub-tile of k_frontend split between
+// TWO waves of one workgroup around a pair of d buffers in LDS.
+//   wave 0, the producer: window registers (52 VGPRs) -> LDS, next window requested, 5:1 decimator, d into buf[t & 1];
+//   wave 1, the consumer: channel FIR from buf[t & 1], discriminator, boxcar, transpose, sign words, the plane stores.
+// Neither wave holds the other's registers, so both fit 128 VGPRs (four waves per SIMD) in the prologue form that the one-wave
+// cf32 kernel has no room for (174 VGPRs): every sub-tile is one block of the layout -- ten whole 128-byte rows, ten whole sign
+// words -- and no halo sub-tile is recomputed.  Same cfma order, fm_discriminate and boxcar rule as frontend_body: the same bits.
+//
+// LDS (20 096 B: eight workgroups = 16 waves per CU): [window XIN_N | d buffer 0: carry 40 + 320 | d buffer 1 | OUT 320 floats].
+// The window region is the producer's alone, OUT the consumer's -- except that the producer parks the prologue's ND decimator
+// outputs in OUT (PD_) in front of barrier P, before the consumer's first write to it.
+//
+// Barrier schedule of a segment of n_sub sub-tiles (n_sub from SegGeo alone: the same number on both waves; workgroup barriers
+// only, each wave executes exactly 1 + n_sub of them, no break or return in between):
+//   producer:  prologue d's -> PD_, buf[0] carry | P | t = 0 .. n_sub-1: { stage window t, request t + 1, (t > 0: carry of buf[t & 1]
+//              from the tail of buf[(t-1) & 1]), decimate, fill buf[t & 1] | B(t) }
+//   consumer:  | P | y_carry, f_carry from PD_ | t = 0 .. n_sub-1: { store the outputs of t - 1 | B(t) | channel FIR .. sign words of t } |
+//              store the outputs of n_sub - 1
+// B(t) releases buf[t & 1] to the consumer; the consumer arrives at B(t) with every read of sub-tile t - 1 landed (its last read
+// group is waited for with lgkmcnt(0)), i.e. with buf[(t+1) & 1] free, which is the buffer the producer touches after B(t):
+// its carry first (read from buf[t & 1], which both may read), its body after the decimator.
+// One workgroup per (segment, channel): the launch is the 2-D grid, there is no item loop.
+// ------------------------------------------------------------------------------------------
+struct PairGeo {
+    using G = Geo<5>;
+    static constexpr size_t XIN_B = sizeof(float2) * G::XIN_N;
+    static constexpr size_t DBUF_B = sizeof(float2) * G::D_N;
+    static constexpr size_t LDS = XIN_B + 2 * DBUF_B + sizeof(float) * G::SUB;
+    static_assert(XIN_B % 16 == 0 && DBUF_B % 16 == 0 && LDS <= 20480, "eight pair workgroups per CU");
+};
+// (the barrier waits for the wave's LDS operations only: the producer's prefetch and the consumer's plane stores stay in flight)
+__device__ __forceinline__ void pair_barrier()
+{
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+}
+__global__ __launch_bounds__(2 * WV, 4) void k_frontend_pair(K1Args a, const Taps* __restrict__)
+{
+    constexpr int FMT = P25FE_FMT_CF32;
+    using G = Geo<5>;
+    constexpr int P = 5, SUB = G::SUB, D_CARRY = G::D_CARRY;
+    constexpr int T3 = K1_CT_AVG_N, HY = T3;
+    constexpr int NBACK = (T3 - 1 + P - 1) / P;
+    static_assert(T3 >= 2 && T3 <= AVG_DPP_MAX && NBACK <= 3 && K1_CT_AVG_UNIFORM, "the build's own post-discriminator filter");
+    constexpr int ND = SegGeo{true}.front(HY, T2);                  // 50
+    constexpr int PWIN = DEC * (ND - 1) + T1;
+    constexpr int NVP = (PWIN + 2 + 2 * WV - 1) / (2 * WV);
+    static_assert(ND <= WV && D_CARRY <= ND && 2 * ND <= SUB, "one prologue d per lane; PD_ fits OUT");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float2* const XIN = reinterpret_cast<float2*>(smem);
+    float2* const DB0 = XIN + G::XIN_N;
+    float2* const DB1 = DB0 + G::D_N;
+    float* const OUT = reinterpret_cast<float*>(DB1 + G::D_N);
+    float2* const PD_ = reinterpret_cast<float2*>(OUT);
+    const int tid = threadIdx.x & (WV - 1);
+    const int role = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int ch = (int)blockIdx.y;
+    const long seg = (long)blockIdx.x + a.seg_first;
+    const SegGeo sg = SegGeo{true, SUB, a.subs_per_seg, 0}.range(a.lead_segs, a.m_begin, a.n_out);
+    const long m_seg0 = sg.start(seg);
+    const long m_seg1 = sg.end(seg);
+    const int n_sub = m_seg0 < a.n_out ? (int)((m_seg1 - m_seg0 + SUB - 1) / SUB) : 0;     // uniform over the workgroup
+    const float fm_gain = K1_CT_FM_GAIN;
+    if (n_sub > 0) {
+    if (role == 0) {
+        // ---------------- producer ----------------
+        const char* xb = reinterpret_cast<const char*>(a.x) + (size_t)ch * a.ch_stride * fmt_bps(FMT);
+        Loader<FMT, P> ld0;
+        Loader<FMT, P, 0, NVP> lp;
+        const long i_last = (long)a.o0 + DEC * (m_seg1 - 1);
+        const long pfirst = K1_FIRST_INPUT(m_seg0 - ND, a.o0, T1);
+        ld0.init(xb, pfirst, a.n_hist, a.n_new, i_last);
+        lp.rs = ld0.rs; lp.base_idx = ld0.base_idx;
+        lp.load_first(pfirst, tid);
+        lp.store(XIN, pfirst, a.n_hist, a.n_new, tid);
+        lp.fixup(XIN, pfirst, a.n_hist, a.n_new, tid);
+        ld0.load_first(K1_FIRST_INPUT(m_seg0, a.o0, T1), tid);      // under the prologue's arithmetic
+        phase_sync();
+        {
+            // d[m_seg0 - ND + l] on lane l (the 14 surplus lanes compute on staged zeros / stale samples, never stored)
+            v2f dacc = v2f{0.f, 0.f};
+            const float2* w = XIN + (int)(pfirst & 1) + DEC * tid;
+            lds_walk<T1, true>(w, [&](auto jc, v2f sv) {
+                constexpr int j = decltype(jc)::value;
+                dacc = cfma(K1_CT_DECIM_TAPS[T1 - 1 - j], sv, dacc);
+            });
+            if (tid < ND) PD_[tid] = make_float2(dacc.x, dacc.y);
+            if (tid >= ND - D_CARRY && tid < ND) DB0[tid - (ND - D_CARRY)] = make_float2(dacc.x, dacc.y);
+        }
+        pair_barrier();                                             // P
+        long dlo = m_seg0;
+        for (int t = 0; t < n_sub; ++t, dlo += SUB) {
+            float2* const Dc = (t & 1) ? DB1 : DB0;
+            const float2* const Dp = (t & 1) ? DB0 : DB1;
+            const long first = K1_FIRST_INPUT(dlo, a.o0, T1);
+            const int xsh = (int)(first & 1);
+#if P25FE_K1_TURNAROUND_PRIO
+            __builtin_amdgcn_s_setprio(P25FE_K1_TURNAROUND_PRIO);
+#endif
+            ld0.store(XIN, first, a.n_hist, a.n_new, tid);
+            {
+                // (the lane index afresh: fixup's 64-bit per-lane sample indices, which only boundary windows look at, are otherwise
+                // hoisted out of the loop and held -- spilled -- across the decimator)
+                int tidf = tid;
+                asm volatile("" : "+v"(tidf));
+                ld0.fixup(XIN, first, a.n_hist, a.n_new, tidf);
+            }
+            phase_sync();
+            ld0.load(first + (long)DEC * SUB, tid);                 // past the segment's end: out of the descriptor's range, no traffic
+#if P25FE_K1_TURNAROUND_PRIO
+            __builtin_amdgcn_s_setprio(0);
+#endif
+            P25FE_M_PAIR_PRODUCER_CUT;
+            if (t > 0 && tid < D_CARRY) Dc[tid] = lds_read_c(Dp + SUB + tid);
+            const float2* w = XIN + xsh + (DEC * P) * tid;
+            v2f acc[P];
+#pragma unroll
+            for (int p = 0; p < P; ++p) acc[p] = v2f{0.f, 0.f};
+            lds_walk<DEC * (P - 1) + T1, true>(w, [&](auto jc, v2f s) {
+                constexpr int j = decltype(jc)::value;
+#pragma unroll
+                for (int p = 0; p < P; ++p) {
+                    const int k = DEC * p + (T1 - 1) - j;
+                    if (k >= 0 && k < T1) acc[p] = cfma(K1_CT_DECIM_TAPS[k], s, acc[p]);
+                }
+            });
+            phase_sync();
+#pragma unroll
+            for (int p = 0; p < P; ++p) Dc[D_CARRY + P * tid + p] = make_float2(acc[p].x, acc[p].y);
+            pair_barrier();                                         // B(t)
+        }
+    } else {
+        // ---------------- consumer ----------------
+        float2 y_carry;
+        float f_carry[NBACK][P];
+        pair_barrier();                                             // P
+        {
+            v2f yv = v2f{0.f, 0.f};
+            if (tid < HY) {
+                const float2* w = PD_ + (ND - HY) - (T2 - 1) + tid;
+                lds_walk<T2, true>(w, [&](auto jc, v2f sv) {
+                    constexpr int j = decltype(jc)::value;
+                    yv = cfma(K1_CT_CHAN_TAPS[T2 - 1 - j], sv, yv);
+                });
+            }
+            float2 yp;
+            yp.x = wave_shr1(yv.x, 0.f);
+            yp.y = wave_shr1(yv.y, 0.f);
+            const float fmv = fm_discriminate(make_float2(yv.x, yv.y), yp, fm_gain);
+            y_carry.x = lane_bcast<HY - 1>(yv.x);
+            y_carry.y = lane_bcast<HY - 1>(yv.y);
+            static_for<0, NBACK>([&](auto bc) {
+                constexpr int b = decltype(bc)::value;
+                static_for<0, P>([&](auto pc) {
+                    constexpr int p = decltype(pc)::value;
+                    constexpr int l = HY - (b + 1) * P + p;
+                    if constexpr (l >= 1) f_carry[b][p] = lane_bcast<l>(fmv);
+                    else f_carry[b][p] = 0.f;
+                });
+            });
+            phase_sync();                                           // PD_ read before OUT is written
+        }
+        float outv[P];
+#pragma unroll
+        for (int q = 0; q < P; ++q) outv[q] = 0.f;
+        int out_rel = -2 * SUB;
+        const int seg_n = (int)(m_seg1 - m_seg0);
+        const int pl_sym = tid & 31, pl_h5 = (tid >> 5) * 5;
+        const int i_seg = (int)((m_seg0 + a.pl_shift) / SPS_);
+        float* const bbp_ch = a.bbp + (size_t)ch * a.bbp_ch_stride;
+        unsigned* const bits_ch = reinterpret_cast<unsigned*>(a.bits + (size_t)ch * a.bits_ch_stride);
+        unsigned bitsv = 0u;
+        auto flush_outputs = [&]() {
+            const int blk = (i_seg >> 5) + out_rel / SUB;
+            float* const row = bbp_ch + (size_t)blk * PL_BLK + pl_sym + 32 * pl_h5;
+#pragma unroll
+            for (int q = 0; q < P; ++q) {
+                const int r = out_rel + SPS_ * pl_sym + pl_h5 + q;
+#if P25FE_K1_NT_STORES
+                if (r >= 0 && r < seg_n) __builtin_nontemporal_store(outv[q], row + 32 * q);
+#else
+                if (r >= 0 && r < seg_n) row[32 * q] = outv[q];
+#endif
+            }
+            if (tid < SPS_ && out_rel >= 0 && out_rel < seg_n) bits_ch[(size_t)blk * SPS_ + tid] = bitsv;
+        };
+        for (int t = 0; t < n_sub; ++t) {
+            const float2* const Dc = (t & 1) ? DB1 : DB0;
+            flush_outputs();
+            pair_barrier();                                         // B(t)
+            P25FE_M_PAIR_CONSUMER_CUT;
+            float2 y[P];
+            {
+                const float2* w = Dc + (D_CARRY - (T2 - 1)) + P * tid;
+                v2f yv[P];
+#pragma unroll
+                for (int p = 0; p < P; ++p) yv[p] = v2f{0.f, 0.f};
+                lds_walk<(P - 1) + T2, true>(w, [&](auto jc, v2f s) {
+                    constexpr int j = decltype(jc)::value;
+#pragma unroll
+                    for (int p = 0; p < P; ++p) {
+                        const int k = p + (T2 - 1) - j;
+                        if (k >= 0 && k < T2) yv[p] = cfma(K1_CT_CHAN_TAPS[k], s, yv[p]);
+                    }
+                });
+#pragma unroll
+                for (int p = 0; p < P; ++p) y[p] = make_float2(yv[p].x, yv[p].y);
+            }
+            float f[P];
+            {
+                float2 yprev;
+                yprev.x = wave_shr1(y[P - 1].x, y_carry.x);
+                yprev.y = wave_shr1(y[P - 1].y, y_carry.y);
+                f[0] = fm_discriminate(y[0], yprev, fm_gain);
+#pragma unroll
+                for (int p = 1; p < P; ++p) f[p] = fm_discriminate(y[p], y[p - 1], fm_gain);
+                y_carry.x = lane_bcast<WV - 1>(y[P - 1].x);
+                y_carry.y = lane_bcast<WV - 1>(y[P - 1].y);
+            }
+            {
+                float prevf[NBACK][P];
+#pragma unroll
+                for (int p = 0; p < P; ++p) prevf[0][p] = wave_shr1(f[p], f_carry[0][p]);
+#pragma unroll
+                for (int b = 1; b < NBACK; ++b)
+#pragma unroll
+                    for (int p = 0; p < P; ++p) prevf[b][p] = wave_shr1(prevf[b - 1][p], f_carry[b][p]);
+                auto fm_back = [&](int p, int j) -> float {          // fm[P tid + p - j]
+                    const int q = p - j;
+                    if (q >= 0) return f[q];
+                    const int b = (-q + P - 1) / P;
+                    return prevf[b - 1][q + b * P];
+                };
+#pragma unroll
+                for (int p = 0; p < P; ++p) {
+                    float acc = f[p];
+#pragma unroll
+                    for (int j = 1; j < T3; ++j) acc = acc + fm_back(p, j);
+                    acc = acc * K1_CT_AVG_TAPS[0];
+                    OUT[P * tid + p] = acc;
+                }
+#pragma unroll
+                for (int p = 0; p < P; ++p) {
+                    if constexpr (NBACK >= 3) f_carry[2][p] = lane_bcast<WV - 3>(f[p]);
+                    if constexpr (NBACK >= 2) f_carry[1][p] = lane_bcast<WV - 2>(f[p]);
+                    f_carry[0][p] = lane_bcast<WV - 1>(f[p]);
+                }
+            }
+            phase_sync();
+            unsigned long long sgn[5];
+#pragma unroll
+            for (int q = 0; q < P; ++q) {
+                outv[q] = OUT[SPS_ * pl_sym + pl_h5 + q];
+                sgn[q] = __builtin_amdgcn_ballot_w64(__float_as_int(outv[q]) < 0);
+            }
+            bitsv = lanes_from_ballots(sgn);
+            out_rel = t * SUB;
+            phase_sync();
+        }
+        flush_outputs();
+    }
+    }   // n_sub > 0
+    // the launch's last workgroup publishes done_flag (as k_frontend does): the consumer wave, behind its own stores
+    if (role == 1 && a.done_flag) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        unsigned ticket = 0u;
+        if (tid == 0) ticket = __hip_atomic_fetch_add(a.done_flag + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ticket = (unsigned)__builtin_amdgcn_readfirstlane((int)ticket);
+        if (ticket == gridDim.x * gridDim.y - 1u) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            if (tid == 0) {
+                __hip_atomic_store(a.done_flag + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(a.done_flag, a.done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+    }
+}
+#endif  // !P25FE_JIT
 
 // ------------------------------------------------------------------------------------------
 // K0: stage 0 of BASELINE.json config 3 -- 10:1 decimating FIR, 2.4 Msps (cf32, s16 or u8) -> 240 ksps cf32, T0 = 80 taps

@@ -4,6 +4,7 @@
 //   P25FE_ABLATE=N          K1 truncated after stage N (1 loads, 2 decimator, 3 channel filter, 4 discriminator, 5 no output staging,
 //                           6 every window load served from one cached row); P25FE_ABLATE_CACHED: that loader with any N;
 //                           P25FE_ABLATE_STORES: N = 1 keeps the output stream; P25FE_DRIFT / P25FE_DRIFT_SPREAD: s_sleep phases there
+//                           (k_frontend_pair: N = 1, with or without P25FE_ABLATE_STORES, and N = 6)
 //   P25FE_EXP (bit mask)    1 no sign planes, 4 channel filter without its FMAs, 8 no baseband stores
 //   P25FE_K1_STAMP          shader-clock time per phase of the sub-tiles, summed into g_k1_stamp (p25fe_debug_k1_stamps)
 //   P25FE_ABLATE_DET=1,2    K2 after the screen / after the exact test;   P25FE_ABLATE6=1,2   K6's store stream alone
@@ -108,6 +109,19 @@ __device__ unsigned long long g_k1_stamp[K1_STAMP_SLOTS][16];
 #define P25FE_M_CUT_LOADS do { } while (0)
 #endif
 #define P25FE_M_CUT(stage_) do { if constexpr (P25FE_ABLATE <= (stage_)) return true; } while (0)
+// k_frontend_pair with N = 1: the producer stops behind its window turnaround, the consumer behind B(t) -- both keep their barriers;
+// P25FE_ABLATE_STORES: the consumer's next iteration stores this sub-tile's (zero) planes.  (N = 6 needs no hook: the loader's offset.)
+#if P25FE_ABLATE <= 1
+#define P25FE_M_PAIR_PRODUCER_CUT { pair_barrier(); continue; }
+#if defined(P25FE_ABLATE_STORES)
+#define P25FE_M_PAIR_CONSUMER_CUT { out_rel = t * SUB; continue; }
+#else
+#define P25FE_M_PAIR_CONSUMER_CUT { continue; }
+#endif
+#else
+#define P25FE_M_PAIR_PRODUCER_CUT do { } while (0)
+#define P25FE_M_PAIR_CONSUMER_CUT do { } while (0)
+#endif
 #define P25FE_M_CUT_KEEP_F2(stage_, arr_, n_)                                                                \
     do { if constexpr (P25FE_ABLATE <= (stage_)) {                                                           \
         _Pragma("unroll") for (int p_ = 0; p_ < (n_); ++p_) asm volatile("" ::"v"((arr_)[p_].x), "v"((arr_)[p_].y)); \

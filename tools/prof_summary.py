@@ -118,14 +118,16 @@ for f in sorted(glob.glob(os.path.join(d, "pmc_*", "**", "*counter_collection.cs
         for c, v in sorted(acc[k].items()):
             vals[k][c] = sum(v) / len(v)
             print("  %-44s %-26s per-launch mean %16.1f  (n=%d)" % (k[:44], c, sum(v) / len(v), len(v)))
-for k, tag in ((next((x for x in vals if x.startswith("k_frontend<0")), None), "cf32"), (next((x for x in vals if x.startswith("k_frontend<1")), None), "u8")):
+# cf32: the pair kernel where the run used it (p25fe_run_dev of a long capture does), else the one-wave kernel
+for k, tag in ((next((x for x in vals if x.startswith("k_frontend_pair")), None) or next((x for x in vals if x.startswith("k_frontend<0")), None), "cf32"),
+               (next((x for x in vals if x.startswith("k_frontend<1")), None), "u8")):
     if not k:
         continue
     k1 = vals[k]
     if "FETCH_SIZE" in k1 and "WRITE_SIZE" in k1:
         rd = 2.0 * k1["FETCH_SIZE"] * 1024.0          # gfx950: FETCH_SIZE counts 64 B per 128-B request -> double it
         wr = k1["WRITE_SIZE"] * 1024.0
-        out = {"kernel": "k_frontend<%s>" % tag, "fetch_size_kib_raw": k1["FETCH_SIZE"], "write_size_kib_raw": k1["WRITE_SIZE"],
+        out = {"kernel": k if k.startswith("k_frontend_pair") else "k_frontend<%s>" % tag, "fetch_size_kib_raw": k1["FETCH_SIZE"], "write_size_kib_raw": k1["WRITE_SIZE"],
                "hbm_read_bytes_per_launch": rd, "hbm_write_bytes_per_launch": wr, "hbm_bytes_per_launch": rd + wr,
                "correction": "FETCH_SIZE x2 (gfx950, wide coalesced reads), WRITE_SIZE as reported; both KiB",
                # which K1 the counters were read from: bench.py compares it with the source it runs and says so when they differ
