@@ -203,6 +203,20 @@ pub const AFC_MAX_D: i32 = 64;
 pub const AFC_MAX_T: i32 = 512;
 pub const AFC_MAX_CH: i32 = 256;
 pub const AFC_MAX_SHIFT: i32 = 40;
+/// p25fe_scan_t: the survey of docs/SPEC.md 3.0h (made for a Handle, which must outlive every use of it)
+pub enum Scan {}
+/// P25FE_SCAN_MAX_SHIFT: 0 <= shift <= 40; N is 1024 or 4096, hop a multiple of 8 that divides N
+pub const SCAN_MAX_SHIFT: i32 = 40;
+/// p25fe_scan_chan_t: one active raster channel of a survey's record (32 bytes)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct ScanChan {
+    pub raster_index: i32,
+    pub reserved: i32,
+    pub centre_hz: f64,
+    pub db_over_floor: f64,
+    pub offset_hz: f64,
+}
 /// P25FE_TUNE_MAX_CH / _DEN: 1 <= channels <= 256; num / den in lowest terms, 1 <= den <= 8192, 2 |num| <= den
 pub const TUNE_MAX_CH: i32 = 256;
 pub const TUNE_MAX_DEN: i32 = 8192;
@@ -297,6 +311,17 @@ extern "C" {
     pub fn p25fe_track_step(cfg: *const TrackCfg, l: i32, m: i32, d: i32, step_ref: i32, acc_in: *const AfcAcc,
                             state_in: *const TrackState, abs_at: u64, acc_out: *mut AfcAcc, state_out: *mut TrackState) -> c_int;
     pub fn p25fe_track_hz(state: *const TrackState, d: i32, hz: *mut f64) -> c_int;
+    // survey (docs/SPEC.md 3.0h): per-bin power sums of one capture row (the record is N + 1 words), and its active raster channels
+    pub fn p25fe_scan_window(n: i32, w: *mut f32, cap: usize) -> c_int;
+    pub fn p25fe_scan_create(h: *mut Handle, n: i32, hop: i32, window: *const f32, shift: i32, out: *mut *mut Scan) -> c_int;
+    pub fn p25fe_scan_destroy(sc: *mut Scan);
+    pub fn p25fe_scan_reset(sc: *mut Scan) -> c_int;
+    pub fn p25fe_scan_dev(sc: *mut Scan, d_iq: *const c_void, fmt: c_int, n_hist: usize, n: usize, abs_first: u64, d_acc: *mut u64,
+                          stream: *mut c_void) -> c_int;
+    pub fn p25fe_scan(sc: *mut Scan, iq: *const c_void, fmt: c_int, n: usize) -> c_int;
+    pub fn p25fe_scan_read(sc: *mut Scan, acc_out: *mut u64, clear: c_int) -> c_int;
+    pub fn p25fe_scan_channels(acc: *const u64, n: i32, fs_hz: u32, raster_hz: f64, half_bw_hz: f64, thr_db: f64, out: *mut ScanChan,
+                               cap: usize, n_out: *mut usize) -> c_int;
     pub fn p25fe_n_baseband(abs0: u64, n: usize) -> usize;
     pub fn p25fe_slice_dev(h: *mut Handle, d_bb: *const f32, bb_stride: usize, n_hist_bb: usize, n_bb: usize, abs_bb0: u64,
                            d_anchor_in: *const Anchor, d_dibits: *mut u8, dibit_stride: usize, d_sync_pos: *mut i64,

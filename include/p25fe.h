@@ -628,6 +628,61 @@ int p25fe_track_step(const p25fe_track_cfg_t *cfg, int32_t L, int32_t M, int32_t
 /* hz = last_theta / 2^32 * 240000 / D, for reports.  Host only.  P25FE_ERR_ARG: a null pointer, D outside the limits. */
 int p25fe_track_hz(const p25fe_track_state_t *state, int32_t D, double *hz);
 
+/* ---- survey: per-bin power spectrum of a capture, and the active raster channels (docs/SPEC.md 3.0h) -------------------------------
+ * The stage in front of the tuner: which raster channels of a capture of any rate carry a signal, and roughly how far off the raster
+ * each one is.  A Welch periodogram of ONE capture row (cf32, s16 or u8; 3.1 / 3.0's conversions): windowed length-N DFTs of frames
+ * H samples apart, squared magnitudes quantised and summed as 64-bit integers per bin.  With absolute indices and x[n] = 0 for n < 0,
+ * frame f ends at n_f = f H + H - 1 and covers [n_f - N + 1, n_f]:
+ *     X_f[b] = sum_j w[j] x[n_f - N + 1 + j] e^{-2 pi i b j / N}          b = 0 .. N - 1   (fp32; the factoring is the implementation's)
+ *     P_f[b] = fma(X.im, X.im, X.re * X.re)
+ *     Q(v)   = (int64) rint(min(v * 2^shift, 2^62)),  NaN -> 0
+ *     acc[b] += Q(P_f[b])  (uint64, wrapping);   acc[N] += 1 per frame
+ * A range owns the frames whose n_f lies in it.  Integer sums commute: any split of a stream into ranges with N - 1 samples of
+ * history gives the same 8 (N + 1) bytes as one range.  Bin b is b fs / N Hz for b < N / 2, else (b - N) fs / N. */
+#define P25FE_SCAN_MAX_SHIFT 40
+typedef struct p25fe_scanner p25fe_scan_t;
+typedef struct p25fe_scan_chan {
+    int32_t raster_index;    /* r: the channel is centred r * raster_hz from the capture's centre */
+    int32_t reserved;        /* 0 */
+    double centre_hz;        /* r * raster_hz */
+    double db_over_floor;    /* the channel's power over the median channel's, dB (+inf over a floor of zero) */
+    double offset_hz;        /* centroid of the channel's raster cell minus centre_hz */
+} p25fe_scan_chan_t;         /* 32 bytes */
+
+/* The designed window: periodic Hann, w[j] = 0.5 - 0.5 cos(2 pi j / N), evaluated in double and rounded once; no device needed.
+ * P25FE_ERR_ARG: N is neither 1024 nor 4096; P25FE_ERR_CAPACITY: cap < N (w may then be null). */
+int p25fe_scan_window(int32_t N, float *w, size_t cap);
+/* A survey object on h's device; h must outlive every USE of it (p25fe_scan_destroy alone is safe after p25fe_destroy(h)).  window:
+ * N real values, null for the designed one.  Every argument is checked before any device is touched: P25FE_ERR_ARG unless N is 1024
+ * or 4096, 8 <= hop <= N with hop a multiple of 8 that divides N, the window is finite and 0 <= shift <= 40 (recommended: 16 for
+ * samples of magnitude up to about 2). */
+int p25fe_scan_create(p25fe_t *h, int32_t N, int32_t hop, const float *window, int32_t shift, p25fe_scan_t **out);
+void p25fe_scan_destroy(p25fe_scan_t *sc);
+/* The host streaming form starts over: position 0, no history, no format, the object's record zeroed.  Waits for the device. */
+int p25fe_scan_reset(p25fe_scan_t *sc);
+/* One device-resident range of the capture, p25fe_tune_dev's conventions: d_iq points at owned sample 0 (16-byte aligned), n_hist
+ * valid samples precede it (n_hist >= N - 1: exact continuation; what is missing reads as zero), abs_first matters modulo hop.  ADDS
+ * into the caller's record d_acc[N + 1] (device, 8-byte aligned): zero it to open a survey.  Enqueues on `stream`, synchronises
+ * nothing.  P25FE_ERR_ARG: a null or misaligned pointer, an unknown format, abs_first or n >= 2^62. */
+int p25fe_scan_dev(p25fe_scan_t *sc, const void *d_iq, int fmt, size_t n_hist, size_t n, uint64_t abs_first, uint64_t *d_acc,
+                   void *stream);
+/* The host streaming form, as p25fe_tune: n more samples of the object's stream, which starts at position 0; the last N - 1 samples
+ * are carried on the device, the sums go into the object's own record.  Returns when the caller's buffer is free again.
+ * P25FE_ERR_FORMAT: the format changed within a stream. */
+int p25fe_scan(p25fe_scan_t *sc, const void *iq, int fmt, size_t n);
+/* Waits for the device, copies the object's record to acc_out[N + 1] and, with clear != 0, zeroes it. */
+int p25fe_scan_read(p25fe_scan_t *sc, uint64_t *acc_out, int clear);
+/* A record the caller has copied back -> the active raster channels; host only, works on doubles formed from the record.  Raster
+ * index r is eligible when |r raster_hz| + raster_hz / 2 <= fs / 2; pow[r] sums acc[b] over the bins with |f_b - r raster_hz| <=
+ * half_bw_hz; the floor is the lower median of pow over the eligible r; r is active iff pow[r] > 0 and pow[r] >= floor *
+ * 10^(thr_db / 10); offset_hz is the centroid sum acc[b] f_b / sum acc[b] over |f_b - r raster_hz| <= raster_hz / 2, minus
+ * r raster_hz.  Sorted by power, descending; ties go to the smaller r.  *n_out is the number of active channels even when it exceeds
+ * cap (the first cap are written); a record of zero frames has none.  Recommended: raster_hz = 12500, half_bw_hz = 4000, thr_db = 20.
+ * P25FE_ERR_ARG: a null acc or n_out, a null out with cap > 0, N neither 1024 nor 4096, fs_hz = 0, raster_hz not finite or <= 0,
+ * half_bw_hz not finite or < 0, thr_db not finite, a raster of more than 10^6 eligible channels a side. */
+int p25fe_scan_channels(const uint64_t *acc, int32_t N, uint32_t fs_hz, double raster_hz, double half_bw_hz, double thr_db,
+                        p25fe_scan_chan_t *out, size_t cap, size_t *n_out);
+
 /* stages 6-7 on device baseband.  d_bb points at the first owned sample; n_hist_bb valid
  * samples precede it; abs_bb0 is its absolute index; d_anchor_in (nullable = no lock) is the
  * carry-in per channel.  d_result[c] is filled per channel.

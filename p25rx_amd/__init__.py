@@ -1,0 +1,1 @@
+from .scan import Scanner  # noqa: F401

@@ -72,6 +72,10 @@ TRACK_STATE_DTYPE = np.dtype([("step", "<i4"), ("ph0", "<u4"), ("last_theta", "<
                               ("n_rejected", "<u4"), ("n_short", "<u4"), ("status", "<u4")])    # p25fe_track_state_t
 assert TRACK_CFG_DTYPE.itemsize == 32 and TRACK_STATE_DTYPE.itemsize == 32
 TRACK_NONE, TRACK_SHORT, TRACK_REJECT, TRACK_APPLY = 0, 1, 2, 3     # p25fe_track_state_t.status
+SCAN_MAX_SHIFT = 40                                                 # P25FE_SCAN_MAX_SHIFT
+SCAN_CHAN_DTYPE = np.dtype([("raster_index", "<i4"), ("reserved", "<i4"), ("centre_hz", "<f8"), ("db_over_floor", "<f8"),
+                            ("offset_hz", "<f8")])                                             # p25fe_scan_chan_t
+assert SCAN_CHAN_DTYPE.itemsize == 32
 
 # every symbol include/p25fe.h declares (tests check the library exports exactly these)
 SYMBOLS = [
@@ -96,6 +100,8 @@ SYMBOLS = [
     "p25fe_afc_measure_dev", "p25fe_afc_hz",
     "p25fe_track_create", "p25fe_track_destroy", "p25fe_track_records", "p25fe_track_measure_dev", "p25fe_track_update_dev", "p25fe_track_run_dev",
     "p25fe_track_read", "p25fe_track_step", "p25fe_track_hz",
+    "p25fe_scan_window", "p25fe_scan_create", "p25fe_scan_destroy", "p25fe_scan_reset", "p25fe_scan_dev", "p25fe_scan", "p25fe_scan_read",
+    "p25fe_scan_channels",
     "p25fe_debug_planes_size", "p25fe_debug_planes_dev",
 ]
 
@@ -233,6 +239,15 @@ def load():
     L.p25fe_track_read.argtypes = [vp, vp]
     L.p25fe_track_step.argtypes = [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, vp, vp, u64, vp, vp]
     L.p25fe_track_hz.argtypes = [vp, C.c_int32, C.POINTER(C.c_double)]
+    L.p25fe_scan_window.argtypes = [C.c_int32, vp, sz]
+    L.p25fe_scan_create.argtypes = [vp, C.c_int32, C.c_int32, vp, C.c_int32, C.POINTER(vp)]
+    L.p25fe_scan_destroy.argtypes = [vp]
+    L.p25fe_scan_destroy.restype = None
+    L.p25fe_scan_reset.argtypes = [vp]
+    L.p25fe_scan_dev.argtypes = [vp, vp, C.c_int, sz, sz, u64, vp, vp]
+    L.p25fe_scan.argtypes = [vp, vp, C.c_int, sz]
+    L.p25fe_scan_read.argtypes = [vp, vp, C.c_int]
+    L.p25fe_scan_channels.argtypes = [vp, C.c_int32, C.c_uint32, C.c_double, C.c_double, C.c_double, vp, sz, psz]
     L.p25fe_n_predecim.argtypes = [u64, sz]
     L.p25fe_n_predecim.restype = sz
     L.p25fe_n_baseband.argtypes = [u64, sz]

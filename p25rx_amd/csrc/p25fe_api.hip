@@ -3264,3 +3264,5 @@ int p25fe_state_import(p25fe_t* h, const void* buf, size_t n)
 
 P25FE_M_API_EXTRAS
 }  // extern "C"
+
+#include "p25fe_scan.inc"       // survey (SPEC 3.0h): k_scan and its entry points

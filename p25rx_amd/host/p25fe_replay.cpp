@@ -1,7 +1,7 @@
 // p25fe_replay -- file-in / file-out driver in the role of the reference's command line for this path
 // (src/main.rs:95-102, 162-175, 278-283 and src/replay.rs:26-57): a deterministic harness for the hot path.
 //
-//   p25fe_replay [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] [-r RATE_HZ [-f OFFSET_HZ | -F OFFSET_HZ [-a MS | -A MS]]] u8|s16|cf32|bb <in> <dibits.out>
+//   p25fe_replay [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] [-r RATE_HZ [-S MS] [-f OFFSET_HZ | -F OFFSET_HZ [-a MS | -A MS]]] u8|s16|cf32|bb <in> <dibits.out>
 //   p25fe_replay -W WINDOW_BYTES u8|s16|cf32 <in> <dibits.out>
 //
 //     u8    RTL-SDR style interleaved u8 I/Q, the reference's live input (src/consts.rs:6: 32768-byte chunks)
@@ -44,6 +44,13 @@
 //               record (the recommended loop: gate 0.75, gain 1, half a window of products); the state is read back and printed as
 //               an {"event":"afc", ...} line per boundary, in -a's format plus "status".
 //
+//     -S MS     with -r: the survey (docs/SPEC.md 3.0h).  The first MS ms of the capture go through p25fe_scan (N = 4096, hop 2048, the
+//               designed window, shift 16), and the active channels of the 12.5 kHz raster (p25fe_scan_channels: +-4 kHz, 20 dB over
+//               the median channel) are printed as ONE line {"event":"scan","n_frames":..,"channels":[{"raster_index","centre_hz",
+//               "db_over_floor","offset_hz"}, ..]}, strongest first, on stdout and in the -j events.  With neither -f nor -F the run
+//               ends there with status 0 and <dibits.out> is not touched; with one of them it goes on as without -S, from the start
+//               of the input: centre_hz + offset_hz of a channel is what -F takes.
+//
 //     -W BYTES  bulk mode for long captures (p25fe_run_host_windows): a READER THREAD fills pinned blocks of eight windows
 //               from the file while the library pipelines the previous block -- window k + 1 on its way to the GPU,
 //               window k in the kernels, window k - 1's dibits on their way back.  The shape of the reference's own loop (a
@@ -58,6 +65,7 @@
 #include <cstring>
 #include <deque>
 #include <fstream>
+#include <memory>
 #include <mutex>
 #include <optional>
 #include <thread>
@@ -120,7 +128,7 @@ struct Sink {
 
 static int usage(const char* argv0)
 {
-    std::fprintf(stderr, "usage: %s [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] [-r RATE_HZ [-f OFFSET_HZ | -F OFFSET_HZ [-a MS | -A MS]]] u8|s16|cf32|bb <in> <dibits.out>\n"
+    std::fprintf(stderr, "usage: %s [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] [-r RATE_HZ [-S MS] [-f OFFSET_HZ | -F OFFSET_HZ [-a MS | -A MS]]] u8|s16|cf32|bb <in> <dibits.out>\n"
                          "       %s -W WINDOW_BYTES u8|s16|cf32 <in> <dibits.out>\n", argv0, argv0);
     return 2;
 }
@@ -141,6 +149,7 @@ struct Options {
     struct { enum { NONE, RATIONAL, NCO } kind = NONE; long long hz = 0; double nco_hz = 0.0; } offset;   // -f: hz; -F: nco_hz
     double afc_ms = 0.0;                                              // -a: measure the first MS ms at -F's offset, correct once
     double track_ms = 0.0;                                            // -A: the loop, updated at every multiple of MS ms of input
+    double scan_ms = 0.0;                                             // -S: survey the first MS ms, print the active raster channels
     bool bb = false;                                                  // the mode: 48 kHz baseband, or ...
     int fmt = 0; size_t bps = 0;                                      // ... IQ in this format (P25FE_FMT_*) of this many bytes per sample
 };
@@ -163,6 +172,7 @@ static bool parse(int argc, char** argv, Options& o)
         else if (opt == "-F") { if (!number(val, o.offset.nco_hz)) return false; F = true; }
         else if (opt == "-a") { if (!number(val, o.afc_ms) || !(o.afc_ms > 0.0) || o.afc_ms > 60000.0) return false; }
         else if (opt == "-A") { if (!number(val, o.track_ms) || !(o.track_ms > 0.0) || o.track_ms > 60000.0) return false; }
+        else if (opt == "-S") { if (!number(val, o.scan_ms) || !(o.scan_ms > 0.0) || o.scan_ms > 60000.0) return false; }
         else if (opt == "-W") {
             char* end = nullptr;
             o.window_bytes = (size_t)std::strtoull(val, &end, 10);
@@ -172,6 +182,7 @@ static bool parse(int argc, char** argv, Options& o)
     }
     if (argc - a != 3 || o.batch == 0 || (f && F) || ((f || F) && !o.rate_hz) || (o.afc_ms > 0.0 && !F)) return false;
     if (o.track_ms > 0.0 && (!F || o.afc_ms > 0.0)) return false;   // -A goes with -F and instead of -a
+    if (o.scan_ms > 0.0 && !o.rate_hz) return false;                 // -S goes with -r
     o.offset.kind = F ? o.offset.NCO : (f ? o.offset.RATIONAL : o.offset.NONE);
     const std::string mode = argv[a];
     o.in_path = argv[a + 1]; o.out_path = argv[a + 2];
@@ -181,7 +192,7 @@ static bool parse(int argc, char** argv, Options& o)
     else if (mode == "bb") o.bb = true;
     else return false;
     if (o.bb && (o.rate_hz || o.window_bytes)) return false;         // the resampler, the tuner and the bulk mode take IQ
-    return !(o.window_bytes && (o.wpath || o.jpath || o.rate_hz || o.afc_ms > 0.0 || o.track_ms > 0.0));
+    return !(o.window_bytes && (o.wpath || o.jpath || o.rate_hz || o.afc_ms > 0.0 || o.track_ms > 0.0 || o.scan_ms > 0.0));
 }
 
 // device memory (hipMalloc) or pinned host memory (hipHostMalloc); p is null when there was none: the caller has the message
@@ -434,6 +445,43 @@ public:
     }
 };
 
+// -S MS: the survey (docs/SPEC.md 3.0h) of the first MS ms of the capture with N = 4096, hop 2048, the designed window and shift 16
+// -> the {"event":"scan"} line with the active channels of the 12.5 kHz raster, strongest first.  The input is back at its start.
+static std::string survey(Handle& h, const Options& o, std::ifstream& in)
+{
+    constexpr int32_t N = 4096;
+    p25fe_scan_t* made = nullptr;
+    expect(p25fe_scan_create(h.get(), N, N / 2, nullptr, 16, &made), "unable to make the survey");
+    const std::unique_ptr<p25fe_scan_t, void (*)(p25fe_scan_t*)> sc(made, p25fe_scan_destroy);
+    size_t left = std::max<size_t>(1, (size_t)((double)o.rate_hz * o.scan_ms / 1000.0));
+    for (std::vector<char> chunk; left;) {
+        const size_t want = std::min(left, (size_t)1 << 22);
+        chunk.resize(want * o.bps);
+        in.read(chunk.data(), (std::streamsize)chunk.size());
+        const size_t got = (size_t)in.gcount() / o.bps;
+        if (got) expect(p25fe_scan(sc.get(), chunk.data(), o.fmt, got), "unable to survey the capture");
+        left -= got;
+        if (got < want) break;                                        // (a capture shorter than MS ms: what there is)
+    }
+    in.clear();
+    in.seekg(0);
+    std::vector<uint64_t> acc((size_t)N + 1);
+    expect(p25fe_scan_read(sc.get(), acc.data(), 0), "unable to read the survey");
+    std::vector<p25fe_scan_chan_t> ch(256);
+    size_t n = 0;
+    expect(p25fe_scan_channels(acc.data(), N, (uint32_t)o.rate_hz, 12500.0, 4000.0, 20.0, ch.data(), ch.size(), &n), "unable to list the channels");
+    char buf[160];
+    std::snprintf(buf, sizeof buf, "{\"event\":\"scan\",\"n_frames\":%" PRIu64 ",\"channels\":[", acc[(size_t)N]);
+    std::string line = buf;
+    for (size_t i = 0; i < std::min(n, ch.size()); ++i) {
+        const double db = ch[i].db_over_floor < 999.0 ? ch[i].db_over_floor : 999.0;              // (JSON has no infinity)
+        std::snprintf(buf, sizeof buf, "%s{\"raster_index\":%d,\"centre_hz\":%.1f,\"db_over_floor\":%.2f,\"offset_hz\":%.1f}", i ? "," : "",
+                      ch[i].raster_index, ch[i].centre_hz, db, ch[i].offset_hz);
+        line += buf;
+    }
+    return line + "]}";
+}
+
 int main(int argc, char** argv)
 try {
     Options o;
@@ -442,12 +490,20 @@ try {
     if (!in) fail("unable to open %s\n", o.in_path);
     Handle h(0, 1);
     if (o.window_bytes) return bulk(h, o, in);
+    std::string scan_event;
+    if (o.scan_ms > 0.0) {
+        scan_event = survey(h, o, in);
+        std::printf("%s\n", scan_event.c_str());
+        std::fflush(stdout);
+        if (o.offset.kind == o.offset.NONE) return 0;                 // a survey alone
+    }
     Hub hub;
     Chan<Baseband> chan;
     Sink sink;
     sink.out.open(o.out_path, std::ios::binary);
     sink.keep = o.jpath != nullptr;
     if (o.jpath && !(hub.js = std::fopen(o.jpath, "w"))) fail("unable to open %s\n", o.jpath);
+    if (hub.js && !scan_event.empty()) std::fprintf(hub.js, "%s\n", scan_event.c_str());
     std::ofstream bbfile;                                             // samples_file, src/main.rs:174-175
     if (o.wpath) bbfile.open(o.wpath, std::ios::binary);
     if (o.wpath && !bbfile) fail("unable to open baseband file\n");
