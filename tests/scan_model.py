@@ -82,6 +82,74 @@ def record(x, N, hop, w, shift, first=0, n=None, n_hist=None):
     return acc
 
 
+def frame_records(X, shift):
+    """X [frames, N] -> one record per frame, uint64 [frames, N + 1]: Q(P_f) and a frame count of 1"""
+    q = quantise(X, shift)
+    rec = np.ones((q.shape[0], q.shape[1] + 1), dtype=np.uint64)
+    rec[:, :-1] = q.astype(np.uint64)
+    return rec
+
+
+def wrapping_sum(rec):
+    """records [k, N + 1] -> their sum as uint64 words, modulo 2^64"""
+    return np.asarray(rec, dtype=np.uint64).sum(axis=0, dtype=np.uint64)
+
+
+def delta(N, w, x):
+    """3.0h's bound on |X|: 8 log2(N) 2^-24 sum|w| max|x|"""
+    return 8.0 * np.log2(N) * 2.0 ** -24 * np.abs(np.asarray(w, dtype=np.float64)).sum() * np.abs(np.asarray(x, dtype=np.complex128)).max()
+
+
+def frame_bound(X, d, shift):
+    """the bound on |acc - Q(P)| of every frame and bin, [frames, N]: |dP| <= 2 |X| d + d^2, times 2^shift, plus one unit for
+    the rounding of Q"""
+    return (2.0 * np.abs(X) * d + d * d) * 2.0 ** shift + 1.0
+
+
+def as_ints(a):
+    """uint64 words or float64 holding integers -> Python integers (an object array): differences above 2^53 stay exact"""
+    return np.array([int(v) for v in np.asarray(a).reshape(-1)], dtype=object).reshape(np.shape(a))
+
+
+def shifted(x, d):
+    """the stream that begins d samples earlier: d zero samples in front of x, so that sample k of x stands at position k + d"""
+    return np.concatenate([np.zeros(d, dtype=np.complex128), np.asarray(x, dtype=np.complex128)])
+
+
+def scan_frames(sc, iq, f0, frames):
+    """the GPU's record of every frame by itself: one Scanner.scan_dev call per frame f = f0 .. f0 + frames - 1 into a fresh record,
+    n_hist = N - 1, n = hop, the range [f hop, f hop + hop) of a device capture that starts at position 0 (f0 hop >= N - 1)
+    -> uint64 [frames, N + 1]"""
+    import torch
+    assert f0 * sc.hop >= sc.N - 1 and (f0 + frames) * sc.hop <= iq.shape[0]
+    rec = torch.zeros((frames, sc.N + 1), dtype=torch.int64, device=iq.device)
+    for k in range(frames):
+        at = (f0 + k) * sc.hop
+        sc.scan_dev(iq, n_hist=sc.N - 1, abs0=at, offset=at, n=sc.hop, acc=rec[k])
+    return rec.cpu().numpy().view(np.uint64).copy()
+
+
+# ---- the saturating scene of the tests of Q's edges: one strong tone on a bin under a caller's window 8 x Hann at shift 40
+SAT_N, SAT_HOP, SAT_SHIFT, SAT_BIN, SAT_GAIN = 1024, 256, 40, 100, 8.0
+_SAT = {}
+
+
+def saturating_capture():
+    """0.75 e^{2 pi i 100 t / N} plus noise of sigma 0.01 per component (default_rng(77)), 4 N + 16 samples, made once ->
+    {format: raw samples}: bin 100's power times 2^40 passes 2^62 in every frame with full history"""
+    if not _SAT:
+        n = 4 * SAT_N + 16
+        t = np.arange(n, dtype=np.float64)
+        g = np.random.default_rng(77).standard_normal((n, 2))
+        x = (0.75 * np.exp(2j * np.pi * SAT_BIN * t / SAT_N) + 0.01 * (g[:, 0] + 1j * g[:, 1])).astype(np.complex64)
+        _SAT.update({"cf32": x, "s16": to_s16(x), "u8": to_u8(x)})
+    return _SAT
+
+
+def saturating_window():
+    return (window(SAT_N).astype(np.float64) * SAT_GAIN).astype(F)   # (a power of two: exact)
+
+
 def bin_hz(N, fs):
     b = np.arange(N)
     return np.where(b < N // 2, b, b - N).astype(np.float64) * float(fs) / N

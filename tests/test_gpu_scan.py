@@ -4,7 +4,9 @@ The DFT is fp32 and factored, so the sums are compared with the model's within 3
 fixed per-frame sequence of operations promise is compared bit for bit: splits, missing history, the formats, the position, the
 host streaming form.  Shapes: N = 1024 at hop 512 with 9 owned frames (two workgroups: a batch is 8 frames), N = 4096 at hop 2048
 with 6, and N = 1024 at hop 1024 (no overlap: the whole ring is rewritten per frame) with 9; ranges start 24 samples past a hop's
-multiple, so the loader's vectors are misaligned against the frames in every format.
+multiple, so a workgroup's strip starts inside a hop -- but on a 16-byte vector of every format (24 is a multiple of 8 samples):
+only the host streaming test puts frames off the loader's vectors here.  Positions that are no multiple of 8, hops of N/4 and below,
+every frame by itself and Q's edges: tests/test_gpu_scan_edges.py.
 
 Largest error observed on an MI355X as a fraction of the bound: see docs/MEASUREMENTS.md, "Survey"."""
 import ctypes as C
@@ -32,6 +34,15 @@ def mods():
     return _lib, FrontEnd, Scanner, Tuner
 
 
+def signal(N, hop, length):
+    """seeded noise plus two tones from position 0, complex64 [length]"""
+    rng = np.random.default_rng(N + hop)
+    t = np.arange(length, dtype=np.float64)
+    x = 0.2 * (rng.standard_normal(len(t)) + 1j * rng.standard_normal(len(t))) / np.sqrt(2.0)
+    x += 0.3 * np.exp(2j * np.pi * 0.1234 * t) + 0.25 * np.exp(-2j * np.pi * (37.5 / N) * t + 1.0j)
+    return x.astype(np.complex64)
+
+
 class Case:
     """seeded noise plus two tones from position 0: the raw samples of every format, their converted samples, and the range
     [first, first + n) that owns `frames` frames with all of its history in memory"""
@@ -41,11 +52,7 @@ class Case:
         self.first = N + hop + 24
         self.n = frames * hop + 16
         assert SM.n_frames(hop, self.first, self.n) == frames and self.first % hop and self.first % 8 == 0
-        rng = np.random.default_rng(N + hop)
-        t = np.arange(self.first + self.n + 8, dtype=np.float64)
-        x = 0.2 * (rng.standard_normal(len(t)) + 1j * rng.standard_normal(len(t))) / np.sqrt(2.0)
-        x += 0.3 * np.exp(2j * np.pi * 0.1234 * t) + 0.25 * np.exp(-2j * np.pi * (37.5 / N) * t + 1.0j)
-        x = x.astype(np.complex64)
+        x = signal(N, hop, self.first + self.n + 8)
         self.raw = {"cf32": x, "s16": SM.to_s16(x), "u8": SM.to_u8(x)}
         self.cf = {"cf32": x, "s16": conv(self.raw["s16"]), "u8": conv(self.raw["u8"])}
         self.w = SM.window(N)

@@ -1,7 +1,9 @@
 """CPU tests of the host side of the survey (docs/SPEC.md 3.0h): the ABI surface, p25fe_scan_window against the formula bit for
 bit, every refusal that needs no device, and p25fe_scan_channels on the records of the numpy model (tests/scan_model.py) for the
 scene the survey's tests share -- four C4FM sources a crystal's few ppm off the raster in a 2.5 Msps capture with white noise --
-in all three formats, plus ties, a short output array and a record of zero frames.  The GPU side is tests/test_gpu_scan.py."""
+in all three formats, plus ties, a short output array and a record of zero frames; and the model's own per-frame records with
+the premise of the clamp test (bin 100 surely saturated, no ambiguous bin).  The GPU side is tests/test_gpu_scan.py and
+tests/test_gpu_scan_edges.py."""
 import ctypes as C
 import json
 import os
@@ -237,3 +239,50 @@ def test_ties_short_output_and_empty_records(lib):
         assert L.p25fe_scan_channels(ap, N, fs, 12500.0, bw, 20.0, op, 4, C.byref(n_sz)) == lib.ERR_ARG
     for thr in (float("nan"), float("inf"), float("-inf")):
         assert L.p25fe_scan_channels(ap, N, fs, 12500.0, 4000.0, thr, op, 4, C.byref(n_sz)) == lib.ERR_ARG
+
+
+def _converted(raw):
+    spec = json.load(open(os.path.join(ROOT, "tests", "golden", "spec.json")))
+    return {"cf32": raw["cf32"], "s16": SM.convert_s16(raw["s16"]), "u8": SM.convert_u8(raw["u8"], spec["u8_scale"], spec["u8_offset"])}
+
+
+def test_the_models_record_is_the_wrapping_sum_of_its_frames():
+    """record() of a range equals the sum modulo 2^64 of frame_records() of the same frames, word for word: on a noisy signal at
+    a small hop with part of the history missing, and on the saturating scene, where four frames of 2^62 wrap bin 100 to zero"""
+    rng = np.random.default_rng(11)
+    x = (0.3 * (rng.standard_normal(3000) + 1j * rng.standard_normal(3000))).astype(np.complex64)
+    w = SM.window(1024)
+    for first, n, n_hist in ((1024 + 24, 70 * 8 + 16, None), (520, 1400, 100), (0, 3000, 0)):
+        X = SM.spectra(x, 1024, 8, w, first, n, n_hist)
+        rec = SM.frame_records(X, 16)
+        assert rec.shape == (SM.n_frames(8, first, n), 1025) and (rec[:, 1024] == 1).all()
+        assert np.array_equal(SM.wrapping_sum(rec), SM.record(x, 1024, 8, w, 16, first, n, n_hist))
+    cf = _converted(SM.saturating_capture())
+    N, H = SM.SAT_N, SM.SAT_HOP
+    for fmt, c in cf.items():
+        X = SM.spectra(c, N, H, SM.saturating_window(), N, 4 * H)
+        rec = SM.frame_records(X, SM.SAT_SHIFT)
+        assert (rec[:, SM.SAT_BIN] == np.uint64(1 << 62)).all(), fmt
+        whole = SM.record(c, N, H, SM.saturating_window(), SM.SAT_SHIFT, N, 4 * H)
+        assert np.array_equal(SM.wrapping_sum(rec), whole) and int(whole[SM.SAT_BIN]) == 0 and int(whole[N]) == 4
+        assert int(SM.wrapping_sum(rec[:3])[SM.SAT_BIN]) == 3 << 62
+        assert sum(int(v) for v in rec[:, SM.SAT_BIN]) == 1 << 64    # (as Python integers: the sum the words wrapped)
+
+
+def test_the_saturating_scene_has_no_ambiguous_bin():
+    """what tests/test_gpu_scan_edges.py's clamp test rests on, in all three formats: in every frame with full history bin 100's
+    scaled power exceeds 2^62 by more than 3.0h's bound, so any conforming implementation clamps it; every other bin stays below
+    2^62 by more than the bound, so none may; and the largest of those is above 2^61, so a clamp set one bit low would show"""
+    cf = _converted(SM.saturating_capture())
+    N, H, w = SM.SAT_N, SM.SAT_HOP, SM.saturating_window()
+    for fmt, c in cf.items():
+        X = SM.spectra(c, N, H, w, N, 4 * H)
+        assert X.shape == (4, N)
+        v = np.ldexp((X.real * X.real + X.imag * X.imag).astype(np.float32).astype(np.float64), SM.SAT_SHIFT)
+        bound = SM.frame_bound(X, SM.delta(N, w, c), SM.SAT_SHIFT)
+        others = np.arange(N) != SM.SAT_BIN
+        assert (v[:, SM.SAT_BIN] - bound[:, SM.SAT_BIN] > 2.0 ** 62).all(), fmt
+        assert (v[:, others] + bound[:, others] < 2.0 ** 62).all(), fmt
+        top = v[:, others].max() / 2.0 ** 62
+        print("%s: bin 100 at %.2f x 2^62, the largest other bin at %.3f x 2^62" % (fmt, v[:, SM.SAT_BIN].min() / 2.0 ** 62, top))
+        assert 0.5 < top < 0.6
