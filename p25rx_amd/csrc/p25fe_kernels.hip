@@ -760,6 +760,45 @@ struct K1Args {
 #ifndef P25FE_K1_PF_S16
 #define P25FE_K1_PF_S16 1
 #endif
+// ------------------------------------------------------------------------------------------
+// Stages of K1's planar output that frontend_body (every k_frontend / k_chunk kernel) and k_frontend_pair share as functions.
+// Builtins only: hipRTC compiles them too.  These two are the stages that could be taken out of the two bodies with every
+// kernel's instruction text unchanged; docs/MEASUREMENTS.md says what the other seven did and why they stay written out twice.
+// ------------------------------------------------------------------------------------------
+// Transposed read of OUT into the planar form: lanes 0..31 take planes 0..4, lanes 32..63 planes 5..9 of the sub-tile's 32 symbols
+// (lane = (half h = tid >> 5, symbol pl_sym = tid & 31), pl_h5 = 5 h; lane stride 10 dwords: a 2-way conflict on 5 reads); a ballot
+// of the sign bits is one 32-symbol word of two planes at once.  Returns the sign words: lane q < 10 holds plane q's.
+__device__ __forceinline__ unsigned k1_planes_from_out(const float* OUT, int pl_sym, int pl_h5, float (&outv)[5])
+{
+    unsigned w = 0u;
+    unsigned long long sg[5];
+#pragma unroll
+    for (int q = 0; q < 5; ++q) {
+        outv[q] = OUT[SPS_ * pl_sym + pl_h5 + q];
+        sg[q] = __builtin_amdgcn_ballot_w64(__float_as_int(outv[q]) < 0);
+    }
+    if constexpr (!P25FE_M_NO_SIGN_PLANES) w = lanes_from_ballots(sg);            // lane q: word of plane q, lane q + 5: plane q + 5
+    return w;
+}
+
+// The launch's last workgroup to finish publishes done_flag[0] = done_seq (K1Args::done_flag), behind its own stores.
+__device__ __forceinline__ void k1_publish_done(unsigned* done_flag, unsigned done_seq, int tid)
+{
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");               // the compiler may drop the wait behind the write-back
+    unsigned ticket = 0u;
+    if (tid == 0) ticket = __hip_atomic_fetch_add(done_flag + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    ticket = (unsigned)__builtin_amdgcn_readfirstlane((int)ticket);
+    if (ticket == gridDim.x * gridDim.y - 1u) {
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        if (tid == 0) {
+            __hip_atomic_store(done_flag + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(done_flag, done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
 template <int FMT, bool CT, int PK, int OM = OUT_LINEAR, int TX = 0>
 __device__ __forceinline__ void frontend_body(const K1Args& a, const Taps* __restrict__ gtaps)
 {
@@ -1241,16 +1280,7 @@ __device__ __forceinline__ void frontend_body(const K1Args& a, const Taps* __res
 #pragma unroll
             for (int q = 0; q < P; ++q) outv[q] = OUT[tid + q * WV];
         } else {
-            // polyphase: lanes 0..31 take planes 0..4, lanes 32..63 planes 5..9 of the sub-tile's 32 symbols (lane stride 10
-            // dwords: a 2-way conflict on 5 reads); a ballot of the sign bits is one 32-symbol word of two planes at once.
-            unsigned w = 0u;
-            unsigned long long sg[5];
-#pragma unroll
-            for (int q = 0; q < P; ++q) {
-                outv[q] = OUT[SPS_ * pl_sym + pl_h5 + q];
-                sg[q] = __builtin_amdgcn_ballot_w64(__float_as_int(outv[q]) < 0);
-            }
-            if constexpr (!P25FE_M_NO_SIGN_PLANES) w = lanes_from_ballots(sg);        // lane q: word of plane q, lane q + 5: plane q + 5
+            const unsigned w = k1_planes_from_out(OUT, pl_sym, pl_h5, outv);      // polyphase; lane q < 10: sign word of plane q
             if constexpr (PRO) {
                 bitsv = w;
             } else {
@@ -1286,21 +1316,7 @@ __device__ __forceinline__ void frontend_body(const K1Args& a, const Taps* __res
     }
     }   // work items
     if constexpr (OM == OUT_PLANAR) {
-        if (a.done_flag) {                                          // uniform
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // the compiler may drop the wait behind the write-back
-            unsigned ticket = 0u;
-            if (tid == 0) ticket = __hip_atomic_fetch_add(a.done_flag + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            ticket = (unsigned)__builtin_amdgcn_readfirstlane((int)ticket);
-            if (ticket == gridDim.x * gridDim.y - 1u) {
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                if (tid == 0) {
-                    __hip_atomic_store(a.done_flag + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(a.done_flag, a.done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-                }
-            }
-        }
+        if (a.done_flag) k1_publish_done(a.done_flag, a.done_seq, tid);       // uniform
     }
     P25FE_M_EXIT;
 }
@@ -1327,7 +1343,9 @@ __global__ __launch_bounds__(WV, k1_wps(FMT, CT, PK, OM)) void k_frontend(K1Args
 //   wave 1, the consumer: channel FIR from buf[t & 1], discriminator, boxcar, transpose, sign words, the plane stores.
 // Neither wave holds the other's registers, so both fit 128 VGPRs (four waves per SIMD) in the prologue form that the one-wave
 // cf32 kernel has no room for (174 VGPRs): every sub-tile is one block of the layout -- ten whole 128-byte rows, ten whole sign
-// words -- and no halo sub-tile is recomputed.  Same cfma order, fm_discriminate and boxcar rule as frontend_body: the same bits.
+// words -- and no halo sub-tile is recomputed.  Same cfma order, fm_discriminate and boxcar rule as frontend_body: the same bits;
+// the transposed read with its sign ballots and the done_flag publication are frontend_body's own functions (k1_planes_from_out,
+// k1_publish_done).
 //
 // LDS (20 096 B: eight workgroups = 16 waves per CU): [window XIN_N | d buffer 0: carry 40 + 320 | d buffer 1 | OUT 320 floats].
 // The window region is the producer's alone, OUT the consumer's -- except that the producer parks the prologue's ND decimator
@@ -1569,13 +1587,7 @@ __global__ __launch_bounds__(2 * WV, 4) void k_frontend_pair(K1Args a, const Tap
                 }
             }
             phase_sync();
-            unsigned long long sgn[5];
-#pragma unroll
-            for (int q = 0; q < P; ++q) {
-                outv[q] = OUT[SPS_ * pl_sym + pl_h5 + q];
-                sgn[q] = __builtin_amdgcn_ballot_w64(__float_as_int(outv[q]) < 0);
-            }
-            bitsv = lanes_from_ballots(sgn);
+            bitsv = k1_planes_from_out(OUT, pl_sym, pl_h5, outv);
             out_rel = t * SUB;
             phase_sync();
         }
@@ -1583,21 +1595,7 @@ __global__ __launch_bounds__(2 * WV, 4) void k_frontend_pair(K1Args a, const Tap
     }
     }   // n_sub > 0
     // the launch's last workgroup publishes done_flag (as k_frontend does): the consumer wave, behind its own stores
-    if (role == 1 && a.done_flag) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        unsigned ticket = 0u;
-        if (tid == 0) ticket = __hip_atomic_fetch_add(a.done_flag + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ticket = (unsigned)__builtin_amdgcn_readfirstlane((int)ticket);
-        if (ticket == gridDim.x * gridDim.y - 1u) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-            if (tid == 0) {
-                __hip_atomic_store(a.done_flag + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(a.done_flag, a.done_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-    }
+    if (role == 1 && a.done_flag) k1_publish_done(a.done_flag, a.done_seq, tid);
 }
 #endif  // !P25FE_JIT
 

@@ -1,8 +1,10 @@
 """k_frontend_pair from a gfx950 cross-compile (needs no GPU): its budget -- at most 128 VGPRs (four waves per SIMD), no scratch,
 at most 20 480 B of LDS per workgroup (eight workgroups = 16 waves per CU), no violation of the hand-issued LDS reads' invariant --
-and the text of every k_frontend / k_chunk kernel beside it, which must be what it was before the pair kernel existed:
+and the text of every k_frontend / k_chunk kernel beside it, which must be what it was before the pair kernel existed, and the pair
+kernel's own, which must be what it was before stages of the sub-tile became functions shared with frontend_body:
 tests/golden/k1_isa_text.json holds, per mangled name, the line count and SHA-256 of the normalised text (tools/isa_text.py) of the
-commit in front of it.  (A compiler update changes those hashes: regenerate the file from the parent commit's build then.)"""
+commit in front of that change.  (A compiler update changes those hashes: regenerate the file from the parent commit's build then.)
+The text is pinned because equal instruction counts are not enough: a commuted v_add_f32 picks the other operand's NaN payload."""
 import json
 import os
 import re
@@ -53,7 +55,7 @@ def test_one_wave_kernels_text_is_unchanged():
     import isa_text
     _remarks()
     want = json.load(open(os.path.join(ROOT, "tests", "golden", "k1_isa_text.json")))
-    got = isa_text.functions(ASM)
+    got = isa_text.functions(ASM, isa_text.K1_PREFIXES + (PAIR,))
     assert sorted(got) == sorted(want), (sorted(set(got) ^ set(want)))
     diff = [n for n in want if got[n] != want[n]]
     assert not diff, diff
