@@ -217,6 +217,18 @@ pub struct ScanChan {
     pub db_over_floor: f64,
     pub offset_hz: f64,
 }
+/// p25fe_waterfall_key_t: one keyed interval of a survey over time, docs/SPEC.md 3.0i (48 bytes)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct WaterfallKey {
+    pub raster_index: i32,
+    pub reserved: i32,
+    pub first_slot: u64,
+    pub n_slots: u64,
+    pub centre_hz: f64,
+    pub offset_hz: f64,
+    pub peak_db_over_floor: f64,
+}
 /// P25FE_TUNE_MAX_CH / _DEN: 1 <= channels <= 256; num / den in lowest terms, 1 <= den <= 8192, 2 |num| <= den
 pub const TUNE_MAX_CH: i32 = 256;
 pub const TUNE_MAX_DEN: i32 = 8192;
@@ -322,6 +334,16 @@ extern "C" {
     pub fn p25fe_scan_read(sc: *mut Scan, acc_out: *mut u64, clear: c_int) -> c_int;
     pub fn p25fe_scan_channels(acc: *const u64, n: i32, fs_hz: u32, raster_hz: f64, half_bw_hz: f64, thr_db: f64, out: *mut ScanChan,
                                cap: usize, n_out: *mut usize) -> c_int;
+    // survey over time (docs/SPEC.md 3.0i): the frames of a range into one row of N + 1 words per slot of B frames, and keyed intervals
+    pub fn p25fe_waterfall_slots(hop: i32, b: u32, abs_first: u64, n: usize, first_slot: *mut u64, n_slots: *mut usize) -> c_int;
+    pub fn p25fe_waterfall_dev(sc: *mut Scan, d_iq: *const c_void, fmt: c_int, n_hist: usize, n: usize, abs_first: u64, b: u32,
+                               slot0: u64, d_rows: *mut u64, n_rows: usize, row_stride: usize, stream: *mut c_void) -> c_int;
+    pub fn p25fe_waterfall_open(sc: *mut Scan, b: u32, max_rows: usize) -> c_int;
+    pub fn p25fe_waterfall(sc: *mut Scan, iq: *const c_void, fmt: c_int, n: usize) -> c_int;
+    pub fn p25fe_waterfall_read(sc: *mut Scan, rows_out: *mut u64, cap_rows: usize, n_rows: *mut usize) -> c_int;
+    pub fn p25fe_waterfall_keys(rows: *const u64, n_rows: usize, row_stride: usize, n: i32, fs_hz: u32, slot0: u64, raster_hz: f64,
+                                half_bw_hz: f64, on_db: f64, off_db: f64, min_slots: u32, out: *mut WaterfallKey, cap: usize,
+                                n_out: *mut usize) -> c_int;
     pub fn p25fe_n_baseband(abs0: u64, n: usize) -> usize;
     pub fn p25fe_slice_dev(h: *mut Handle, d_bb: *const f32, bb_stride: usize, n_hist_bb: usize, n_bb: usize, abs_bb0: u64,
                            d_anchor_in: *const Anchor, d_dibits: *mut u8, dibit_stride: usize, d_sync_pos: *mut i64,

@@ -683,6 +683,58 @@ int p25fe_scan_read(p25fe_scan_t *sc, uint64_t *acc_out, int clear);
 int p25fe_scan_channels(const uint64_t *acc, int32_t N, uint32_t fs_hz, double raster_hz, double half_bw_hz, double thr_db,
                         p25fe_scan_chan_t *out, size_t cap, size_t *n_out);
 
+/* ---- survey over time: per-slot spectra in one launch, and keyed intervals (docs/SPEC.md 3.0i) --------------------------------------
+ * Which raster channel was keyed from when to when.  Frames, window, X_f, P_f and Q are 3.0h's and the object is a p25fe_scan_t (its
+ * N, hop, window, shift and device).  With B >= 1 frames per slot, frame f (ABSOLUTE: the one that ends at f H + H - 1) belongs to
+ * slot s = f / B, and a call adds Q(P_f[b]) into row[s - slot0][b] and 1 into row[s - slot0][N] of d_rows[n_rows][row_stride]
+ * (uint64, wrapping); words N + 1 .. row_stride - 1 of a row are never written.  Integer sums commute: any split of a stream into
+ * calls, inside a slot included, gives the same bytes; the wrapping sum of the rows of a range is p25fe_scan_dev's record of it, and
+ * with B = 1 a row is that frame's record. */
+typedef struct p25fe_waterfall_key {
+    int32_t raster_index;    /* r: the channel is centred r * raster_hz from the capture's centre */
+    int32_t reserved;        /* 0 */
+    uint64_t first_slot;     /* the interval's first slot (slot0 + its first row) */
+    uint64_t n_slots;        /* ... and its length in slots */
+    double centre_hz;        /* r * raster_hz */
+    double offset_hz;        /* centroid of the channel's raster cell over the interval's rows minus centre_hz */
+    double peak_db_over_floor;   /* the largest per-row power over that row's floor, dB (+inf over a floor of zero) */
+} p25fe_waterfall_key_t;     /* 48 bytes */
+
+/* The slots the frames of [abs_first, abs_first + n) at this hop fall into: [*first_slot, *first_slot + *n_slots); n_slots = 0 when
+ * the range owns no frame.  Host only.  P25FE_ERR_ARG: a null pointer, hop not a multiple of 8 from 8 to 4096 that divides 4096,
+ * B = 0 or B > 2^20, abs_first or n >= 2^62. */
+int p25fe_waterfall_slots(int32_t hop, uint32_t B, uint64_t abs_first, size_t n, uint64_t *first_slot, size_t *n_slots);
+/* One device-resident range, p25fe_scan_dev's conventions, except that abs_first matters in full: ADDS the range's frames into the
+ * rows of their slots, row i standing for slot slot0 + i (device, 8-byte aligned; zero them to open a survey).  One launch;
+ * enqueues on `stream`, synchronises nothing.  A range that owns no frame returns P25FE_OK and writes nothing.
+ * P25FE_ERR_ARG (before any device is touched): p25fe_scan_dev's refusals, B = 0 or B > 2^20, row_stride < N + 1, d_rows null or
+ * misaligned, n_rows = 0 while the range owns a frame.  P25FE_ERR_CAPACITY: the range owns a frame whose slot lies outside
+ * [slot0, slot0 + n_rows) -- nothing is enqueued and nothing written. */
+int p25fe_waterfall_dev(p25fe_scan_t *sc, const void *d_iq, int fmt, size_t n_hist, size_t n, uint64_t abs_first, uint32_t B,
+                        uint64_t slot0, uint64_t *d_rows, size_t n_rows, size_t row_stride, void *stream);
+/* The host streaming form.  _open allocates and zeroes [max_rows][N + 1] on the device for slots of B frames from slot 0 (a second
+ * open replaces the first; P25FE_ERR_ARG: B = 0 or > 2^20, max_rows = 0 or > 2^20).  p25fe_waterfall is p25fe_scan with the call's
+ * frames going into the rows: it shares the object's position, carried history and format rule, so the two may be mixed on one
+ * stream, each call's frames going where that call sends them.  P25FE_ERR_CAPACITY: the call would pass the last row; nothing is
+ * consumed (the arguments and the format are checked first).  _read waits for the device and copies the *n_rows =
+ * min(ceil(frames so far / B), max_rows) rows touched so far (P25FE_ERR_CAPACITY with *n_rows set when cap_rows is smaller).  Frames
+ * count whichever call took them and p25fe_scan has no last row: a stream may run past the rows, the count then stays at max_rows
+ * and every further p25fe_waterfall that owns a frame is P25FE_ERR_CAPACITY.  p25fe_scan_reset also zeroes the open rows.  Without an open, p25fe_waterfall and
+ * _read are P25FE_ERR_ARG. */
+int p25fe_waterfall_open(p25fe_scan_t *sc, uint32_t B, size_t max_rows);
+int p25fe_waterfall(p25fe_scan_t *sc, const void *iq, int fmt, size_t n);
+int p25fe_waterfall_read(p25fe_scan_t *sc, uint64_t *rows_out, size_t cap_rows, size_t *n_rows);
+/* Rows the caller has copied back -> keyed intervals; host only.  Eligible raster indices, pow[t][r] and the floor of row t are
+ * p25fe_scan_channels' rules applied to every row t with row[t][N] > 0.  Channel r turns on at the first row where pow > 0 and
+ * pow >= floor 10^(on_db / 10) and stays on while pow >= floor 10^(off_db / 10); a row of zero frames and the end of the rows end
+ * every open interval; intervals shorter than min_slots are dropped.  offset_hz is the centroid over the raster cell of the bins
+ * summed as doubles over the interval's rows; peak_db_over_floor the largest per-row ratio.  Sorted by first_slot, then
+ * raster_index.  *n_out counts all intervals even beyond cap.  Recommended: on_db = 20, off_db = 14, min_slots = 2.
+ * P25FE_ERR_ARG: p25fe_scan_channels' refusals, row_stride < N + 1, off_db > on_db, a number not finite, min_slots = 0. */
+int p25fe_waterfall_keys(const uint64_t *rows, size_t n_rows, size_t row_stride, int32_t N, uint32_t fs_hz, uint64_t slot0,
+                         double raster_hz, double half_bw_hz, double on_db, double off_db, uint32_t min_slots,
+                         p25fe_waterfall_key_t *out, size_t cap, size_t *n_out);
+
 /* stages 6-7 on device baseband.  d_bb points at the first owned sample; n_hist_bb valid
  * samples precede it; abs_bb0 is its absolute index; d_anchor_in (nullable = no lock) is the
  * carry-in per channel.  d_result[c] is filled per channel.

@@ -76,6 +76,9 @@ SCAN_MAX_SHIFT = 40                                                 # P25FE_SCAN
 SCAN_CHAN_DTYPE = np.dtype([("raster_index", "<i4"), ("reserved", "<i4"), ("centre_hz", "<f8"), ("db_over_floor", "<f8"),
                             ("offset_hz", "<f8")])                                             # p25fe_scan_chan_t
 assert SCAN_CHAN_DTYPE.itemsize == 32
+WATERFALL_KEY_DTYPE = np.dtype([("raster_index", "<i4"), ("reserved", "<i4"), ("first_slot", "<u8"), ("n_slots", "<u8"),
+                                ("centre_hz", "<f8"), ("offset_hz", "<f8"), ("peak_db_over_floor", "<f8")])   # p25fe_waterfall_key_t
+assert WATERFALL_KEY_DTYPE.itemsize == 48
 
 # every symbol include/p25fe.h declares (tests check the library exports exactly these)
 SYMBOLS = [
@@ -102,6 +105,8 @@ SYMBOLS = [
     "p25fe_track_read", "p25fe_track_step", "p25fe_track_hz",
     "p25fe_scan_window", "p25fe_scan_create", "p25fe_scan_destroy", "p25fe_scan_reset", "p25fe_scan_dev", "p25fe_scan", "p25fe_scan_read",
     "p25fe_scan_channels",
+    "p25fe_waterfall_slots", "p25fe_waterfall_dev", "p25fe_waterfall_open", "p25fe_waterfall", "p25fe_waterfall_read",
+    "p25fe_waterfall_keys",
     "p25fe_debug_planes_size", "p25fe_debug_planes_dev",
 ]
 
@@ -248,6 +253,13 @@ def load():
     L.p25fe_scan.argtypes = [vp, vp, C.c_int, sz]
     L.p25fe_scan_read.argtypes = [vp, vp, C.c_int]
     L.p25fe_scan_channels.argtypes = [vp, C.c_int32, C.c_uint32, C.c_double, C.c_double, C.c_double, vp, sz, psz]
+    L.p25fe_waterfall_slots.argtypes = [C.c_int32, C.c_uint32, u64, sz, C.POINTER(u64), psz]
+    L.p25fe_waterfall_dev.argtypes = [vp, vp, C.c_int, sz, sz, u64, C.c_uint32, u64, vp, sz, sz, vp]
+    L.p25fe_waterfall_open.argtypes = [vp, C.c_uint32, sz]
+    L.p25fe_waterfall.argtypes = [vp, vp, C.c_int, sz]
+    L.p25fe_waterfall_read.argtypes = [vp, vp, sz, psz]
+    L.p25fe_waterfall_keys.argtypes = [vp, sz, sz, C.c_int32, C.c_uint32, u64, C.c_double, C.c_double, C.c_double, C.c_double,
+                                       C.c_uint32, vp, sz, psz]
     L.p25fe_n_predecim.argtypes = [u64, sz]
     L.p25fe_n_predecim.restype = sz
     L.p25fe_n_baseband.argtypes = [u64, sz]

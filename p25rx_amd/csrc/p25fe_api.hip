@@ -3266,3 +3266,4 @@ P25FE_M_API_EXTRAS
 }  // extern "C"
 
 #include "p25fe_scan.inc"       // survey (SPEC 3.0h): k_scan and its entry points
+#include "p25fe_waterfall.inc"  // survey over time (SPEC 3.0i): k_waterfall and its entry points

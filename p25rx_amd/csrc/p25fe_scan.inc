@@ -14,7 +14,8 @@
 // on the frame.  Radix 4 holds them in registers.  Radix 16 cannot at two workgroups per CU (256 registers a lane): pass 1's 240
 // distinct twiddle pairs sit in LDS, the last pass's 15 pairs a lane and the 16 window values are read per frame from the tables,
 // which L2 serves.  A frame's arithmetic is one fixed sequence of operations on its N converted samples: the values do not depend
-// on the workgroup or on the frame's place in its batch.
+// on the workgroup or on the frame's place in its batch.  The body is sc_frames, which k_waterfall (p25fe_waterfall.inc, SPEC 3.0i)
+// shares: there the sums go into one row per slot of B frames instead.
 #ifndef P25FE_SCAN_INC
 #define P25FE_SCAN_INC
 
@@ -90,8 +91,22 @@ __device__ __forceinline__ unsigned long long sc_q(float2 X, float scale)
     return (unsigned long long)(long)__builtin_rintf(s);
 }
 
-template <int FMT, bool LUTM, int N>
-__global__ __launch_bounds__(SC_WG, 2) void k_scan(SurveyArgs a, WideConv cv)
+// where the frames of a launch go when they go into rows (SPEC 3.0i; p25fe_waterfall.inc): frame f0 + g of the range belongs to
+// slot (f0 + g) / B, whose row is acc + (slot - slot0) stride.  All of it is uniform: the compiler keeps it in scalar registers
+struct SurveyRows {
+    unsigned long long f0;      // absolute index of the range's first owned frame
+    unsigned long long slot0;   // the slot of row 0
+    long stride;                // words from one row to the next (>= N + 1)
+    unsigned B;                 // frames per slot
+};
+
+// The body of k_scan and of k_waterfall: the hop loader, the staging, the transform of every frame up to x[r] as bins in natural
+// order and the sums are one text.  ROWS = false: the sums of all the workgroup's frames go into a.acc once, behind the loop
+// (rw is not looked at).  ROWS = true: they go into the current slot's row whenever a slot or the batch ends, and start over.
+// Inlined into its kernel, whose launch bound it runs under.  (`a` by value and the table staged behind the early return: in this
+// form the eight k_scan instantiations keep the registers tests/test_isa_scan.py pins; the arithmetic does not depend on either.)
+template <int FMT, bool LUTM, int N, bool ROWS>
+__device__ __forceinline__ void sc_frames(const SurveyArgs a, const WideConv& cv, const SurveyRows& rw)
 {
     static_assert(FMT == P25FE_FMT_U8 || !LUTM, "only u8 has a table");
     constexpr int R = sc_radix(N), P = sc_passes(N), T = N / R;
@@ -102,15 +117,15 @@ __global__ __launch_bounds__(SC_WG, 2) void k_scan(SurveyArgs a, WideConv cv)
     __shared__ float2 BUF[sc_pad(N)];                               // the transposes between passes
     const int tid = threadIdx.x;
     const float* lut = nullptr;
+    const long g0 = (long)blockIdx.x * a.F;                         // the workgroup's first frame
+    long nfl = a.n_frames - g0;
+    if (nfl <= 0) return;                                           // uniform (the host launches no such workgroup)
+    const int nf = (int)(nfl < (long)a.F ? nfl : (long)a.F);
     if constexpr (LUTM) {
         __shared__ float LUT[256];
         LUT[tid] = cv.lut[tid];
         lut = LUT;
     }
-    const long g0 = (long)blockIdx.x * a.F;                         // the workgroup's first frame
-    long nfl = a.n_frames - g0;
-    if (nfl <= 0) return;                                           // uniform (the host launches no such workgroup)
-    const int nf = (int)(nfl < (long)a.F ? nfl : (long)a.F);
     const int H = a.H, HV = H >> LS, NH = N / H;
     // the strip: position p is sample s0 + p (relative to owned sample 0); hop c covers positions [c H, c H + H)
     const long s0 = a.e0 + g0 * H - (N - 1);
@@ -185,6 +200,14 @@ __global__ __launch_bounds__(SC_WG, 2) void k_scan(SurveyArgs a, WideConv cv)
     unsigned long long sum[R];
 #pragma unroll
     for (int r = 0; r < R; ++r) sum[r] = 0ull;
+    // the slot of the workgroup's first frame (one 64-bit division), the frames it still lacks, its row and the frames summed
+    unsigned long long* row = a.acc;
+    unsigned left = 0u, held = 0u;
+    if constexpr (ROWS) {
+        const unsigned long long fa = rw.f0 + (unsigned long long)g0, slot = fa / rw.B;
+        left = rw.B - (unsigned)(fa - slot * rw.B);
+        row += (long)(slot - rw.slot0) * rw.stride;
+    }
 
     if constexpr (LUTM) __syncthreads();                            // the table before the first look-up
     for (int c = 0; c < NH; ++c) { load(c); stage(c); }             // frame 0's hops
@@ -242,10 +265,27 @@ __global__ __launch_bounds__(SC_WG, 2) void k_scan(SurveyArgs a, WideConv cv)
         }
 #pragma unroll
         for (int r = 0; r < R; ++r) sum[r] += sc_q(x[r], a.scale); // x[r] is bin tid + 256 r
-    }
+        if constexpr (ROWS) {
+            ++held;
+            if (--left == 0u || !more) {                            // uniform: the slot is complete, or the batch ends inside it
 #pragma unroll
-    for (int r = 0; r < R; ++r) atomicAdd(a.acc + tid + r * T, sum[r]);
-    if (tid == 0) atomicAdd(a.acc + N, (unsigned long long)nf);
+                for (int r = 0; r < R; ++r) { atomicAdd(row + tid + r * T, sum[r]); sum[r] = 0ull; }
+                if (tid == 0) atomicAdd(row + N, (unsigned long long)held);
+                row += rw.stride; left = rw.B; held = 0u;
+            }
+        }
+    }
+    if constexpr (!ROWS) {
+#pragma unroll
+        for (int r = 0; r < R; ++r) atomicAdd(a.acc + tid + r * T, sum[r]);
+        if (tid == 0) atomicAdd(a.acc + N, (unsigned long long)nf);
+    }
+}
+
+template <int FMT, bool LUTM, int N>
+__global__ __launch_bounds__(SC_WG, 2) void k_scan(SurveyArgs a, WideConv cv)
+{
+    sc_frames<FMT, LUTM, N, false>(a, cv, SurveyRows{});
 }
 
 }  // namespace p25k
@@ -262,22 +302,94 @@ struct p25fe_scanner {
     DevBuf d_acc, d_hist, d_in;
     uint64_t pos = 0;                      // samples consumed
     int fmt = -1;                          // format of the stream (-1: none yet)
+    // survey over time (3.0i, p25fe_waterfall.inc): the open rows [wf_rows][N + 1] of slots of wf_B frames from slot 0 (wf_B = 0: none)
+    DevBuf d_rows;
+    uint32_t wf_B = 0;
+    size_t wf_rows = 0;
 };
 
 namespace {
 
 constexpr double SC_PI = 3.14159265358979323846;
 inline bool sc_n_ok(int64_t N) { return N == 1024 || N == 4096; }
+inline bool finite_d(double v) { return v - v == 0.0; }
 inline bool sc_hop_ok(int64_t N, int64_t H) { return H >= 8 && H <= N && H % 8 == 0 && N % H == 0; }
 // frames a range owns: 3.0b's rule with L = 1, M = H
 inline size_t sc_n_frames(uint64_t H, uint64_t abs_first, size_t n) { return (size_t)((uint64_t)n / H + (abs_first % H + (uint64_t)n % H) / H); }
 inline size_t sc_lead(int N) { return round_up((size_t)N - 1, 8); }
+// frames per workgroup: the N / H - 1 hops in front of a batch are read again by its neighbour, so a batch is at least four
+// frame lengths; about a thousand workgroups fill the device twice over
+inline int sc_batch(int N, int H, size_t n_frames)
+{
+    return (int)std::min((size_t)1 << 20, std::max({(size_t)8, (size_t)(4 * (N / H)), (n_frames + 1023) / 1024}));
+}
+
+// the raster of p25fe_scan_channels and p25fe_waterfall_keys over N bins at fs: the eligible indices, and for each the bins (in
+// order of signed frequency) whose powers make pow[r] and those of its raster cell
+struct ScRaster {
+    struct Chan { int r; double fc; std::vector<uint32_t> in_bw, in_cell; };
+    std::vector<Chan> chan;
+    std::vector<double> fb;
+    int build(int32_t N, double fs, double raster_hz, double half_bw_hz)
+    {
+        const double rm = floor((fs / 2.0 - raster_hz / 2.0) / raster_hz);
+        if (rm < 0.0) return P25FE_OK;
+        if (rm > 1e6) return P25FE_ERR_ARG;
+        const int rmax = (int)rm;
+        fb.resize((size_t)N);
+        for (int b = 0; b < N; ++b) fb[(size_t)b] = (double)(b < N / 2 ? b : b - N) * fs / (double)N;
+        const double df = fs / (double)N, reach = std::max(half_bw_hz, raster_hz / 2.0);
+        for (int r = -rmax; r <= rmax; ++r) {
+            const double fc = (double)r * raster_hz;
+            if (fabs(fc) + raster_hz / 2.0 > fs / 2.0) continue;
+            Chan c; c.r = r; c.fc = fc;
+            const long k0 = (long)floor((fc - reach) / df) - 1, k1 = (long)ceil((fc + reach) / df) + 1;
+            for (long k = std::max(k0, -(long)(N / 2)); k <= std::min(k1, (long)(N / 2) - 1); ++k) {
+                const uint32_t b = (uint32_t)(k < 0 ? k + N : k);
+                const double d = fabs(fb[b] - fc);
+                if (d <= half_bw_hz) c.in_bw.push_back(b);
+                if (d <= raster_hz / 2.0) c.in_cell.push_back(b);
+            }
+            chan.push_back(std::move(c));
+        }
+        return P25FE_OK;
+    }
+};
 
 template <int FMT, bool LUTM>
 void sc_launch_as(int N, dim3 grid, hipStream_t st, const SurveyArgs& a, const WideConv& cv)
 {
     if (N == 4096) hipLaunchKernelGGL((k_scan<FMT, LUTM, 4096>), grid, dim3(SC_WG), 0, st, a, cv);
     else hipLaunchKernelGGL((k_scan<FMT, LUTM, 1024>), grid, dim3(SC_WG), 0, st, a, cv);
+}
+
+// The host streaming form of p25fe_scan and p25fe_waterfall: the format rule, the position, the carried history and the device
+// row are the object's and one text; where the call's frames go is `enqueue`(owned sample 0 on the device, format, n_hist, n),
+// which runs on the handle's stream at the object's position; `admit`() may refuse the call behind the argument and format checks,
+// before anything is copied or consumed
+template <class Admit, class Enqueue>
+int sc_stream(p25fe_scanner* sc, const void* iq, int fmt, size_t n, Admit admit, Enqueue enqueue)
+{
+    if (!sc || !sc->h || !wide_fmt_known(fmt) || (n && !iq)) return P25FE_ERR_ARG;
+    if (sc->fmt >= 0 && fmt != sc->fmt) return P25FE_ERR_FORMAT;
+    if (position_refused(sc->pos) || n >= P25FE_MAX_POSITION) return P25FE_ERR_ARG;
+    if (n == 0) return P25FE_OK;
+    if (int rc = admit()) return rc;
+    p25fe_t* h = sc->h;
+    const size_t bps = fmt_bytes(fmt), keep = (size_t)sc->N - 1, lead = sc_lead(sc->N);
+    const size_t n_hist = sc->pos < keep ? (size_t)sc->pos : keep;
+    // the device row: [the carried history, right-aligned in `lead` slots | n new samples], owned sample 0 16-byte aligned
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, sc->d_in.ensure((lead + round_up(n, 8)) * bps));
+    unsigned char* din = sc->d_in.as<unsigned char>();
+    HIPCHK(h, hipMemcpyAsync(din, sc->d_hist.p, lead * bps, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(din + lead * bps, iq, n * bps, hipMemcpyHostToDevice, h->stream));
+    if (int rc = enqueue(din + lead * bps, fmt, n_hist, n)) return rc;
+    // the carry moves: the last `lead` samples of [history | new]
+    HIPCHK(h, hipMemcpyAsync(sc->d_hist.p, din + n * bps, lead * bps, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));                     // the caller's buffer and the row are free again
+    sc->pos += n; sc->fmt = fmt;
+    return P25FE_OK;
 }
 
 }  // namespace
@@ -349,9 +461,7 @@ int p25fe_scan_dev(p25fe_scan_t* sc, const void* d_iq, int fmt, size_t n_hist, s
     a.e0 = (long)(H - 1 - (int)(abs_first % (uint64_t)H));
     a.n_frames = (long)n_frames;
     a.H = H;
-    // frames per workgroup: the N / H - 1 hops in front of a batch are read again by its neighbour, so a batch is at least four
-    // frame lengths; about a thousand workgroups fill the device twice over
-    a.F = (int)std::min((size_t)1 << 20, std::max({(size_t)8, (size_t)(4 * (N / H)), (n_frames + 1023) / 1024}));
+    a.F = sc_batch(N, H, n_frames);
     a.scale = ldexpf(1.0f, sc->shift);
     a.win = sc->d_win.as<float>(); a.tw = sc->d_tw.as<float2>();
     a.acc = reinterpret_cast<unsigned long long*>(d_acc);
@@ -371,25 +481,9 @@ int p25fe_scan_dev(p25fe_scan_t* sc, const void* d_iq, int fmt, size_t n_hist, s
 
 int p25fe_scan(p25fe_scan_t* sc, const void* iq, int fmt, size_t n)
 {
-    if (!sc || !sc->h || !wide_fmt_known(fmt) || (n && !iq)) return P25FE_ERR_ARG;
-    if (sc->fmt >= 0 && fmt != sc->fmt) return P25FE_ERR_FORMAT;
-    if (position_refused(sc->pos) || n >= P25FE_MAX_POSITION) return P25FE_ERR_ARG;
-    if (n == 0) return P25FE_OK;
-    p25fe_t* h = sc->h;
-    const size_t bps = fmt_bytes(fmt), keep = (size_t)sc->N - 1, lead = sc_lead(sc->N);
-    const size_t n_hist = sc->pos < keep ? (size_t)sc->pos : keep;
-    // the device row: [the carried history, right-aligned in `lead` slots | n new samples], owned sample 0 16-byte aligned
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, sc->d_in.ensure((lead + round_up(n, 8)) * bps));
-    unsigned char* din = sc->d_in.as<unsigned char>();
-    HIPCHK(h, hipMemcpyAsync(din, sc->d_hist.p, lead * bps, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(din + lead * bps, iq, n * bps, hipMemcpyHostToDevice, h->stream));
-    if (int rc = p25fe_scan_dev(sc, din + lead * bps, fmt, n_hist, n, sc->pos, sc->d_acc.as<uint64_t>(), h->stream)) return rc;
-    // the carry moves: the last `lead` samples of [history | new]
-    HIPCHK(h, hipMemcpyAsync(sc->d_hist.p, din + n * bps, lead * bps, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));                     // the caller's buffer and the row are free again
-    sc->pos += n; sc->fmt = fmt;
-    return P25FE_OK;
+    return sc_stream(sc, iq, fmt, n, [] { return P25FE_OK; }, [sc](const void* d_iq, int f, size_t n_hist, size_t cnt) {
+        return p25fe_scan_dev(sc, d_iq, f, n_hist, cnt, sc->pos, sc->d_acc.as<uint64_t>(), sc->h->stream);
+    });
 }
 
 int p25fe_scan_reset(p25fe_scan_t* sc)
@@ -399,6 +493,7 @@ int p25fe_scan_reset(p25fe_scan_t* sc)
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     HIPCHK(h, hipMemset(sc->d_acc.p, 0, ((size_t)sc->N + 1) * sizeof(uint64_t)));
+    if (sc->wf_B) HIPCHK(h, hipMemset(sc->d_rows.p, 0, sc->wf_rows * ((size_t)sc->N + 1) * sizeof(uint64_t)));
     sc->pos = 0; sc->fmt = -1;
     return P25FE_OK;
 }
@@ -419,35 +514,20 @@ int p25fe_scan_channels(const uint64_t* acc, int32_t N, uint32_t fs_hz, double r
                         p25fe_scan_chan_t* out, size_t cap, size_t* n_out)
 {
     if (n_out) *n_out = 0;
-    const auto finite_d = [](double v) { return v - v == 0.0; };
     if (!acc || !n_out || (cap && !out) || !sc_n_ok(N) || fs_hz == 0 || !finite_d(raster_hz) || !(raster_hz > 0.0) ||
         !finite_d(half_bw_hz) || half_bw_hz < 0.0 || !finite_d(thr_db)) return P25FE_ERR_ARG;
     if (acc[N] == 0) return P25FE_OK;                               // no frame: no channel
-    const double fs = (double)fs_hz;
-    const double rm = floor((fs / 2.0 - raster_hz / 2.0) / raster_hz);
-    if (rm < 0.0) return P25FE_OK;                                  // the raster is wider than the capture
-    if (rm > 1e6) return P25FE_ERR_ARG;
-    const int rmax = (int)rm;
-    std::vector<double> fb((size_t)N), pw((size_t)N);
-    for (int b = 0; b < N; ++b) { fb[(size_t)b] = (double)(b < N / 2 ? b : b - N) * fs / (double)N; pw[(size_t)b] = (double)acc[b]; }
+    ScRaster ra;
+    if (int rc = ra.build(N, (double)fs_hz, raster_hz, half_bw_hz)) return rc;   // (none eligible: the raster is wider than the capture)
     struct Cand { int r; double pow, off; };
     std::vector<Cand> cand;
     std::vector<double> pows;
-    const double df = fs / (double)N, reach = std::max(half_bw_hz, raster_hz / 2.0);
-    for (int r = -rmax; r <= rmax; ++r) {
-        const double fc = (double)r * raster_hz;
-        if (fabs(fc) + raster_hz / 2.0 > fs / 2.0) continue;
-        // bins near fc, in order of frequency: k is the bin's signed index
-        const long k0 = (long)floor((fc - reach) / df) - 1, k1 = (long)ceil((fc + reach) / df) + 1;
+    for (const ScRaster::Chan& c : ra.chan) {
         double p = 0.0, s = 0.0, sf = 0.0;
-        for (long k = std::max(k0, -(long)(N / 2)); k <= std::min(k1, (long)(N / 2) - 1); ++k) {
-            const size_t b = (size_t)(k < 0 ? k + N : k);
-            const double d = fabs(fb[b] - fc);
-            if (d <= half_bw_hz) p += pw[b];
-            if (d <= raster_hz / 2.0) { s += pw[b]; sf += pw[b] * fb[b]; }
-        }
+        for (uint32_t b : c.in_bw) p += (double)acc[b];
+        for (uint32_t b : c.in_cell) { const double v = (double)acc[b]; s += v; sf += v * ra.fb[b]; }
         pows.push_back(p);
-        cand.push_back(Cand{r, p, s > 0.0 ? sf / s - fc : 0.0});
+        cand.push_back(Cand{c.r, p, s > 0.0 ? sf / s - c.fc : 0.0});
     }
     if (cand.empty()) return P25FE_OK;
     std::vector<double> sorted(pows);

@@ -60,6 +60,7 @@
 // Wires DemodTask -> RecvTask exactly like src/main.rs:270-287, single-threaded through in-memory channels.
 #include <chrono>
 #include <cinttypes>
+#include <cmath>
 #include <condition_variable>
 #include <cstdarg>
 #include <cstring>
@@ -129,7 +130,8 @@ struct Sink {
 static int usage(const char* argv0)
 {
     std::fprintf(stderr, "usage: %s [-w BB.f32le] [-j EVENTS.jsonl] [-b CHUNKS] [-r RATE_HZ [-S MS] [-f OFFSET_HZ | -F OFFSET_HZ [-a MS | -A MS]]] u8|s16|cf32|bb <in> <dibits.out>\n"
-                         "       %s -W WINDOW_BYTES u8|s16|cf32 <in> <dibits.out>\n", argv0, argv0);
+                         "       %s -W WINDOW_BYTES u8|s16|cf32 <in> <dibits.out>\n"
+                         "       %s -r RATE_HZ -T MS u8|s16|cf32 <in> <unused>\n", argv0, argv0, argv0);
     return 2;
 }
 
@@ -150,14 +152,22 @@ struct Options {
     double afc_ms = 0.0;                                              // -a: measure the first MS ms at -F's offset, correct once
     double track_ms = 0.0;                                            // -A: the loop, updated at every multiple of MS ms of input
     double scan_ms = 0.0;                                             // -S: survey the first MS ms, print the active raster channels
+    double activity_ms = 0.0;                                         // -T: survey the whole input in slots of MS ms, print the keyed intervals
     bool bb = false;                                                  // the mode: 48 kHz baseband, or ...
     int fmt = 0; size_t bps = 0;                                      // ... IQ in this format (P25FE_FMT_*) of this many bytes per sample
 };
+
+// -T: frames of hop 2048 per slot of MS ms, at least one
+static uint64_t activity_slot_frames(const Options& o)
+{
+    return (uint64_t)std::max(1.0, std::floor(o.activity_ms * (double)o.rate_hz / 1000.0 / 2048.0 + 0.5));
+}
 
 // argv -> Options; false: a usage error (all of them are decided here, before anything is opened or created)
 static bool parse(int argc, char** argv, Options& o)
 {
     bool f = false, F = false;                                        // -f and -F exclude each other
+    bool b = false;                                                   // -b was given (-T takes no other option but -r)
     const auto number = [](const char* s, double& v) { char* end = nullptr; v = std::strtod(s, &end); return end != s && *end == '\0'; };
     int a = 1;
     for (; a < argc && argv[a][0] == '-' && argv[a][1] != '\0'; a += 2) {
@@ -166,13 +176,14 @@ static bool parse(int argc, char** argv, Options& o)
         const char* val = argv[a + 1];
         if (opt == "-w") o.wpath = val;
         else if (opt == "-j") o.jpath = val;
-        else if (opt == "-b") o.batch = (size_t)std::strtoull(val, nullptr, 10);
+        else if (opt == "-b") { o.batch = (size_t)std::strtoull(val, nullptr, 10); b = true; }
         else if (opt == "-r") { if ((o.rate_hz = std::strtoul(val, nullptr, 10)) == 0 || o.rate_hz > 0xfffffffful) return false; }
         else if (opt == "-f") { o.offset.hz = std::strtoll(val, nullptr, 10); f = true; }
         else if (opt == "-F") { if (!number(val, o.offset.nco_hz)) return false; F = true; }
         else if (opt == "-a") { if (!number(val, o.afc_ms) || !(o.afc_ms > 0.0) || o.afc_ms > 60000.0) return false; }
         else if (opt == "-A") { if (!number(val, o.track_ms) || !(o.track_ms > 0.0) || o.track_ms > 60000.0) return false; }
         else if (opt == "-S") { if (!number(val, o.scan_ms) || !(o.scan_ms > 0.0) || o.scan_ms > 60000.0) return false; }
+        else if (opt == "-T") { if (!number(val, o.activity_ms) || !(o.activity_ms > 0.0) || o.activity_ms > 60000.0) return false; }
         else if (opt == "-W") {
             char* end = nullptr;
             o.window_bytes = (size_t)std::strtoull(val, &end, 10);
@@ -183,6 +194,9 @@ static bool parse(int argc, char** argv, Options& o)
     if (argc - a != 3 || o.batch == 0 || (f && F) || ((f || F) && !o.rate_hz) || (o.afc_ms > 0.0 && !F)) return false;
     if (o.track_ms > 0.0 && (!F || o.afc_ms > 0.0)) return false;   // -A goes with -F and instead of -a
     if (o.scan_ms > 0.0 && !o.rate_hz) return false;                 // -S goes with -r
+    if (o.activity_ms > 0.0 && (!o.rate_hz || o.scan_ms > 0.0 || f || F || o.afc_ms > 0.0 || o.track_ms > 0.0 || o.wpath || o.jpath || b ||
+                                o.window_bytes)) return false;       // -T goes with -r and with nothing else
+    if (o.activity_ms > 0.0 && activity_slot_frames(o) > ((uint64_t)1 << 20)) return false;   // more frames a slot than the library takes
     o.offset.kind = F ? o.offset.NCO : (f ? o.offset.RATIONAL : o.offset.NONE);
     const std::string mode = argv[a];
     o.in_path = argv[a + 1]; o.out_path = argv[a + 2];
@@ -482,6 +496,57 @@ static std::string survey(Handle& h, const Options& o, std::ifstream& in)
     return line + "]}";
 }
 
+// -T MS: the survey over time (docs/SPEC.md 3.0i) of the whole input in slots of about MS ms (a whole number of frames of N = 4096 at
+// hop 2048, the designed window, shift 16; at most 65 536 slots, then "truncated") -> the {"event":"activity"} line with the keyed
+// intervals of the 12.5 kHz raster at 20 / 14 dB, at least two slots long, by first slot
+static std::string activity(Handle& h, const Options& o, std::ifstream& in)
+{
+    constexpr int32_t N = 4096, H = N / 2;
+    constexpr size_t MAX_SLOTS = 65536;
+    const uint32_t B = (uint32_t)activity_slot_frames(o);
+    p25fe_scan_t* made = nullptr;
+    expect(p25fe_scan_create(h.get(), N, H, nullptr, 16, &made), "unable to make the survey");
+    const std::unique_ptr<p25fe_scan_t, void (*)(p25fe_scan_t*)> sc(made, p25fe_scan_destroy);
+    expect(p25fe_waterfall_open(sc.get(), B, MAX_SLOTS), "unable to open the rows");
+    uint64_t left = (uint64_t)MAX_SLOTS * B * (uint64_t)H;           // samples whose frames all have a row
+    bool truncated = false;
+    for (std::vector<char> chunk;;) {
+        const size_t want = (size_t)std::min<uint64_t>(left, (uint64_t)1 << 22);
+        chunk.resize(std::max<size_t>(want, 1) * o.bps);
+        in.read(chunk.data(), (std::streamsize)chunk.size());
+        const size_t got = (size_t)in.gcount() / o.bps;
+        if (want == 0) { truncated = got != 0; break; }              // every row is in use: is there more input?
+        if (got) expect(p25fe_waterfall(sc.get(), chunk.data(), o.fmt, got), "unable to survey the capture");
+        left -= got;
+        if (got < want) break;
+    }
+    size_t n_rows = 0;
+    (void)p25fe_waterfall_read(sc.get(), nullptr, 0, &n_rows);       // (P25FE_ERR_CAPACITY with the count)
+    std::vector<uint64_t> rows(std::max<size_t>(n_rows, 1) * ((size_t)N + 1));
+    expect(p25fe_waterfall_read(sc.get(), rows.data(), n_rows, &n_rows), "unable to read the rows");
+    std::vector<p25fe_waterfall_key_t> key(256);
+    size_t n = 0;
+    for (int pass = 0; pass < 2; ++pass) {                            // (the count is whole even beyond the capacity: once more with room for all)
+        expect(p25fe_waterfall_keys(rows.data(), n_rows, (size_t)N + 1, N, (uint32_t)o.rate_hz, 0, 12500.0, 4000.0, 20.0, 14.0, 2, key.data(),
+                                    key.size(), &n), "unable to list the keyed intervals");
+        if (n <= key.size()) break;
+        key.resize(n);
+    }
+    const double slot_ms = (double)B * (double)H * 1000.0 / (double)o.rate_hz;
+    char buf[256];
+    std::snprintf(buf, sizeof buf, "{\"event\":\"activity\",\"slot_frames\":%u,\"slot_ms\":%.4f,\"n_slots\":%zu,%s\"keys\":[", B, slot_ms, n_rows,
+                  truncated ? "\"truncated\":true," : "");
+    std::string line = buf;
+    for (size_t i = 0; i < n; ++i) {
+        const double db = key[i].peak_db_over_floor < 999.0 ? key[i].peak_db_over_floor : 999.0;   // (JSON has no infinity)
+        std::snprintf(buf, sizeof buf, "%s{\"raster_index\":%d,\"centre_hz\":%.1f,\"offset_hz\":%.1f,\"first_ms\":%.3f,\"last_ms\":%.3f,\"db_over_floor\":%.2f}",
+                      i ? "," : "", key[i].raster_index, key[i].centre_hz, key[i].offset_hz, (double)key[i].first_slot * slot_ms,
+                      (double)(key[i].first_slot + key[i].n_slots) * slot_ms, db);
+        line += buf;
+    }
+    return line + "]}";
+}
+
 int main(int argc, char** argv)
 try {
     Options o;
@@ -490,6 +555,10 @@ try {
     if (!in) fail("unable to open %s\n", o.in_path);
     Handle h(0, 1);
     if (o.window_bytes) return bulk(h, o, in);
+    if (o.activity_ms > 0.0) {                                        // the survey over time alone: no output file
+        std::printf("%s\n", activity(h, o, in).c_str());
+        return 0;
+    }
     std::string scan_event;
     if (o.scan_ms > 0.0) {
         scan_event = survey(h, o, in);

@@ -6,6 +6,11 @@ the GPU (kernel k_scan), and the list of active raster channels formed from it o
     for ch in Scanner.channels(acc.cpu().numpy(), fs):         # strongest first
         step = Tuner.nco_step(fs, ch["centre_hz"] + ch["offset_hz"])
 
+and, with a time axis (3.0i: kernel k_waterfall, one launch for all slots), which raster channel was keyed from when to when:
+
+    rows = sc.waterfall_dev(capture, B=12)                     # int64 [n_slots, N + 1] on the device: one record per slot of B frames
+    for k in Scanner.keys(rows.cpu().numpy(), fs):             # by first slot: raster_index, first_slot, n_slots, offset_hz, ...
+
 torch supplies device memory and streams only; all arithmetic on the samples happens in libp25fe.so.
 """
 import ctypes as C
@@ -13,7 +18,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import FMT_CF32, FMT_U8, FMT_S16, SCAN_CHAN_DTYPE
+from ._lib import FMT_CF32, FMT_U8, FMT_S16, SCAN_CHAN_DTYPE, WATERFALL_KEY_DTYPE
 
 
 def _p(a):
@@ -50,6 +55,39 @@ class Scanner:
         out = np.zeros(max(want, 1), dtype=SCAN_CHAN_DTYPE)
         _lib.check(L_, None, L_.p25fe_scan_channels(_p(acc), N, int(fs_hz), float(raster_hz), float(half_bw_hz), float(thr_db),
                                                     _p(out), want, C.byref(n)))
+        got = out[:min(n.value, want)].copy()
+        return got if cap is None else (got, n.value)
+
+    @staticmethod
+    def slots(hop, B, abs0, n):
+        """the slots of B frames the frames of [abs0, abs0 + n) fall into -> (first_slot, n_slots); n_slots = 0 when the range owns
+        no frame (p25fe_waterfall_slots; needs no device)"""
+        L_ = _lib.load()
+        first, cnt = C.c_uint64(0), C.c_size_t(0)
+        _lib.check(L_, None, L_.p25fe_waterfall_slots(int(hop), int(B), int(abs0), int(n), C.byref(first), C.byref(cnt)))
+        return first.value, cnt.value
+
+    @staticmethod
+    def keys(rows, fs_hz, slot0=0, raster_hz=12500.0, half_bw_hz=4000.0, on_db=20.0, off_db=14.0, min_slots=2, cap=None, N=None):
+        """rows on the host (uint64 or int64 words [n_rows, row_stride]; N: row_stride - 1 unless given, the rest of a row is
+        padding) -> the keyed intervals by first slot, then raster index, as a structured array of WATERFALL_KEY_DTYPE
+        (p25fe_waterfall_keys; needs no device).  With cap the result is (keys, n_intervals)."""
+        L_ = _lib.load()
+        rows = np.ascontiguousarray(rows)
+        rows = rows.view(np.uint64) if rows.dtype == np.int64 else rows.astype(np.uint64, copy=False)
+        assert rows.ndim == 2
+        stride = rows.shape[1]
+        N = stride - 1 if N is None else int(N)
+        n = C.c_size_t(0)
+        want = 64 if cap is None else int(cap)
+        while True:
+            out = np.zeros(max(want, 1), dtype=WATERFALL_KEY_DTYPE)
+            _lib.check(L_, None, L_.p25fe_waterfall_keys(_p(rows), rows.shape[0], stride, N, int(fs_hz), int(slot0), float(raster_hz),
+                                                         float(half_bw_hz), float(on_db), float(off_db), int(min_slots), _p(out),
+                                                         want, C.byref(n)))
+            if cap is not None or n.value <= want:
+                break
+            want = n.value
         got = out[:min(n.value, want)].copy()
         return got if cap is None else (got, n.value)
 
@@ -97,6 +135,12 @@ class Scanner:
     def scan(self, iq):
         """host streaming form: the capture's next samples (complex64 [n], int16 or uint8 interleaved pairs [2 n]) are added to the
         object's own record; the object keeps the history and the position between calls"""
+        iq, fmt, n = self._host_samples(iq)
+        _lib.check(self.lib, self.fe.h, self.lib.p25fe_scan(self.sc, _p(iq), fmt, n))
+
+    @staticmethod
+    def _host_samples(iq):
+        """complex64 [n], int16 or uint8 interleaved pairs [2 n] -> (contiguous flat array, format, n)"""
         iq = np.asarray(iq)
         if iq.dtype == np.uint8:
             fmt = FMT_U8
@@ -105,11 +149,59 @@ class Scanner:
         else:
             fmt, iq = FMT_CF32, iq.astype(np.complex64, copy=False)
         iq = np.ascontiguousarray(iq).reshape(-1)
-        n = iq.size if fmt == FMT_CF32 else iq.size // 2
-        _lib.check(self.lib, self.fe.h, self.lib.p25fe_scan(self.sc, _p(iq), fmt, n))
+        return iq, fmt, iq.size if fmt == FMT_CF32 else iq.size // 2
 
     def read(self, clear=False):
         """waits for the device and returns the object's record, uint64 [N + 1] (word N: the frames); clear zeroes it afterwards"""
         acc = np.empty(self.N + 1, dtype=np.uint64)
         _lib.check(self.lib, self.fe.h, self.lib.p25fe_scan_read(self.sc, _p(acc), 1 if clear else 0))
         return acc
+
+    def waterfall_dev(self, iq, B, n_hist=0, abs0=0, offset=0, n=None, rows=None, slot0=None):
+        """scan_dev with a time axis: the frames of the range go into one row per slot of B frames, int64 [n_rows, N + 1] on the
+        device, in ONE launch.  ADDS into `rows` ([n_rows, >= N + 1], row 0 standing for slot `slot0`; None: zeroed rows for
+        exactly the slots the range touches, slot0 None: its first slot).  abs0 matters in full: frame f belongs to slot f // B."""
+        import torch
+        from .frontend import _torch_fmt, fmt_bytes
+        assert iq.is_cuda and iq.dim() == 2 and iq.shape[1] == 2 and iq.is_contiguous()
+        fmt = _torch_fmt(iq.dtype)
+        if n is None:
+            n = iq.shape[0] - offset
+        assert 0 <= n <= iq.shape[0] - offset and 0 <= n_hist <= offset
+        if rows is None or slot0 is None:
+            first, cnt = self.slots(self.hop, B, abs0, n)
+            if slot0 is None:
+                slot0 = first
+            if rows is None:
+                rows = torch.zeros((first + cnt - slot0 if first + cnt > slot0 else 0, self.N + 1), dtype=torch.int64, device=iq.device)
+        assert rows.is_cuda and rows.dtype == torch.int64 and rows.dim() == 2 and rows.stride(1) == 1
+        if rows.shape[0] == 0:                                       # no row has no address: nothing to call with
+            if self.slots(self.hop, B, abs0, n)[1]:
+                raise _lib.P25feError(_lib.ERR_ARG, "the range owns a frame and there is no row")
+            return rows
+        ptr, stride = C.c_void_p(rows.data_ptr()), rows.stride(0) if rows.shape[0] > 1 else rows.shape[1]
+        _lib.check(self.lib, self.fe.h,
+                   self.lib.p25fe_waterfall_dev(self.sc, C.c_void_p(iq.data_ptr() + fmt_bytes(fmt) * offset), fmt, n_hist, n, abs0,
+                                                int(B), int(slot0), ptr, rows.shape[0], stride, self.fe._stream()))
+        return rows
+
+    def open_waterfall(self, B, max_rows):
+        """the host streaming form gets rows: [max_rows, N + 1] zeroed on the device, for slots of B frames from slot 0"""
+        _lib.check(self.lib, self.fe.h, self.lib.p25fe_waterfall_open(self.sc, int(B), int(max_rows)))
+
+    def waterfall(self, iq):
+        """host streaming form, as scan(): the capture's next samples go into the open rows; may be mixed with scan() on one
+        stream, each call's frames going where that call sends them"""
+        iq, fmt, n = self._host_samples(iq)
+        _lib.check(self.lib, self.fe.h, self.lib.p25fe_waterfall(self.sc, _p(iq), fmt, n))
+
+    def read_waterfall(self):
+        """waits for the device and returns the rows touched so far, uint64 [ceil(frames / B), N + 1]"""
+        n = C.c_size_t(0)
+        rc = self.lib.p25fe_waterfall_read(self.sc, None, 0, C.byref(n))
+        if rc != _lib.ERR_CAPACITY:
+            _lib.check(self.lib, self.fe.h, rc)
+        rows = np.zeros((n.value, self.N + 1), dtype=np.uint64)
+        if n.value:
+            _lib.check(self.lib, self.fe.h, self.lib.p25fe_waterfall_read(self.sc, _p(rows), n.value, C.byref(n)))
+        return rows
