@@ -134,16 +134,16 @@ SAT_N, SAT_HOP, SAT_SHIFT, SAT_BIN, SAT_GAIN = 1024, 256, 40, 100, 8.0
 _SAT = {}
 
 
-def saturating_capture():
-    """0.75 e^{2 pi i 100 t / N} plus noise of sigma 0.01 per component (default_rng(77)), 4 N + 16 samples, made once ->
-    {format: raw samples}: bin 100's power times 2^40 passes 2^62 in every frame with full history"""
-    if not _SAT:
-        n = 4 * SAT_N + 16
+def saturating_capture(n=None):
+    """0.75 e^{2 pi i 100 t / N} plus noise of sigma 0.01 per component (default_rng(77)), n samples (None: 4 N + 16), made once per
+    length -> {format: raw samples}: bin 100's power times 2^40 passes 2^62 in every frame with full history"""
+    n = 4 * SAT_N + 16 if n is None else int(n)
+    if n not in _SAT:
         t = np.arange(n, dtype=np.float64)
         g = np.random.default_rng(77).standard_normal((n, 2))
         x = (0.75 * np.exp(2j * np.pi * SAT_BIN * t / SAT_N) + 0.01 * (g[:, 0] + 1j * g[:, 1])).astype(np.complex64)
-        _SAT.update({"cf32": x, "s16": to_s16(x), "u8": to_u8(x)})
-    return _SAT
+        _SAT[n] = {"cf32": x, "s16": to_s16(x), "u8": to_u8(x)}
+    return _SAT[n]
 
 
 def saturating_window():

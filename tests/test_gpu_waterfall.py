@@ -6,6 +6,7 @@ bit: B = 1 rows against the per-frame records, slots whose boundaries fall at ev
 slot too), the wrapping sum of the rows against p25fe_scan_dev's record, positions past 2^40, rows that keep their padding and
 their neighbours, about a thousand workgroups, the host streaming form mixed with p25fe_scan, and the keyed scene.  The only
 tolerance is 3.0h's per-frame bound (test 1).  Shapes and captures are tests/test_gpu_scan_edges.py's.
+Every B here is below the batch F; slots spanning workgroups, the u8 table, two streams, wrapping rows: test_gpu_waterfall_edges.py.
 
 Largest error observed on an MI355X as a fraction of the per-frame bound: see docs/MEASUREMENTS.md, "Survey over time"."""
 import ctypes as C

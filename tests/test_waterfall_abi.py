@@ -154,6 +154,28 @@ def test_slots_are_the_formula(lib):
     assert some_empty >= 4 and Scanner.slots(2048, 6, (1 << 40) + 5, 100000) == (((1 << 40) + 5) // 2048 // 6, 9)
 
 
+def test_the_models_batches_and_contributors():
+    """what tests/test_gpu_waterfall_edges.py's premises are asserted with: WM.batch at the shapes that file launches (and at
+    the formula's three regimes), WM.contributors on cases counted by hand"""
+    for N, hop, frames, F in ((1024, 512, 70, 8), (1024, 256, 70, 16), (4096, 1024, 70, 16), (4096, 2048, 40, 8), (1024, 512, 9221, 10)):
+        assert WM.batch(N, hop, frames) == F, (N, hop, frames)
+    assert WM.batch(1024, 8, 9230) == 512 and WM.batch(1024, 64, 70) == 64 and WM.batch(4096, 4096, 1) == 8
+    assert WM.batch(1024, 512, 8 * 1024) == 8 and WM.batch(1024, 512, 8 * 1024 + 1) == 9
+    assert WM.batch(1024, 1024, (1 << 30) + 1) == 1 << 20
+    # frames 5 .. 14 in batches of 4 (workgroup 0: 5 .. 8, 1: 9 .. 12, 2: 13, 14), slots of 3 (slot 1: 5; 2: 6 .. 8; 3: 9 .. 11;
+    # 4: 12 .. 14)
+    assert WM.contributors(5, 10, 4, 3) == [{0}, {0}, {1}, {1, 2}]
+    # frames 6 .. 14 in batches of 2 (6 7 | 8 9 | 10 11 | 12 13 | 14), slots of 6 (slot 1: 6 .. 11; 2: 12 .. 14)
+    assert WM.contributors(6, 9, 2, 6) == [{0, 1, 2}, {3, 4}]
+    # frames 7 .. 11 in batches of 4 (7 .. 10 | 11), slots of 4 (slot 1: 7; 2: 8 .. 11): both workgroups meet in the second row
+    assert WM.contributors(7, 5, 4, 4) == [{0}, {0, 1}]
+    assert WM.contributors(3, 4, 8, 1 << 20) == [{0}] and WM.contributors(3, 0, 8, 5) == []
+    for fa, k, F, B in ((5, 10, 4, 3), (6, 9, 2, 6), (0, 70, 8, 29), ((1 << 40) + 3, 70, 16, 17)):
+        con = WM.contributors(fa, k, F, B)
+        assert len(con) == WM.group(np.zeros((k, 2)), fa, B)[1].shape[0] == WM.slots(1, B, fa, k)[1]
+        assert set().union(*con) == set(range(-(-k // F)))
+
+
 def _quiet(n_rows, N=1024, frames=6):
     """rows of a flat floor: every bin 100 per frame"""
     rows = np.full((n_rows, N + 1), 100 * frames, dtype=np.uint64)

@@ -29,6 +29,22 @@ def group(frames, f0, B):
     return slot0, rows
 
 
+def batch(N, hop, n_frames):
+    """F, the consecutive frames one workgroup of a launch over n_frames frames takes: sc_batch of
+    p25rx_amd/csrc/p25fe_scan.inc, min(2^20, max(8, 4 N / H, ceil(n_frames / 1024)))"""
+    return min(1 << 20, max(8, 4 * (N // hop), -(-n_frames // 1024)))
+
+
+def contributors(fa, k, F, B):
+    """a launch over the frames fa .. fa + k - 1 in batches of F: per row (row i: slot fa // B + i), the set of workgroup indices
+    (f - fa) // F whose frames land in it -> [set] of the length group() gives the rows"""
+    slot0 = fa // B
+    out = [set() for _ in range(((fa + k - 1) // B - slot0 + 1) if k else 0)]
+    for f in range(fa, fa + k):
+        out[f // B - slot0].add((f - fa) // F)
+    return out
+
+
 def rows(x, N, hop, w, shift, B, first=0, n=None, n_hist=None):
     """the rows of one range of the stream x (converted samples, from position 0) -> (slot0, uint64 [n_slots, N + 1])"""
     X = SM.spectra(x, N, hop, w, first, n, n_hist)
