@@ -229,6 +229,17 @@ pub struct WaterfallKey {
     pub offset_hz: f64,
     pub peak_db_over_floor: f64,
 }
+/// p25fe_cut_t: one cut of a capture, docs/SPEC.md 3.0j (24 bytes)
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq)]
+pub struct Cut {
+    pub abs_first: u64,
+    pub n: u64,
+    pub step: i32,
+    pub ph0: u32,
+}
+pub const CUTS_MAX: usize = 4096;
+pub enum Cuts {}
 /// P25FE_TUNE_MAX_CH / _DEN: 1 <= channels <= 256; num / den in lowest terms, 1 <= den <= 8192, 2 |num| <= den
 pub const TUNE_MAX_CH: i32 = 256;
 pub const TUNE_MAX_DEN: i32 = 8192;
@@ -344,6 +355,13 @@ extern "C" {
     pub fn p25fe_waterfall_keys(rows: *const u64, n_rows: usize, row_stride: usize, n: i32, fs_hz: u32, slot0: u64, raster_hz: f64,
                                 half_bw_hz: f64, on_db: f64, off_db: f64, min_slots: u32, out: *mut WaterfallKey, cap: usize,
                                 n_out: *mut usize) -> c_int;
+    pub fn p25fe_cuts_from_keys(keys: *const WaterfallKey, n_keys: usize, n: i32, hop: i32, b: u32, fs_hz: u32, margin: u64,
+                                range_first: u64, range_n: u64, out: *mut Cut, cap: usize, n_out: *mut usize) -> c_int;
+    pub fn p25fe_cuts_create(tn: *mut Tuner, cuts: *const Cut, n_cuts: usize, counts_out: *mut usize, max_count: *mut usize,
+                             out: *mut *mut Cuts) -> c_int;
+    pub fn p25fe_cuts_destroy(ct: *mut Cuts);
+    pub fn p25fe_cuts_dev(ct: *mut Cuts, d_iq: *const c_void, fmt: c_int, n_hist: usize, n: usize, abs_first: u64,
+                          d_out: *mut f32, out_stride: usize, stream: *mut c_void) -> c_int;
     pub fn p25fe_n_baseband(abs0: u64, n: usize) -> usize;
     pub fn p25fe_slice_dev(h: *mut Handle, d_bb: *const f32, bb_stride: usize, n_hist_bb: usize, n_bb: usize, abs_bb0: u64,
                            d_anchor_in: *const Anchor, d_dibits: *mut u8, dibit_stride: usize, d_sync_pos: *mut i64,

@@ -735,6 +735,48 @@ int p25fe_waterfall_keys(const uint64_t *rows, size_t n_rows, size_t row_stride,
                          double raster_hz, double half_bw_hz, double on_db, double off_db, uint32_t min_slots,
                          p25fe_waterfall_key_t *out, size_t cap, size_t *n_out);
 
+/* ---- tuner, cuts: keyed intervals cut out of one capture in a single launch (docs/SPEC.md 3.0j) -------------------------------------
+ * A cut {abs_first, n, step, ph0} owns the absolute input samples [abs_first, abs_first + n); (step, ph0) is an NCO channel's pair
+ * (3.0d / 3.0e).  Its output is, bit for bit, the slice [m0, m0 + cnt) of the row p25fe_tune_dev writes for an NCO channel with that
+ * (step, ph0) over the call's whole range: m0 = p25fe_n_resample(L, M, call.abs_first, cut.abs_first - call.abs_first), cnt =
+ * p25fe_n_resample(L, M, cut.abs_first, cut.n).  A cut that begins inside the call's range therefore reads the real samples in front
+ * of it (what lies before the call's -n_hist reads as zero), the mixer's phase is a function of the absolute index alone, and
+ * splitting a cut at any sample -- within a call, or across two calls of a stream, the second with n_hist >= T - 1 -- gives the same
+ * concatenated outputs.  A cut with step = 0 and ph0 = 0 is p25fe_resample_dev's slice; a cut with cnt = 0 writes nothing. */
+#define P25FE_CUTS_MAX 4096
+typedef struct p25fe_cut {
+    uint64_t abs_first, n;   /* the samples the cut owns; both < 2^62 */
+    int32_t step;            /* the NCO's step (p25fe_nco_step) ... */
+    uint32_t ph0;            /* ... and phase offset (3.0e; 0 for a channel tuned from the start of the stream) */
+} p25fe_cut_t;               /* 24 bytes */
+typedef struct p25fe_cuts p25fe_cuts_t;
+
+/* keys -> cuts, host only: cut j is key j (p25fe_waterfall_keys' output for a survey of N, hop, B at fs_hz).  Frame f of the survey
+ * spans samples [f hop + hop - N, f hop + hop - 1], so key j owns [first_slot B hop + hop - N - margin, (first_slot + n_slots) B hop
+ * + hop - 1 + margin], clipped to [range_first, range_first + range_n) (empty after clipping: n = 0, abs_first at the range's nearer
+ * end); step = p25fe_nco_step(fs_hz, centre_hz + offset_hz), ph0 = 0.  *n_out = n_keys.  P25FE_ERR_ARG: a null n_out, null keys with
+ * n_keys > 0, null out with cap > 0, N neither 1024 nor 4096, hop not a multiple of 8 from 8 to N that divides N, B = 0 or B > 2^20,
+ * fs_hz = 0, margin, range_first or range_n >= 2^62, a key whose frequency p25fe_nco_step refuses (past Nyquist, not finite).
+ * P25FE_ERR_CAPACITY: cap < n_keys (*n_out is set, nothing written). */
+int p25fe_cuts_from_keys(const p25fe_waterfall_key_t *keys, size_t n_keys, int32_t N, int32_t hop, uint32_t B, uint32_t fs_hz,
+                         uint64_t margin, uint64_t range_first, uint64_t range_n, p25fe_cut_t *out, size_t cap, size_t *n_out);
+/* Checks, plans and uploads a list of cuts (synchronous).  tn must be an NCO tuner: its table, rotator, device and u8 conversion are
+ * used, its own channels are not.  counts_out (nullable) [n_cuts] = cnt_j; *max_count (nullable) = their maximum.  tn must outlive
+ * every USE of the object (p25fe_cuts_destroy alone is safe after the tuner is gone).  Every argument is checked before any device is
+ * touched.  P25FE_ERR_ARG: a null out or cuts, n_cuts = 0 or > P25FE_CUTS_MAX, a cut with abs_first or n >= 2^62, a null or rational
+ * tuner, more than 2^31 - 1 workgroups in total. */
+int p25fe_cuts_create(p25fe_tuner_t *tn, const p25fe_cut_t *cuts, size_t n_cuts, size_t *counts_out, size_t *max_count,
+                      p25fe_cuts_t **out);
+void p25fe_cuts_destroy(p25fe_cuts_t *ct);
+/* p25fe_tune_dev's conventions for d_iq / fmt / n_hist / n / abs_first / stream.  Writes exactly cnt_j cf32 samples to d_out + j *
+ * out_stride (complex samples) and nothing else; ONE launch; synchronises nothing.  The rows have different lengths and
+ * p25fe_run_dev on an n_cuts-channel handle needs rows of one length: nothing is written beyond cnt_j, so ZERO d_out first and run
+ * the rows at max_count -- a zero tail demodulates to zero baseband.  Give d_out 16-byte alignment and an even out_stride for that.
+ * P25FE_ERR_ARG (before any device is touched, nothing enqueued): p25fe_tune_dev's refusals, a cut not inside [abs_first, abs_first +
+ * n), out_stride < max_count (or >= 2^50). */
+int p25fe_cuts_dev(p25fe_cuts_t *ct, const void *d_iq, int fmt, size_t n_hist, size_t n, uint64_t abs_first,
+                   float *d_out, size_t out_stride, void *stream);
+
 /* stages 6-7 on device baseband.  d_bb points at the first owned sample; n_hist_bb valid
  * samples precede it; abs_bb0 is its absolute index; d_anchor_in (nullable = no lock) is the
  * carry-in per channel.  d_result[c] is filled per channel.

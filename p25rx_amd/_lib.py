@@ -79,6 +79,9 @@ assert SCAN_CHAN_DTYPE.itemsize == 32
 WATERFALL_KEY_DTYPE = np.dtype([("raster_index", "<i4"), ("reserved", "<i4"), ("first_slot", "<u8"), ("n_slots", "<u8"),
                                 ("centre_hz", "<f8"), ("offset_hz", "<f8"), ("peak_db_over_floor", "<f8")])   # p25fe_waterfall_key_t
 assert WATERFALL_KEY_DTYPE.itemsize == 48
+CUT_DTYPE = np.dtype([("abs_first", "<u8"), ("n", "<u8"), ("step", "<i4"), ("ph0", "<u4")])   # p25fe_cut_t
+assert CUT_DTYPE.itemsize == 24
+CUTS_MAX = 4096
 
 # every symbol include/p25fe.h declares (tests check the library exports exactly these)
 SYMBOLS = [
@@ -107,6 +110,7 @@ SYMBOLS = [
     "p25fe_scan_channels",
     "p25fe_waterfall_slots", "p25fe_waterfall_dev", "p25fe_waterfall_open", "p25fe_waterfall", "p25fe_waterfall_read",
     "p25fe_waterfall_keys",
+    "p25fe_cuts_from_keys", "p25fe_cuts_create", "p25fe_cuts_destroy", "p25fe_cuts_dev",
     "p25fe_debug_planes_size", "p25fe_debug_planes_dev",
 ]
 
@@ -260,6 +264,11 @@ def load():
     L.p25fe_waterfall_read.argtypes = [vp, vp, sz, psz]
     L.p25fe_waterfall_keys.argtypes = [vp, sz, sz, C.c_int32, C.c_uint32, u64, C.c_double, C.c_double, C.c_double, C.c_double,
                                        C.c_uint32, vp, sz, psz]
+    L.p25fe_cuts_from_keys.argtypes = [vp, sz, C.c_int32, C.c_int32, C.c_uint32, C.c_uint32, u64, u64, u64, vp, sz, psz]
+    L.p25fe_cuts_create.argtypes = [vp, vp, sz, vp, psz, C.POINTER(vp)]
+    L.p25fe_cuts_destroy.argtypes = [vp]
+    L.p25fe_cuts_destroy.restype = None
+    L.p25fe_cuts_dev.argtypes = [vp, vp, C.c_int, sz, sz, u64, vp, sz, vp]
     L.p25fe_n_predecim.argtypes = [u64, sz]
     L.p25fe_n_predecim.restype = sz
     L.p25fe_n_baseband.argtypes = [u64, sz]

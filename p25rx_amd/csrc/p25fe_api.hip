@@ -3267,3 +3267,4 @@ P25FE_M_API_EXTRAS
 
 #include "p25fe_scan.inc"       // survey (SPEC 3.0h): k_scan and its entry points
 #include "p25fe_waterfall.inc"  // survey over time (SPEC 3.0i): k_waterfall and its entry points
+#include "p25fe_cuts.inc"       // tuner, cuts (SPEC 3.0j): the entry points of k_tune_cuts

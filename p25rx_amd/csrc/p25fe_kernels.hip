@@ -1864,7 +1864,8 @@ struct RsArgs {
 // ------------------------------------------------------------------------------------------
 constexpr int TN_ROT_LDS_DEN = 512;          // largest denominator whose rotator goes to LDS (8 bytes per entry: 4 KB)
 constexpr int TN_NCO_DEN = 256;              // the NCO's coarse table: 2^32 / 256 = 2^24 phase units per entry
-constexpr int MIX_NONE = 0, MIX_RATIONAL = 1, MIX_NCO = 2;
+constexpr int MIX_NONE = 0, MIX_RATIONAL = 1, MIX_NCO = 2, MIX_CUTS = 3;
+constexpr bool mix_is_nco(int mix) { return mix == MIX_NCO || mix == MIX_CUTS; }   // the NCO mixer: a tuner's channels, or cuts
 
 struct TuneCh {
     const float2* rot;      // (C_D[i], S_D[i]), i < D, device
@@ -1880,6 +1881,29 @@ struct TuneArgs {
     int K;
     int rot_off;            // floats from the start of dynamic LDS to the rotator's copy (even)
     unsigned long abs_first;// position of owned sample 0 (< 2^62)
+};
+// Cuts (SPEC 3.0j, k_tune_cuts): J pieces of ONE capture in one launch, each the slice of the row k_tune_nco writes for an NCO channel
+// (step, ph0) over the call's whole range.  It is the NCO body entered differently: grid.x counts the workgroups of all cuts, cut j
+// owning [first_wg[j], first_wg[j + 1]) (an exclusive prefix the host builds; a cut without outputs owns none), and a workgroup
+// finds its cut by a uniform binary search.  The cut's record replaces what differs from the call -- (p0, d0) of ITS first owned
+// output, its output count, its (step, ph0) --; x, n_hist, n_new, the tables and abs_first stay the call's, so the loader's clamping,
+// the zeroing of missing history and the phase product are the tuner's code, unchanged.  The record is uploaded once, when the cuts
+// are made, so it holds nothing of a call: d0 is relative to the CUT's first sample, and the workgroup adds the cut's offset into
+// the call's buffer, cut.abs_first - call.abs_first, in 64 bits (it does not fit RsArgs::d0's int); row j starts j * y_stride
+// samples into y.
+struct CutRec {
+    unsigned long abs_first;// position of the cut's first sample (< 2^62)
+    long n_out;             // outputs of the cut (> 0 for every cut a workgroup can find)
+    int p0, d0;             // the cut's owned output 0: phase, and input index relative to the cut's first sample
+    int step;
+    unsigned ph0;
+};
+static_assert(sizeof(CutRec) == 32, "the record is 32 bytes");
+struct CutArgs {
+    const CutRec* rec;      // [J]
+    const int* first_wg;    // [J + 1], non-decreasing, first_wg[0] = 0, first_wg[J] = grid.x
+    const float2* rot;      // the tuner's ONE rotator table
+    int J;
 };
 
 // The NCO's factor (c, s) = e^{+j 2 pi ph / 2^32} to fp32 (SPEC 3.0d): ROT is the rotator of TN_NCO_DEN as (cos, sin) pairs
@@ -1958,9 +1982,9 @@ __device__ __forceinline__ void rs_fir(const float2* const (&xp)[RS_R], const fl
     }
 }
 
-// ta: the tuner's arguments (a is ta->r) when MIX, unused otherwise
+// ta: the tuner's arguments (a is ta->r) when MIX, unused otherwise; ca: the cuts when MIX_CUTS
 template <int FMT, bool LUTM, int MIX>
-__device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* ta, const WideConv& cv)
+__device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* ta, const WideConv& cv, const CutArgs* ca = nullptr)
 {
     static_assert(FMT == P25FE_FMT_U8 || !LUTM, "only u8 has a table");
     constexpr int LS = wide_log_spv(FMT), SPV = 1 << LS, NV = wide_nv(FMT, RS_NIN);
@@ -1974,7 +1998,24 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
     unsigned row = blockIdx.y;                                      // the resampler's channel: input row and output row
     const uint4* xb;
     TuneCh c{};
-    if constexpr (MIX != MIX_NONE) {
+    // owned output 0 and the output count: the call's, or the cut's
+    int p0 = a.p0;
+    long d0 = a.d0, n_out = a.n_out;
+    float2* yb;
+    if constexpr (MIX == MIX_CUTS) {
+        // the cut whose workgroups hold this one: first_wg[lo] <= blockIdx.x < first_wg[hi] throughout (uniform; scalar loads)
+        int lo = 0, hi = ca->J;
+        while (hi - lo > 1) {
+            const int mid = (int)(((unsigned)lo + (unsigned)hi) >> 1);
+            if (ca->first_wg[mid] <= (int)blockIdx.x) lo = mid; else hi = mid;
+        }
+        const CutRec q = ca->rec[lo];
+        wg = (long)((int)blockIdx.x - ca->first_wg[lo]);
+        p0 = q.p0; d0 = (long)q.d0 + (long)(q.abs_first - ta->abs_first); n_out = q.n_out;
+        c.rot = ca->rot; c.ph0 = q.ph0; c.step = q.step;
+        xb = reinterpret_cast<const uint4*>(a.x);
+        yb = reinterpret_cast<float2*>(a.y) + (size_t)lo * a.y_stride;
+    } else if constexpr (MIX != MIX_NONE) {
         row = blockIdx.x % (unsigned)ta->K;                         // the tuner's channel varies fastest; every channel reads the one input row
         wg = (long)blockIdx.y * (gridDim.x / (unsigned)ta->K) + blockIdx.x / (unsigned)ta->K;
         c = ta->ch[row];
@@ -1982,11 +2023,11 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
     } else {
         xb = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(a.x) + (size_t)fmt_bps(FMT) * row * a.ch_stride);
     }
-    float2* yb = reinterpret_cast<float2*>(a.y) + (size_t)row * a.y_stride;
+    if constexpr (MIX != MIX_CUTS) yb = reinterpret_cast<float2*>(a.y) + (size_t)row * a.y_stride;
     // D: the denominator (MIX_RATIONAL only); inc: what a sample adds to the rotator's index (num mod D) or to the phase (step)
     unsigned D = 0, inc = 0, ph0 = 0;
     if constexpr (MIX == MIX_RATIONAL) { D = (unsigned)c.D; inc = (unsigned)c.nm; }
-    if constexpr (MIX == MIX_NCO) { ph0 = c.ph0; inc = (unsigned)c.step; }
+    if constexpr (mix_is_nco(MIX)) { ph0 = c.ph0; inc = (unsigned)c.step; }
     const float* lut = nullptr;
     if constexpr (LUTM) {
         __shared__ float LUT[256];
@@ -2003,7 +2044,7 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
             for (unsigned k = tid; k < D; k += WV) rot[k] = c.rot[k];
         ROT = rot;
     }
-    if constexpr (MIX == MIX_NCO) {
+    if constexpr (mix_is_nco(MIX)) {
         float2* const rot = reinterpret_cast<float2*>(RS_HT + ta->rot_off);
         mode = (inc | ph0) == 0 ? 0 : 3;
         if (mode == 3)
@@ -2014,9 +2055,9 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
 
     const long m_wg0 = wg * ((long)a.tile * RS_SUBS);
     if constexpr (MIX != MIX_NONE)
-        if (m_wg0 >= a.n_out) return;                               // (a last row of grid.y may be partial)
-    const long u_wg = (long)a.p0 + m_wg0 * M;
-    long nt = (long)a.d0 + u_wg / L;                                // input index of the sub-tile's first output
+        if (m_wg0 >= n_out) return;                                 // (a last row of grid.y may be partial)
+    const long u_wg = (long)p0 + m_wg0 * M;
+    long nt = d0 + u_wg / L;                                        // input index of the sub-tile's first output
     int pt = (int)(u_wg % L);                                       // ... and its phase
     unsigned rb = 0, il = 0, sv = 0;
     if constexpr (MIX == MIX_RATIONAL) {
@@ -2026,7 +2067,7 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
         il = (inc * (unsigned)(SPV * tid)) % D;                     // this lane's index offset inside a vector row
         sv = (inc * (unsigned)(SPV * WV)) % D;                      // ... and from one of its vectors to the next
     }
-    if constexpr (MIX == MIX_NCO) {
+    if constexpr (mix_is_nco(MIX)) {
         // rb is the PHASE of the window's first sample, ph0 + step * position mod 2^32: the one product; it follows the window by adds
         rb = ph0 + inc * (unsigned)((long)ta->abs_first + (nt - (T - 1)));
         il = inc * (unsigned)(SPV * tid);
@@ -2053,7 +2094,7 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
     // MODE: 0 no product (the resampler, and a channel at the capture's centre) / 1 rotator in LDS / 2 rotator gathered / 3 NCO
     auto stage = [&](long base, auto mc) {
         constexpr int MODE = decltype(mc)::value;
-        static_assert(MODE == 0 || (MIX == MIX_RATIONAL && MODE <= 2) || (MIX == MIX_NCO && MODE == 3),
+        static_assert(MODE == 0 || (MIX == MIX_RATIONAL && MODE <= 2) || (mix_is_nco(MIX) && MODE == 3),
                       "only the tuner mixes");
         const long v0 = base >> LS;
         const int sh = (int)(base - (v0 << LS));                    // 0 .. SPV - 1
@@ -2108,7 +2149,7 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
             for (int r = 0; r < RS_R; ++r) {
                 const int k = tid + a.gl * r;
                 const long m = out_m0 + k;
-                if (tid < a.gl && r < a.R && k < a.tile && m < a.n_out) yb[m] = outv[r];
+                if (tid < a.gl && r < a.R && k < a.tile && m < n_out) yb[m] = outv[r];
             }
         }
     };
@@ -2118,10 +2159,10 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
 #pragma unroll 1
     for (int it = 0; it < RS_SUBS; ++it) {
         const long m0 = m_wg0 + (long)it * a.tile;
-        if (m0 >= a.n_out) break;                                   // uniform
+        if (m0 >= n_out) break;                                     // uniform
         if constexpr (MIX == MIX_NONE) stage(nt - (T - 1), icst<0>{});
         else if (mode == 0) stage(nt - (T - 1), icst<0>{});
-        else if constexpr (MIX == MIX_NCO) stage(nt - (T - 1), icst<3>{});
+        else if constexpr (mix_is_nco(MIX)) stage(nt - (T - 1), icst<3>{});
         else if (mode == 1) stage(nt - (T - 1), icst<1>{});
         else stage(nt - (T - 1), icst<2>{});
         phase_sync();
@@ -2130,7 +2171,7 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
         const unsigned dn = un / (unsigned)L;                       // the window moves on by dn samples
         const long nt_next = nt + dn;
         const int pt_next = (int)(un % (unsigned)L);
-        load(nt_next - (T - 1), it == RS_SUBS - 1 || m0 + a.tile >= a.n_out);
+        load(nt_next - (T - 1), it == RS_SUBS - 1 || m0 + a.tile >= n_out);
 
         const unsigned ul = (unsigned)pt + (unsigned)tid * (unsigned)M;
         const int q0 = (int)(ul / (unsigned)L), ph = (int)(ul % (unsigned)L);
@@ -2149,7 +2190,7 @@ __device__ __forceinline__ void resample_body(const RsArgs& a, const TuneArgs* t
         out_m0 = m0;
         nt = nt_next; pt = pt_next;
         if constexpr (MIX == MIX_RATIONAL) rb = (rb + dn % D) % D;
-        if constexpr (MIX == MIX_NCO) rb += inc * dn;
+        if constexpr (mix_is_nco(MIX)) rb += inc * dn;
         phase_sync();                                               // every lane's window reads precede the next staging
     }
     flush();
@@ -2160,6 +2201,11 @@ template <int FMT, bool LUTM>
 __global__ __launch_bounds__(WV, RS_WPS) void k_tune(TuneArgs ta, WideConv cv) { resample_body<FMT, LUTM, MIX_RATIONAL>(ta.r, &ta, cv); }
 template <int FMT, bool LUTM>
 __global__ __launch_bounds__(WV, RS_WPS) void k_tune_nco(TuneArgs ta, WideConv cv) { resample_body<FMT, LUTM, MIX_NCO>(ta.r, &ta, cv); }
+template <int FMT, bool LUTM>
+__global__ __launch_bounds__(WV, RS_WPS) void k_tune_cuts(TuneArgs ta, CutArgs ca, WideConv cv)
+{
+    resample_body<FMT, LUTM, MIX_CUTS>(ta.r, &ta, cv, &ca);
+}
 // One NCO channel's record (step, ph0) rewritten in stream order: launches issued before it on the stream have read the old one,
 // launches after it read the new one (p25fe_afc_set_step)
 __global__ void k_afc_set_ch(TuneCh* ch, int step, unsigned ph0)

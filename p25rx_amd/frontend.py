@@ -740,6 +740,10 @@ class Tuner:
                                            C.c_void_p(out.data_ptr()), out.stride(0) // 2, self.fe._stream()))
         return out, no
 
+    def cuts(self, cuts):
+        """the cuts of docs/SPEC.md 3.0j on this (NCO) tuner: a structured array of _lib.CUT_DTYPE, or (abs_first, n, step, ph0) tuples"""
+        return Cuts(self, cuts)
+
     def tune(self, iq, cap=None):
         """host streaming form: the capture's next samples (complex64 [n], int16 or uint8 interleaved pairs [2 n]) -> complex64
         [K, n_out]; the object keeps the history and the position between calls"""
@@ -758,6 +762,62 @@ class Tuner:
         no = C.c_size_t(0)
         _lib.check(self.lib, self.fe.h, self.lib.p25fe_tune(self.tn, _p(iq), fmt, n, _p(out), cap, C.byref(no)))
         return out[:, :no.value].copy()
+
+
+class Cuts:
+    """Cuts of one capture (docs/SPEC.md 3.0j, p25fe_cuts_t): J pieces {abs_first, n, step, ph0} tuned in ONE launch, each the slice of
+    the row Tuner.tune_dev writes for an NCO channel (step, ph0) over the whole range, bit for bit.  Made on an NCO tuner (its table,
+    rotator and device; its own channels are not used), which must outlive every use.  counts[j] is cut j's output count."""
+
+    @staticmethod
+    def from_keys(keys, N, hop, B, fs_hz, margin=0, range_first=0, range_n=0):
+        """Scanner.keys' intervals -> cuts (structured array of _lib.CUT_DTYPE), clipped to [range_first, range_first + range_n)
+        (p25fe_cuts_from_keys; needs no device)"""
+        L_ = _lib.load()
+        keys = np.ascontiguousarray(keys, dtype=_lib.WATERFALL_KEY_DTYPE)
+        out = np.zeros(max(keys.size, 1), dtype=_lib.CUT_DTYPE)
+        n = C.c_size_t(0)
+        _lib.check(L_, None, L_.p25fe_cuts_from_keys(_p(keys), keys.size, int(N), int(hop), int(B), int(fs_hz), int(margin),
+                                                     int(range_first), int(range_n), _p(out), out.size, C.byref(n)))
+        return out[:n.value].copy()
+
+    def __init__(self, tuner, cuts):
+        self.tuner, self.fe, self.lib = tuner, tuner.fe, tuner.lib
+        if not (isinstance(cuts, np.ndarray) and cuts.dtype == _lib.CUT_DTYPE):
+            cuts = np.array([tuple(int(v) for v in c) for c in cuts], dtype=_lib.CUT_DTYPE)
+        self.cuts = np.ascontiguousarray(cuts).reshape(-1)
+        self.J = int(self.cuts.size)
+        counts = np.zeros(max(self.J, 1), dtype=np.uintp)
+        mx = C.c_size_t(0)
+        self.ct = C.c_void_p()
+        _lib.check(self.lib, self.fe.h, self.lib.p25fe_cuts_create(tuner.tn, _p(self.cuts), self.J, _p(counts), C.byref(mx), C.byref(self.ct)))
+        self.counts = [int(c) for c in counts[:self.J]]
+        self.max_count = int(mx.value)
+
+    def close(self):
+        if getattr(self, "ct", None):
+            self.lib.p25fe_cuts_destroy(self.ct)
+            self.ct = None
+
+    __del__ = close
+
+    def tune_dev(self, iq, n_hist=0, abs0=0, offset=0, out=None, stride=None):
+        """cf32, int16 or uint8 [n, 2] on the device -> cf32 [J, stride, 2]: row j holds counts[j] samples and, where this call makes
+        the rows, zeros behind them (stride: even, at least max_count, max_count rounded up by default; rows 16-byte aligned), so the
+        rows feed a J-channel FrontEnd's run_dev as they are.  A given `out` is written in [0, counts[j]) of each row only."""
+        import torch
+        assert iq.is_cuda and iq.dim() == 2 and iq.shape[1] == 2 and iq.is_contiguous()
+        fmt = _torch_fmt(iq.dtype)
+        n = iq.shape[0] - offset
+        if out is None:
+            if stride is None:
+                stride = (self.max_count + 3) // 2 * 2
+            assert stride % 2 == 0
+            out = torch.zeros((self.J, stride, 2), dtype=torch.float32, device=iq.device)
+        _lib.check(self.lib, self.fe.h,
+                   self.lib.p25fe_cuts_dev(self.ct, C.c_void_p(iq.data_ptr() + fmt_bytes(fmt) * offset), fmt, n_hist, n, abs0,
+                                                C.c_void_p(out.data_ptr()), out.stride(0) // 2, self.fe._stream()))
+        return out
 
 
 class Afc:

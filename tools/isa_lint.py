@@ -4,7 +4,7 @@
 lds_issue_b64 / lds_landed* (p25fe_kernels.hip) define VGPRs from `asm volatile("ds_read_b64 ...")` that the compiler
 believes are ready while the LDS read is still in flight; correctness rests on the explicit `s_waitcnt lgkmcnt(n)` asm in
 front of every use AND on the compiler never touching such a register in between (a copy, a coalescing move, a spill).
-This script walks the generated gfx950 assembly of every k_frontend / k_frontend_pair / k_chunk / k_resample / k_tune / k_tune_nco / k_afc_measure
+This script walks the generated gfx950 assembly of every k_frontend / k_frontend_pair / k_chunk / k_resample / k_tune / k_tune_nco / k_tune_cuts / k_afc_measure
 kernel and checks exactly that:
 
   * every inline-asm `ds_read_b64 v[a:b]` puts (a, b) on an in-flight list (LDS operations of a wave return in order);
@@ -32,7 +32,7 @@ def regs_of(text):
 def lint(path):
     src = open(path).read()
     bad, warn, n_kernels, n_reads = [], [], 0, 0
-    for m in re.finditer(r"^(_ZN4p25k(?:10k_frontend|15k_frontend_pair|7k_chunk|10k_resample|6k_tune|10k_tune_nco|13k_afc_measure)\w+):[^\n]*\n", src, re.M):
+    for m in re.finditer(r"^(_ZN4p25k(?:10k_frontend|15k_frontend_pair|7k_chunk|10k_resample|6k_tune|10k_tune_nco|11k_tune_cuts|13k_afc_measure)\w+):[^\n]*\n", src, re.M):
         name = m.group(1)
         end = src.index(".Lfunc_end", m.end())
         lines = src[m.end():end].split("\n")
