@@ -2,10 +2,11 @@
 it IS K0, and against itself across formats, ranges, positions and chunkings.
 
 The bit-exact cases use random, ASYMMETRIC tables: a designed prototype is symmetric and would hide a reversed tap or phase order.
-A sub-tile of the kernel holds at most 256 outputs and a workgroup at most four sub-tiles; what the launch makes of a ratio is
-smaller (180 outputs per sub-tile at 12/125 and 15/128, 17 at 3/250, 192 at 24/25 and 1/10, 128 at 2/25), so the parity sizes below --
-2400 to 3935 outputs -- cover at least two full workgroups and a partial one at every ratio, and would still cover two of the largest
-workgroup the kernel could ever be given (1024 outputs) plus a partial one."""
+A sub-tile of the kernel holds at most 256 outputs and a workgroup at most four sub-tiles.  No case of THIS file reaches that: what
+the launch makes of its ratios is 180 outputs per sub-tile at 12/125 and 15/128, 17 at 3/250, 192 at 24/25 and 1/10, 128 at 2/25, so
+the parity sizes below -- 2400 to 3935 outputs -- cover at least two full workgroups and a partial one at every ratio here.  The
+256-output sub-tile, every other launch plan the shape limits admit (lane counts, outputs per lane, tiles down to one output) and
+the tap loop's short paths are run by tests/test_gpu_resample_shapes.py on tests/resample_shapes.py's table."""
 import numpy as np
 import pytest
 

@@ -11,10 +11,10 @@ import numpy as np
 
 import afc_model as AM
 import resample_model as RM
+from resample_shapes import RS_NIN, RS_R, RS_SUBS, WV, plan          # the kernel's window, register block, sub-tiles and wave
 
 MASK = (1 << 32) - 1
 CUTS_MAX = 4096
-RS_NIN, RS_R, RS_SUBS, WV = 2040, 4, 4, 64                           # the kernel's window, register block, sub-tiles and wave
 
 
 def nco_step(fs, offset_hz):
@@ -47,9 +47,7 @@ def slice_of(L, M, call_first, cut_first, cut_n):
 
 def tile(L, M, T):
     """outputs per sub-tile: the host plan's fit of the sub-tile to the window (rs_fill_args)"""
-    fit = 1 + (RS_NIN - T) * L // M
-    gl = WV - WV % L
-    return gl * min(fit // gl, RS_R) if fit >= gl else fit
+    return plan(L, M, T)[3]
 
 
 def wg_counts(L, M, T, cuts):
