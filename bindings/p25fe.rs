@@ -240,6 +240,10 @@ pub struct Cut {
 }
 pub const CUTS_MAX: usize = 4096;
 pub enum Cuts {}
+/// p25fe_keys_t: the keyed intervals of docs/SPEC.md 3.0k computed on the device (made from a Scan, which must outlive it)
+pub enum Keys {}
+/// P25FE_KEYS_MAX_CHANNELS: the eligible raster channels a Keys object admits
+pub const KEYS_MAX_CHANNELS: usize = 4096;
 /// P25FE_TUNE_MAX_CH / _DEN: 1 <= channels <= 256; num / den in lowest terms, 1 <= den <= 8192, 2 |num| <= den
 pub const TUNE_MAX_CH: i32 = 256;
 pub const TUNE_MAX_DEN: i32 = 8192;
@@ -362,6 +366,12 @@ extern "C" {
     pub fn p25fe_cuts_destroy(ct: *mut Cuts);
     pub fn p25fe_cuts_dev(ct: *mut Cuts, d_iq: *const c_void, fmt: c_int, n_hist: usize, n: usize, abs_first: u64,
                           d_out: *mut f32, out_stride: usize, stream: *mut c_void) -> c_int;
+    pub fn p25fe_keys_create(sc: *mut Scan, fs_hz: u32, raster_hz: f64, half_bw_hz: f64, on_db: f64, off_db: f64, min_slots: u32,
+                             max_rows: usize, max_keys: usize, out: *mut *mut Keys) -> c_int;
+    pub fn p25fe_keys_destroy(kp: *mut Keys);
+    pub fn p25fe_keys_dev(kp: *mut Keys, d_rows: *const u64, n_rows: usize, row_stride: usize, slot0: u64, stream: *mut c_void) -> c_int;
+    pub fn p25fe_keys_stream(kp: *mut Keys) -> c_int;
+    pub fn p25fe_keys_read(kp: *mut Keys, out: *mut WaterfallKey, cap: usize, n_out: *mut usize) -> c_int;
     pub fn p25fe_n_baseband(abs0: u64, n: usize) -> usize;
     pub fn p25fe_slice_dev(h: *mut Handle, d_bb: *const f32, bb_stride: usize, n_hist_bb: usize, n_bb: usize, abs_bb0: u64,
                            d_anchor_in: *const Anchor, d_dibits: *mut u8, dibit_stride: usize, d_sync_pos: *mut i64,

@@ -777,6 +777,37 @@ void p25fe_cuts_destroy(p25fe_cuts_t *ct);
 int p25fe_cuts_dev(p25fe_cuts_t *ct, const void *d_iq, int fmt, size_t n_hist, size_t n, uint64_t abs_first,
                    float *d_out, size_t out_stride, void *stream);
 
+/* ---- survey over time, keys on the device: the keyed intervals computed where the rows are (docs/SPEC.md 3.0k) -----------------------
+ * p25fe_waterfall_keys is the definition; an object of this section returns the same bytes -- the count and the whole 48-byte
+ * records -- for the same rows and parameters without the rows leaving the device.  The object is the plan of one raster over a
+ * p25fe_scan_t's N on its device; a run enqueues a fixed number of launches and leaves a few raw records on the device; _read
+ * waits for the run, copies them back and finishes them on the host (the centroid's quotient and 10 log10 of the largest ratio).
+ * The caller orders the calls on one object, as it orders the rows. */
+#define P25FE_KEYS_MAX_CHANNELS 4096
+typedef struct p25fe_keys p25fe_keys_t;
+/* Builds the raster (p25fe_waterfall_keys' own), uploads it and allocates all scratch; synchronous.  sc must outlive every USE of
+ * the object (p25fe_keys_destroy alone is safe after it is gone).  Every argument is checked before any device is touched.
+ * P25FE_ERR_ARG: p25fe_waterfall_keys' refusals, a null sc or out, max_rows = 0 or > 2^20, max_keys = 0 or > 2^20.
+ * P25FE_ERR_CAPACITY (limits of the device form; the host function has none): more than P25FE_KEYS_MAX_CHANNELS eligible channels,
+ * max_rows * (channels + 1) > 2^28 words of scratch.  A raster with no eligible channel is a valid object whose runs find no key. */
+int p25fe_keys_create(p25fe_scan_t *sc, uint32_t fs_hz, double raster_hz, double half_bw_hz, double on_db, double off_db,
+                      uint32_t min_slots, size_t max_rows, size_t max_keys, p25fe_keys_t **out);
+void p25fe_keys_destroy(p25fe_keys_t *kp);
+/* One run over d_rows[n_rows][row_stride] (device, 8-byte aligned; p25fe_waterfall_dev's rows, row i standing for slot slot0 + i):
+ * four launches on `stream`, a memset among them, whatever n_rows and the raster are; synchronises nothing, reads nothing back and
+ * never writes d_rows.  The run replaces the object's previous result; n_rows = 0 is P25FE_OK and a result of no key.
+ * P25FE_ERR_ARG (before any device is touched): d_rows null or misaligned, row_stride < N + 1.  P25FE_ERR_CAPACITY: n_rows >
+ * max_rows. */
+int p25fe_keys_dev(p25fe_keys_t *kp, const uint64_t *d_rows, size_t n_rows, size_t row_stride, uint64_t slot0, void *stream);
+/* The same run over the rows of sc's open host-streaming waterfall: the rows touched so far (p25fe_waterfall_read's count), slot0 =
+ * 0, on the handle's stream behind the p25fe_waterfall calls made so far.  P25FE_ERR_ARG: no open waterfall. */
+int p25fe_keys_stream(p25fe_keys_t *kp);
+/* Waits for the last run (an event recorded behind it) and returns its keys with p25fe_waterfall_keys' contract for out, cap and
+ * n_out, sorted by first_slot, then raster_index.  One difference: a run that found more than max_keys intervals is
+ * P25FE_ERR_CAPACITY with *n_out the true count and nothing written -- the device emits in no particular order, so there is no
+ * sorted prefix.  Before any run: P25FE_OK and no key. */
+int p25fe_keys_read(p25fe_keys_t *kp, p25fe_waterfall_key_t *out, size_t cap, size_t *n_out);
+
 /* stages 6-7 on device baseband.  d_bb points at the first owned sample; n_hist_bb valid
  * samples precede it; abs_bb0 is its absolute index; d_anchor_in (nullable = no lock) is the
  * carry-in per channel.  d_result[c] is filled per channel.

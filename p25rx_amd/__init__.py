@@ -1,1 +1,1 @@
-from .scan import Scanner  # noqa: F401
+from .scan import Keys, Scanner  # noqa: F401

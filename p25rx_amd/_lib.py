@@ -82,6 +82,7 @@ assert WATERFALL_KEY_DTYPE.itemsize == 48
 CUT_DTYPE = np.dtype([("abs_first", "<u8"), ("n", "<u8"), ("step", "<i4"), ("ph0", "<u4")])   # p25fe_cut_t
 assert CUT_DTYPE.itemsize == 24
 CUTS_MAX = 4096
+KEYS_MAX_CHANNELS = 4096                                            # P25FE_KEYS_MAX_CHANNELS
 
 # every symbol include/p25fe.h declares (tests check the library exports exactly these)
 SYMBOLS = [
@@ -111,6 +112,7 @@ SYMBOLS = [
     "p25fe_waterfall_slots", "p25fe_waterfall_dev", "p25fe_waterfall_open", "p25fe_waterfall", "p25fe_waterfall_read",
     "p25fe_waterfall_keys",
     "p25fe_cuts_from_keys", "p25fe_cuts_create", "p25fe_cuts_destroy", "p25fe_cuts_dev",
+    "p25fe_keys_create", "p25fe_keys_destroy", "p25fe_keys_dev", "p25fe_keys_stream", "p25fe_keys_read",
     "p25fe_debug_planes_size", "p25fe_debug_planes_dev",
 ]
 
@@ -269,6 +271,12 @@ def load():
     L.p25fe_cuts_destroy.argtypes = [vp]
     L.p25fe_cuts_destroy.restype = None
     L.p25fe_cuts_dev.argtypes = [vp, vp, C.c_int, sz, sz, u64, vp, sz, vp]
+    L.p25fe_keys_create.argtypes = [vp, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_uint32, sz, sz, C.POINTER(vp)]
+    L.p25fe_keys_destroy.argtypes = [vp]
+    L.p25fe_keys_destroy.restype = None
+    L.p25fe_keys_dev.argtypes = [vp, vp, sz, sz, u64, vp]
+    L.p25fe_keys_stream.argtypes = [vp]
+    L.p25fe_keys_read.argtypes = [vp, vp, sz, psz]
     L.p25fe_n_predecim.argtypes = [u64, sz]
     L.p25fe_n_predecim.restype = sz
     L.p25fe_n_baseband.argtypes = [u64, sz]

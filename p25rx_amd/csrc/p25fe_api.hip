@@ -3268,3 +3268,4 @@ P25FE_M_API_EXTRAS
 #include "p25fe_scan.inc"       // survey (SPEC 3.0h): k_scan and its entry points
 #include "p25fe_waterfall.inc"  // survey over time (SPEC 3.0i): k_waterfall and its entry points
 #include "p25fe_cuts.inc"       // tuner, cuts (SPEC 3.0j): the entry points of k_tune_cuts
+#include "p25fe_keys.inc"       // survey over time, keys on the device (SPEC 3.0k): k_keys_pow / _walk / _cell and their entry points

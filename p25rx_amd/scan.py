@@ -11,6 +11,12 @@ and, with a time axis (3.0i: kernel k_waterfall, one launch for all slots), whic
     rows = sc.waterfall_dev(capture, B=12)                     # int64 [n_slots, N + 1] on the device: one record per slot of B frames
     for k in Scanner.keys(rows.cpu().numpy(), fs):             # by first slot: raster_index, first_slot, n_slots, offset_hz, ...
 
+and the same keys without the rows leaving the device (3.0k: three kernels and a memset, the same bytes as Scanner.keys):
+
+    kp = sc.keys_plan(fs, max_rows=256, max_keys=64)
+    kp.run_dev(rows)                                           # behind waterfall_dev on the same stream; synchronises nothing
+    for k in kp.read():                                        # waits for the run; only the keys cross the bus
+
 torch supplies device memory and streams only; all arithmetic on the samples happens in libp25fe.so.
 """
 import ctypes as C
@@ -185,6 +191,11 @@ class Scanner:
                                                 int(B), int(slot0), ptr, rows.shape[0], stride, self.fe._stream()))
         return rows
 
+    def keys_plan(self, fs_hz, raster_hz=12500.0, half_bw_hz=4000.0, on_db=20.0, off_db=14.0, min_slots=2, max_rows=1024, max_keys=1024):
+        """a Keys object for this survey's N and device: Scanner.keys' rule with these parameters, run on the device over up to
+        max_rows rows for up to max_keys intervals"""
+        return Keys(self, fs_hz, raster_hz, half_bw_hz, on_db, off_db, min_slots, max_rows, max_keys)
+
     def open_waterfall(self, B, max_rows):
         """the host streaming form gets rows: [max_rows, N + 1] zeroed on the device, for slots of B frames from slot 0"""
         _lib.check(self.lib, self.fe.h, self.lib.p25fe_waterfall_open(self.sc, int(B), int(max_rows)))
@@ -205,3 +216,57 @@ class Scanner:
         if n.value:
             _lib.check(self.lib, self.fe.h, self.lib.p25fe_waterfall_read(self.sc, _p(rows), n.value, C.byref(n)))
         return rows
+
+
+class Keys:
+    """Scanner.keys on the device (p25fe_keys_t, docs/SPEC.md 3.0k): the plan of one raster over a Scanner's N, which must outlive
+    it.  A run enqueues four launches on the front end's stream and synchronises nothing; read() waits for the last run and returns
+    the bytes Scanner.keys returns for the same rows and parameters."""
+
+    def __init__(self, scanner, fs_hz, raster_hz=12500.0, half_bw_hz=4000.0, on_db=20.0, off_db=14.0, min_slots=2, max_rows=1024,
+                 max_keys=1024):
+        self.scanner, self.lib = scanner, scanner.lib
+        self.max_rows, self.max_keys = int(max_rows), int(max_keys)
+        self.kp = C.c_void_p()
+        _lib.check(self.lib, scanner.fe.h,
+                   self.lib.p25fe_keys_create(scanner.sc, int(fs_hz), float(raster_hz), float(half_bw_hz), float(on_db), float(off_db),
+                                              int(min_slots), self.max_rows, self.max_keys, C.byref(self.kp)))
+
+    def close(self):
+        if getattr(self, "kp", None):
+            self.lib.p25fe_keys_destroy(self.kp)
+            self.kp = None
+
+    __del__ = close
+
+    def run_dev(self, rows, slot0=0, n_rows=None):
+        """rows as waterfall_dev returns them (int64 [n, >= N + 1] on the device, row 0 standing for slot `slot0`; the stride is
+        the tensor's; n_rows: the first so many, None: all) -> the object's result, replacing the previous one.  The rows are
+        read, never written."""
+        assert rows.is_cuda and rows.element_size() == 8 and rows.dim() == 2 and rows.stride(1) == 1
+        n = rows.shape[0] if n_rows is None else int(n_rows)
+        assert 0 <= n <= rows.shape[0]
+        stride = rows.stride(0) if rows.shape[0] > 1 else rows.shape[1]
+        _lib.check(self.lib, self.scanner.fe.h,
+                   self.lib.p25fe_keys_dev(self.kp, C.c_void_p(rows.data_ptr()), n, stride, int(slot0), self.scanner.fe._stream()))
+
+    def run_stream(self):
+        """the same run over the rows of the scanner's open host-streaming waterfall touched so far, from slot 0"""
+        _lib.check(self.lib, self.scanner.fe.h, self.lib.p25fe_keys_stream(self.kp))
+
+    def read(self, cap=None):
+        """waits for the last run -> its keyed intervals by first slot, then raster index, as a structured array of
+        WATERFALL_KEY_DTYPE; with cap the first cap of them and the count, (keys, n_intervals).  A run that found more than
+        max_keys intervals raises P25feError with status ERR_CAPACITY and the true count in its `count`."""
+        n = C.c_size_t(0)
+        want = self.max_keys if cap is None else int(cap)
+        out = np.zeros(max(want, 1), dtype=WATERFALL_KEY_DTYPE)
+        rc = self.lib.p25fe_keys_read(self.kp, _p(out), want, C.byref(n))
+        if rc != _lib.OK:
+            try:
+                _lib.check(self.lib, self.scanner.fe.h, rc)
+            except _lib.P25feError as e:
+                e.count = n.value
+                raise
+        got = out[:min(n.value, want)].copy()
+        return got if cap is None else (got, n.value)
