@@ -53,6 +53,7 @@ def bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
+import chz_model as CM
 from spec_model import grid_count as cnt       # samples i of [abs0, abs0 + n) with i % step == phase, in Python integers
 
 
@@ -151,8 +152,9 @@ def test_demod_dev_with_real_history_cf32_and_u8(O, FE, c4fm_1s, spec, bound, va
 
 @pytest.mark.parametrize("two", [31, 32, 40, 56])
 def test_predecim_and_channelise_at_large_abs0(O, FE, spec, two):
-    """p25fe_predecim_dev (bit-exact) and p25fe_channelise_dev (the tolerance test_channeliser_parity_and_end_to_end derives:
-    2e-6 * sum|h| * max|x|) with abs0 straddling 2^31, 2^32, 2^40 and 2^56 wideband samples, over all ten residues of the 10:1 grid.
+    """p25fe_predecim_dev (bit-exact) and p25fe_channelise_dev (the tolerance of test_channeliser_parity_and_end_to_end: per output
+    (2e-6 + 2^-24) * T of tests/chz_model.py, and never more than 2e-6 * sum|h| * max|x|) with abs0 straddling 2^31, 2^32, 2^40
+    and 2^56 wideband samples, over all ten residues of the 10:1 grid.
     References: the oracle's pre-decimator with P % 10 zeros in front; oracle.channelise at P' = P mod lcm(10, 192) AND at P itself."""
     hsum = float(np.abs(np.array(spec["pre_taps"], dtype=np.float64)).sum())
     rng = np.random.default_rng(two)
@@ -177,7 +179,7 @@ def test_predecim_and_channelise_at_large_abs0(O, FE, spec, two):
         z, nz = fe.channelise_dev(t, n_hist=0, abs0=P)
         assert nz == no_want
         got = z[:, :nz].cpu().numpy().view(np.complex64)[..., 0]
-        assert np.abs(got - small).max() <= tol, (two, r, float(np.abs(got - small).max()), tol)
+        CM.within(got, x, 0, P, k=CM.K_SPEC + CM.U, ref=small, cap=tol, what="2^%d, r = %d" % (two, r))
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
